@@ -16,6 +16,10 @@ in HBM before the timed region starts.
   python bench.py --gpus N --total-batch 262144                  strong scaling: BASELINE config 4, the same
                                                                  262 144 filters over 1 / 2 / 4 / 8 GPUs
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...      (what the driver runs)
+  python bench.py ... --full                                     also every side leg described below (a plain run sets up, warms up,
+                                                                 times the K steps and prints the line: `value`, `ms_per_step`,
+                                                                 `roofline` from the HIP events inside the timed region)
+  python bench.py ... --dump-outputs DIR                         the state the timed steps left, as DIR/<name>.npy (dump_outputs)
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment starts the N rank processes itself
 (`python -m torch.distributed.run ...` as a CHILD process, before this process has touched the GPU),
@@ -105,7 +109,16 @@ def parse():
                          "the per-kernel HIP-event timing then comes from a short eager pass after the timed region")
     ap.add_argument("--kernel-timing", choices=["on", "off"], default="on",
                     help="bracket runs of launches with HIP events inside the timed region (feeds `roofline`)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: fused frame / window, the end-of-run gather and state check, the "
+                         "large-batch roofline legs, fp64, north_star_rows and the CPU baseline (the --no-* options trim this set)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (what BatchedFilter.get_state / applied return) as "
+                         "DIR/<name>.npy; with N ranks, rank 0's filters")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------
@@ -379,6 +392,28 @@ def _timed(torch, fn, steps, warmup, barrier, before_timing):
         sys.stderr.write("host submit ms per step: " + " ".join(f"{(b - a) * 1e3:.2f}" for a, b in zip([0.0] + marks, marks[:-1])) +
                          f" | submitted at {marks[-1] * 1e3:.2f} ms, GPU done at {el * 1e3:.2f} ms\n")
     return el
+
+
+DUMP_BYTES = 64 * 10**6             # --dump-outputs: all files together stay below this
+
+
+def dump_outputs(path, flt):
+    """--dump-outputs: the state the timed steps left, as a caller of the per-call API receives it (get_state + applied), one .npy
+    per array in the records' float type (marker ids and indices as float64: exact).  When all filters do not fit in DUMP_BYTES a
+    fixed, seeded sample of them is written -- the same filters in every array, named by `filter_index`."""
+    nominal, rot, P, prev = flt.get_state()
+    fdt = nominal.dtype
+    arrays = {"nominal": nominal, "rot": rot, "P": P, "prev_marker": prev.astype(np.float64),
+              "applied": flt.applied().astype(fdt)}
+    per_filter = sum(a[0].nbytes for a in arrays.values()) + 8          # + filter_index
+    B = nominal.shape[0]
+    n = min(B, (DUMP_BYTES - 4096 * (len(arrays) + 1)) // per_filter)      # (npy headers)
+    idx = np.arange(B) if n == B else np.sort(np.random.default_rng(0).choice(B, n, replace=False))
+    arrays = {k: v[idx] for k, v in arrays.items()}
+    arrays["filter_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
 
 
 def roofline_block(w, pred_ms, pred_n, corr_ms, corr_n, traffic, traffic_src):
@@ -847,6 +882,8 @@ def main():
 
     elapsed = timed(torch, bench_step, args.steps, args.warmup, barrier, clear)
     elapsed = shard.max_over_ranks(elapsed, dist, world, ctl_dev)
+    if args.dump_outputs and rank == 0:                     # before anything below steps the filters again
+        dump_outputs(args.dump_outputs, flt)
 
     if args.graphs and args.kernel_timing == "on":          # events cannot live inside a graph: short eager pass
         flt.timing_reset()
@@ -857,52 +894,54 @@ def main():
     corr_ms, corr_n = flt.timing_read(capi.KERNEL_CORRECT)
     flt.timing_enable(False)
 
-    # ---- extra (never `value`): the same frames through the fused one-launch-per-frame kernel ----
-    w.reset_state()
-    fused_elapsed = timed(torch, lambda i: w.step(i, fused=True), args.steps, args.warmup, barrier)
-    fused_elapsed = shard.max_over_ranks(fused_elapsed, dist, world, ctl_dev)
-    flt._keep.clear()
+    # everything below up to the result line runs with --full only: a plain run times the headline and reports it
+    if args.full:
+        # ---- extra (never `value`): the same frames through the fused one-launch-per-frame kernel ----
+        w.reset_state()
+        fused_elapsed = timed(torch, lambda i: w.step(i, fused=True), args.steps, args.warmup, barrier)
+        fused_elapsed = shard.max_over_ranks(fused_elapsed, dist, world, ctl_dev)
+        flt._keep.clear()
 
-    # ---- extra (never `value`): the same steps, each as ONE launch of the frame-window kernel ----
-    w.reset_state()
-    w.build_windows()
-    window_elapsed = timed(torch, w.step_window, args.steps, args.warmup, barrier)
-    window_elapsed = shard.max_over_ranks(window_elapsed, dist, world, ctl_dev)
-    flt._keep.clear()
-    w.windows = None
+        # ---- extra (never `value`): the same steps, each as ONE launch of the frame-window kernel ----
+        w.reset_state()
+        w.build_windows()
+        window_elapsed = timed(torch, w.step_window, args.steps, args.warmup, barrier)
+        window_elapsed = shard.max_over_ranks(window_elapsed, dist, world, ctl_dev)
+        flt._keep.clear()
+        w.windows = None
 
-    # ---- the single end-of-run collective: gather the packed records (timed separately) ----
-    # Through the LIBRARY: fbus_ekf_gather issues ncclAllGather (equal shards) / a grouped ncclBroadcast per rank (ragged shards)
-    # on the handle's stream with the library's own communicator -- also with one rank, so that a 1-GPU run exercises the same
-    # call.  torch.distributed only carries the 128-byte unique id.  The gloo rehearsal on a shared GPU
-    # (FBUS_BENCH_DEBUG_SHARED_GPU) cannot use RCCL (two ranks on one device) and keeps the torch path.
-    gather_via = "torch.distributed"
-    sizes = shard.record_bytes_of_ranks(args.total_batch, world, w.bpf) if strong else None
-    if not shared and os.environ.get("FBUS_BENCH_TORCH_GATHER") != "1":
-        failed = 0.0
-        try:
-            shard.native_comm_init(flt, rank, world, dist, ctl_dev)
-        except Exception as e:                       # no RCCL on this box: say so, fall back
-            failed = 1.0
-            sys.stderr.write(f"bench.py: native RCCL communicator unavailable on rank {rank} ({e}); gathering through torch.distributed\n")
-        # the choice is collective: one rank without the communicator and everybody takes the torch path
-        if shard.max_over_ranks(failed, dist, world, ctl_dev) == 0.0:
-            gather_via = "fbus_ekf_gather (RCCL inside the library)"
-    torch.cuda.synchronize()
-    barrier()
-    tg = time.perf_counter()
-    if gather_via.startswith("fbus_ekf_gather"):
-        gathered = shard.gather_records_native(flt, w.rec, sizes, world)
-    else:
-        gathered = shard.gather_records(w.rec.cpu() if ctl_dev == "cpu" else w.rec, dist, world) if not strong else \
-            shard.gather_records_ragged(w.rec.cpu() if ctl_dev == "cpu" else w.rec, dist, world, ctl_dev)
-    torch.cuda.synchronize()
-    gather_ms = (time.perf_counter() - tg) * 1e3
-    if gather_via.startswith("fbus_ekf_gather"):
-        assert torch.equal(gathered[rank], w.rec), "gathered records differ from this rank's own"
-    nomf, _, Pf, _ = flt.get_state()
-    finite = bool(np.isfinite(nomf).all() and np.isfinite(Pf).all())
-    finite = shard.max_over_ranks(0.0 if finite else 1.0, dist, world, ctl_dev) == 0.0
+        # ---- the single end-of-run collective: gather the packed records (timed separately) ----
+        # Through the LIBRARY: fbus_ekf_gather issues ncclAllGather (equal shards) / a grouped ncclBroadcast per rank (ragged shards)
+        # on the handle's stream with the library's own communicator -- also with one rank, so that a 1-GPU run exercises the same
+        # call.  torch.distributed only carries the 128-byte unique id.  The gloo rehearsal on a shared GPU
+        # (FBUS_BENCH_DEBUG_SHARED_GPU) cannot use RCCL (two ranks on one device) and keeps the torch path.
+        gather_via = "torch.distributed"
+        sizes = shard.record_bytes_of_ranks(args.total_batch, world, w.bpf) if strong else None
+        if not shared and os.environ.get("FBUS_BENCH_TORCH_GATHER") != "1":
+            failed = 0.0
+            try:
+                shard.native_comm_init(flt, rank, world, dist, ctl_dev)
+            except Exception as e:                       # no RCCL on this box: say so, fall back
+                failed = 1.0
+                sys.stderr.write(f"bench.py: native RCCL communicator unavailable on rank {rank} ({e}); gathering through torch.distributed\n")
+            # the choice is collective: one rank without the communicator and everybody takes the torch path
+            if shard.max_over_ranks(failed, dist, world, ctl_dev) == 0.0:
+                gather_via = "fbus_ekf_gather (RCCL inside the library)"
+        torch.cuda.synchronize()
+        barrier()
+        tg = time.perf_counter()
+        if gather_via.startswith("fbus_ekf_gather"):
+            gathered = shard.gather_records_native(flt, w.rec, sizes, world)
+        else:
+            gathered = shard.gather_records(w.rec.cpu() if ctl_dev == "cpu" else w.rec, dist, world) if not strong else \
+                shard.gather_records_ragged(w.rec.cpu() if ctl_dev == "cpu" else w.rec, dist, world, ctl_dev)
+        torch.cuda.synchronize()
+        gather_ms = (time.perf_counter() - tg) * 1e3
+        if gather_via.startswith("fbus_ekf_gather"):
+            assert torch.equal(gathered[rank], w.rec), "gathered records differ from this rank's own"
+        nomf, _, Pf, _ = flt.get_state()
+        finite = bool(np.isfinite(nomf).all() and np.isfinite(Pf).all())
+        finite = shard.max_over_ranks(0.0 if finite else 1.0, dist, world, ctl_dev) == 0.0
     ranks_seen = int(shard.sum_over_ranks(1.0, dist, world, ctl_dev))
 
     if rank == 0:
@@ -930,19 +969,22 @@ def main():
                        "ranks_seen": ranks_seen,
                        "collective_backend": (dist.get_backend() if dist is not None else None)},
             "roofline": roof, "correct_kernel": corr,
-            "fused_frame": {"value": total_steps / fused_elapsed, "unit": "EKF steps/s",
-                            "ms_per_step": fused_elapsed / args.steps * 1e3,
-                            "note": "same frames, one launch per camera frame (K predicts + correct, records "
-                                    "resident in registers); moves 1/(K+1) of the per-call bytes, VALU-bound; "
-                                    "reported beside, never instead of, the per-call number"},
-            "fused_window": {"value": total_steps / window_elapsed, "unit": "EKF steps/s",
-                             "ms_per_step": window_elapsed / args.steps * 1e3, "frames_per_launch": len(PATTERN) * PATTERNS_PER_STEP,
-                             "note": "same steps, one launch per bench step (fbus_ekf_frames_fused_dev: 30 camera frames = 200 "
-                                     "predicts + 30 corrects with the records resident in registers from the first load to the "
-                                     "last store) -- the offline-replay form; beside, never instead of, the per-call number"},
-            "gather_ms": gather_ms, "gathered_bytes": int(sum(g.numel() for g in gathered)), "gather_via": gather_via,
-            "state_finite": finite,
         }
+        if args.full:
+            out.update({
+                "fused_frame": {"value": total_steps / fused_elapsed, "unit": "EKF steps/s",
+                                "ms_per_step": fused_elapsed / args.steps * 1e3,
+                                "note": "same frames, one launch per camera frame (K predicts + correct, records "
+                                        "resident in registers); moves 1/(K+1) of the per-call bytes, VALU-bound; "
+                                        "reported beside, never instead of, the per-call number"},
+                "fused_window": {"value": total_steps / window_elapsed, "unit": "EKF steps/s",
+                                 "ms_per_step": window_elapsed / args.steps * 1e3, "frames_per_launch": len(PATTERN) * PATTERNS_PER_STEP,
+                                 "note": "same steps, one launch per bench step (fbus_ekf_frames_fused_dev: 30 camera frames = 200 "
+                                         "predicts + 30 corrects with the records resident in registers from the first load to the "
+                                         "last store) -- the offline-replay form; beside, never instead of, the per-call number"},
+                "gather_ms": gather_ms, "gathered_bytes": int(sum(g.numel() for g in gathered)), "gather_via": gather_via,
+                "state_finite": finite,
+            })
     flt.close()
     del w
 
@@ -973,7 +1015,11 @@ def main():
         out["roofline_hbm_resident"] = out["roofline_b262144"] = out["fp64"] = out["north_star_rows"] = None
         # legs this line does NOT carry, and why (an N > 1 line has none of the single-GPU side legs: say so instead of nulls)
         skipped = []
-        if world > 1 or strong:
+        if not args.full:
+            skipped += [f"{leg}: side leg, run with --full" for leg in
+                        ("fused_frame", "fused_window", "gather", "state_finite", "roofline_hbm_resident", "roofline_b262144", "fp64",
+                         "north_star_rows", "cpu_baseline")]
+        elif world > 1 or strong:
             why = f"{world} ranks" if world > 1 else "strong-scaling run (--total-batch)"
             skipped += [f"{leg}: single-GPU side leg, not run with {why}" for leg in
                         ("roofline_hbm_resident", "roofline_b262144", "fp64", "north_star_rows", "cpu_baseline")]
@@ -988,7 +1034,7 @@ def main():
         if world == 1 and not strong and out["roofline"].get("traffic") is None:
             skipped += [f"roofline.traffic: no profiles/r{PROFILE_ROUND:02d}_digest_b{args.batch}.json taken on this configuration (digests of earlier rounds' kernels are not quoted)"]
         out["legs_skipped"] = skipped
-        if world == 1 and not args.no_hbm_leg and not strong and args.batch < MID_LEG_BATCH:
+        if args.full and world == 1 and not args.no_hbm_leg and not strong and args.batch < MID_LEG_BATCH:
             out["roofline_hbm_resident"] = batch_leg(
                 HBM_LEG_BATCH, 2, 16, max(2, min(args.steps, 3)),
                 "same bench pattern at 1 048 576 filters on one GPU: 839 MB of records (three times the 256 MiB Infinity Cache) + "
@@ -999,12 +1045,12 @@ def main():
                 MID_LEG_BATCH, 1, 1, max(2, min(args.steps, 4)),
                 "262 144 filters: 210 MB of records -- PARTLY CACHE-RESIDENT (they fit the 268 MB Infinity Cache; round 2 reported "
                 "this leg as the HBM figure): kept for continuity, the HBM claim is roofline_hbm_resident")
-        if world == 1 and not args.no_extra_legs and not strong:
+        if args.full and world == 1 and not args.no_extra_legs and not strong:
             out["fp64"] = fp64_leg(torch, dev, local_rank, args, capi)
             out["north_star_rows"] = north_star_rows_leg(torch, dev, local_rank, args, capi)
             if not args.no_hbm_leg:
                 out["north_star_rows_hbm_resident"] = north_star_rows_leg(torch, dev, local_rank, args, capi, hbm_resident=True)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         else:
             out["cpu_baseline"] = None

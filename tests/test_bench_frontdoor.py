@@ -3,7 +3,8 @@
 CPU part: `--gpus N` on a box with fewer GPUs fails loudly (no JSON line, non-zero exit), a launcher whose
 WORLD_SIZE disagrees with --gpus is refused, and the ragged gather used by the strong-scaling mode works over gloo.
 GPU part (one GPU is enough): the N > 1 code path rehearsed with all ranks on cuda:0 and gloo for the control
-collectives (FBUS_BENCH_DEBUG_SHARED_GPU=1), weak and strong scaling, started the way the driver's `--gpus N` does.
+collectives (FBUS_BENCH_DEBUG_SHARED_GPU=1), weak and strong scaling, started the way the driver's `--gpus N` does;
+and a plain one-GPU run (no --full) with --dump-outputs.
 """
 import json
 import os
@@ -94,7 +95,7 @@ def _run_bench(extra, env):
     import tempfile
     with tempfile.TemporaryDirectory() as td:
         detail = os.path.join(td, "detail.json")
-        r = subprocess.run([sys.executable, BENCH, "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-leg", "--no-extra-legs",
+        r = subprocess.run([sys.executable, BENCH, "--full", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-hbm-leg", "--no-extra-legs",
                             "--detail-file", detail] + extra, env=env, capture_output=True, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{") and "\"metric\"" in l]
@@ -154,6 +155,39 @@ def test_single_rank_through_rccl_itself():
     assert out["n_gpus"] == 1 and out["config"]["collective_backend"] == "nccl" and out["config"]["ranks_seen"] == 1
     assert out["gathered_bytes"] == 4096 * 800 and out["state_finite"] and out["gather_ms"] > 0
     assert out["gather_via"].startswith("fbus_ekf_gather")          # the records travel through the library's own communicator
+
+
+@pytest.mark.gpu
+def test_plain_run_and_dumped_outputs(tmp_path):
+    """without --full the run times the headline only: exactly --steps timed steps, the contract keys, every side leg named as
+    skipped.  --dump-outputs writes the state the timed steps left: identical from run to run (seeded inputs), and identical with
+    --full, whose side legs start after the dump"""
+    runs = []
+    for extra in ([], [], ["--full", "--no-cpu-baseline", "--no-hbm-leg", "--no-extra-legs"]):
+        d = tmp_path / f"out{len(runs)}"
+        r = subprocess.run([sys.executable, BENCH, "--steps", "2", "--warmup", "1", "--batch", "4096", "--dump-outputs", str(d),
+                            "--detail-file", str(tmp_path / "detail.json")] + extra, env=_env(), capture_output=True, text=True,
+                           timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert sum(f.stat().st_size for f in d.iterdir()) < 64e6
+        runs.append((line, {f.stem: np.load(f) for f in d.glob("*.npy")}))
+    line, out = runs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["dtype"] == "f32" and line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(4096 * 230 * 2 / (line["ms_per_step"] * 2e-3), rel=1e-6)
+    assert line["cpu_baseline"] is None and "fused_frame" not in line and "gather_ms" not in line
+    assert {"fused_frame", "fused_window", "gather", "fp64", "north_star_rows", "cpu_baseline"} <= set(line["legs_skipped"])
+    assert "fused_frame" in runs[2][0] and "gather_ms" in runs[2][0]
+    assert set(out) == {"nominal", "rot", "P", "prev_marker", "applied", "filter_index"}
+    assert out["nominal"].shape == (4096, 19) and out["rot"].shape == (4096, 9) and out["P"].shape == (4096, 18, 18)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values()) and out["nominal"].dtype == np.float32
+    assert np.array_equal(out["filter_index"], np.arange(4096))
+    assert np.isfinite(out["nominal"]).all() and np.isfinite(out["P"]).all() and out["applied"].any()
+    for _, other in runs[1:]:
+        for name, a in out.items():
+            np.testing.assert_array_equal(other[name], a, err_msg=name)
 
 
 @pytest.mark.gpu

@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -80,3 +81,41 @@ def test_non_finite_numbers_do_not_break_the_line(canned):
     line = json.loads(bench.compact_line(out))                # strict JSON: no NaN token
     assert line["correct_kernel"]["avg_launch_us"] is None
     assert "NaN" not in bench.compact_line(out)
+
+
+class _FakeFilter:
+    """what dump_outputs reads of a BatchedFilter: get_state() and applied() of B filters"""
+
+    def __init__(self, B, dtype):
+        rng = np.random.default_rng(3)
+        self.state = (rng.normal(size=(B, 19)).astype(dtype), rng.normal(size=(B, 9)).astype(dtype),
+                      rng.normal(size=(B, 18, 18)).astype(dtype), rng.integers(-1, 12, B).astype(np.int32))
+        self.flags = rng.integers(0, 2, B).astype(np.uint8)
+
+    def get_state(self):
+        return self.state
+
+    def applied(self):
+        return self.flags
+
+
+@pytest.mark.parametrize("B,dtype", [(4096, np.float32), (65536, np.float32), (65536, np.float64)])
+def test_dump_outputs_fits_the_budget_with_a_fixed_sample(tmp_path, B, dtype):
+    """--dump-outputs: every array in the records' float type (ids as float64), all filters while they fit in 64 MB, past that the
+    same seeded sample of filters in every array -- the same sample on every run"""
+    flt = _FakeFilter(B, dtype)
+    bench.dump_outputs(str(tmp_path / "a"), flt)
+    bench.dump_outputs(str(tmp_path / "b"), flt)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) < 64e6
+    out = {f.stem: np.load(f) for f in (tmp_path / "a").glob("*.npy")}
+    assert set(out) == {"nominal", "rot", "P", "prev_marker", "applied", "filter_index"}
+    idx = out["filter_index"].astype(np.int64)
+    assert np.array_equal(out["filter_index"], idx) and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < B
+    assert len(idx) == B if B == 4096 else len(idx) > B // 3
+    nom, rot, P, prev = flt.get_state()
+    for name, full in (("nominal", nom), ("rot", rot), ("P", P)):
+        assert out[name].dtype == dtype and np.array_equal(out[name], full[idx]), name
+    assert out["prev_marker"].dtype == np.float64 and np.array_equal(out["prev_marker"], prev[idx])
+    assert np.array_equal(out["applied"], flt.applied()[idx])
+    for f in (tmp_path / "a").iterdir():
+        assert np.array_equal(np.load(f), np.load(tmp_path / "b" / f.name))

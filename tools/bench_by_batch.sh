@@ -9,7 +9,7 @@ echo "bench.py --batch B --steps 6 --warmup 2 (65 536: --steps 20 --warmup 5), o
 echo " filters   EKF steps/s  predict us  correct us  fused frame  frame window" >> $out
 for B in ${BATCHES:-32768 65536 69632 73728 81920 98304 131072 262144}; do
   S="--steps 6 --warmup 2"; [ $B = 65536 ] && S="--steps 20 --warmup 5"
-  python bench.py --batch $B $S --no-cpu-baseline --no-extra-legs --no-hbm-leg --detail-file /tmp/bb_detail.json 2>/dev/null | python -c "
+  python bench.py --full --batch $B $S --no-cpu-baseline --no-extra-legs --no-hbm-leg --detail-file /tmp/bb_detail.json 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%8d    %.3e  %10.2f  %10.2f    %.3e    %.3e' % ($B, d['value'], d['roofline']['avg_launch_us'], d['correct_kernel']['avg_launch_us'], d['fused_frame']['value'], d['fused_window']['value']))" >> $out

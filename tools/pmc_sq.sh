@@ -4,7 +4,7 @@
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"      # the GPU box exports GRAFT_REPO_ROOT; elsewhere: the script's repository
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT" || exit 1
 TAG=${1:-a}
-ARGS="--steps 2 --warmup 1 --no-cpu-baseline --no-hbm-leg --no-extra-legs --kernel-timing off ${2:-}"
+ARGS="--full --steps 2 --warmup 1 --no-cpu-baseline --no-hbm-leg --no-extra-legs --kernel-timing off ${2:-}"
 export OUT=gpurun_out/pmc_sq_$TAG
 mkdir -p $OUT
 timeout 600 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY --output-format csv -d $OUT/p1 -- python3 bench.py $ARGS > $OUT/p1.log 2>&1

@@ -8,7 +8,7 @@
 ROOT="${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}"      # the GPU box exports GRAFT_REPO_ROOT; elsewhere: the script's repository
 TAG=${1:-r02_b65536}
 ARGS=${2:-"--batch 65536 --steps 20 --warmup 5"}
-ARGS="$ARGS --no-cpu-baseline --no-hbm-leg --no-extra-legs"
+ARGS="$ARGS --full --no-cpu-baseline --no-hbm-leg --no-extra-legs"
 cd /tmp && export TMPDIR=/tmp && cd "$ROOT" || exit 1
 OUT=gpurun_out/prof_$TAG
 mkdir -p $OUT

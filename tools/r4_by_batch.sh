@@ -8,7 +8,7 @@ for B in ${BATCHES:-65536 69632 73728 98304 131072 196608 262144}; do
   for C in 0 auto; do
     if [ $C = auto ]; then unset FBUS_CHUNK; else export FBUS_CHUNK=$C; fi
     S="--steps 6 --warmup 2"; [ $B = 65536 ] && S="--steps 20 --warmup 5"
-    python bench.py --batch $B $S --no-cpu-baseline --no-extra-legs --no-hbm-leg 2>/dev/null | python -c "
+    python bench.py --full --batch $B $S --no-cpu-baseline --no-extra-legs --no-hbm-leg 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%8d %6s    %.3e  %10.2f  %10.2f    %.3e    %.3e' % ($B, d['roofline']['launch_policy']['chunk_filters'] or '-', d['value'], d['roofline']['avg_launch_us'], d['correct_kernel']['avg_launch_us'], d['fused_frame']['value'], d['fused_window']['value']))" >> $out

@@ -1,7 +1,7 @@
 #!/bin/bash
 # round 4 profile sets: headline (fp32, 65 536 filters) and the fp64 legs (65 536 filters; 524 288 filters = 839 MB of 1600-byte records)
 mkdir -p gpurun_out/r04
-python bench.py --steps 6 --warmup 2 --no-hbm-leg --no-cpu-baseline 2>/dev/null | python -c "
+python bench.py --full --steps 6 --warmup 2 --no-hbm-leg --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); f=d['fp64']
 print('fp64 per-call %.4g steps/s, predict %.2f us, correct %.2f us; fused frame %.4g steps/s (x%.2f)' % (f['value'], f['roofline']['avg_launch_us'], f['correct_kernel']['avg_launch_us'], f['fused_frame']['value'], f['fused_frame']['vs_per_call']))" | tee gpurun_out/r04/fp64_leg.txt

@@ -9,7 +9,7 @@ mkdir -p $O
 timeout 2400 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1; echo "gpu suite rc=$?"
 grep -a "passed\|failed" $O/pytest_gpu.log | tail -2 | cut -c1-200; grep -a "^FAILED\|^ERROR" $O/pytest_gpu.log | head -20
 timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -4 | cut -c1-200
-timeout 900 python bench.py --detail-file $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
+timeout 900 python bench.py --full --detail-file $O/bench_detail.json > $O/bench_line.json 2> $O/bench.err; echo "bench rc=$?"
 python - <<PY
 import json
 l = open('$O/bench_line.json').read().strip().splitlines()[-1]
