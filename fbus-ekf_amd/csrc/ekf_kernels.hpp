@@ -915,13 +915,48 @@ frame_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, co
 // wave per SIMD ~15 of its 38 us are that head and tail, during which the wave cannot compute; here they are paid once per
 // window.  Same device functions, same order of operations per filter as F fused frames (bit-identical results).
 struct FrameCounts { unsigned char k[FBUS_MAX_WINDOW_FRAMES]; };      // IMU samples in front of each frame
-template <typename T, int N, int DIALECT, int COV, bool JOINT>
+
+// Per-frame trajectory rows of a window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): what FBUS_EKF.m:201-204 appends
+// to EKFResults and filter.cpp:238-248 writes to fusion.txt after every frame, written by the window kernels straight from the resident
+// registers.  Row r = f * B + b: nom[r][19] (API order p v q ba bg g, the index map of unpack_kernel), pdiag[r][N] = diag(P), applied[r]
+// (what fbus_ekf_get_applied reports after frame f alone).  Each pointer may be null.
+template <typename T>
+struct TrajOut { T* nom; T* pdiag; unsigned char* applied; };
+// record element of API nominal element i (TileIO::nom_elem, as a constant expression: the rows index registers)
+template <int N>
+__host__ __device__ constexpr int api_nom_elem(int i)
+{
+    using L = Lay<N>;
+    return i < 3 ? L::OFF_P3 + i : i < 6 ? L::OFF_V + (i - 3) : i < 10 ? L::OFF_Q + (i - 6)
+         : i < 13 ? L::OFF_BA + (i - 10) : i < 16 ? L::OFF_BG + (i - 13) : L::OFF_G + (i - 16);
+}
+// nom: the record's nominal part (Lay<N> order), P: its covariance part (P[0] = record element OFF_COV)
+template <typename T, int N>
+__device__ __forceinline__ void traj_row(const TrajOut<T>& o, size_t row, const T* nom, const T* P, unsigned char app)
+{
+    if (o.nom) {
+        T* d = o.nom + row * 19;
+#pragma unroll
+        for (int i = 0; i < 19; ++i) d[i] = nom[api_nom_elem<N>(i)];
+    }
+    if (o.pdiag) {
+        T* d = o.pdiag + row * N;
+#pragma unroll
+        for (int i = 0; i < N; ++i) d[i] = P[pidx<N>(i, i)];
+    }
+    if (o.applied) o.applied[row] = app;
+}
+
+// TJ = TrajOut<T> (fbus_ekf_frames_fused_traj_dev, instantiated in a family of its own: kernels_tu.hip "framest"): frame f's trajectory
+// row goes out after its update, from the resident registers.  The empty pack is the window without rows.
+template <typename T, int N, int DIALECT, int COV, bool JOINT, typename... TJ>
 __global__ void __launch_bounds__(BLOCK)
 frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __restrict__ accel, const T* __restrict__ gyro,
               const T* __restrict__ dt, int dt_stride, int M, const int* __restrict__ ids, const T* __restrict__ pos,
               const T* __restrict__ quat, int mode, const unsigned char* __restrict__ skip,
-              unsigned char* __restrict__ applied, DevConst<T> dc)
+              unsigned char* __restrict__ applied, DevConst<T> dc, TJ... traj)
 {
+    constexpr bool TRAJ = sizeof...(TJ) > 0;
     using L = Lay<N>;
     using RC = Rec<T, N>;
     const int b = blockIdx.x * BLOCK + threadIdx.x;
@@ -940,6 +975,8 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
     }
     if (b >= B) return;
     int k0 = 0, last_used = 0;
+    // (TRAJ) M = 0: no frame writes d_applied, get_applied keeps reporting what it did before the window
+    const unsigned char app_in = (TRAJ && M == 0) ? applied[b] : 0;
 #pragma unroll 1
     for (int f = 0; f < F; ++f) {
         const int K = kc.k[f];
@@ -1007,13 +1044,13 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
             if (new_prev >= 0) P[L::OFF_PREV - L::OFF_COV] = (T)new_prev;
         }
         last_used = used;
+        if constexpr (TRAJ) traj_row<T, N>(traj..., (size_t)f * B + b, nom, P, M > 0 ? (used > 0 ? 1 : 0) : app_in);
         __builtin_amdgcn_sched_barrier(0);
     }
     if (M > 0 && F > 0) applied[b] = last_used > 0 ? 1 : 0;
     store_chunks<T, N, 0, RC::CH_NOM, FBUS_X_FRAME_ST>(rs, my_lane(), nom);
     store_chunks<T, N, RC::CH_NOM, RC::NCH, FBUS_X_FRAME_ST>(rs, my_lane(), P);
 }
-
 // The fused frame for launches of >= 2048 waves: at most 256 registers, two waves per SIMD (stacked mode, simple form).
 // frame_kernel holds the record in 383 registers and is VALU-bound with one wave per SIMD at 57 % issue utilisation;
 // from 131 072 filters on a second wave per SIMD fills its stalls.  What makes the 256 registers possible:
@@ -1519,6 +1556,47 @@ unpack_kernel(const T* __restrict__ recs, int B, T* __restrict__ nominal, T* __r
             const int f = o / (N * N), r = o - f * (N * N);
             P[f0 * N * N + o] = lds[f * IO::PITCH + tab[r]];
         }
+}
+
+// fbus_ekf_snapshot_dev: the nominal state (B x 19), diag(P) (B x N) and the applied flags (B) of the current records -- the pose and
+// its sigma without unpacking the full covariance.  The index maps and the coalesced path through LDS are unpack_kernel's, so the rows
+// equal get_state's nominal and diag(P) bit for bit.  Each output may be null.
+template <typename T, int N>
+__global__ void __launch_bounds__(BLOCK)
+snapshot_kernel(const T* __restrict__ recs, int B, const unsigned char* __restrict__ d_applied, T* __restrict__ nominal,
+                T* __restrict__ pdiag, unsigned char* __restrict__ applied)
+{
+    using IO = TileIO<T, N>;
+    using RC = Rec<T, N>;
+    __shared__ T lds[BLOCK * IO::PITCH];
+    const int lane = threadIdx.x, tile = blockIdx.x;
+    const int nvalid = min(BLOCK, B - tile * BLOCK);
+    const size_t f0 = (size_t)tile * BLOCK;
+    const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, tile);
+    T rec[IO::NR];
+    constexpr int CN = RC::CH_NOM, EPC = RC::EPC;
+    if (nominal) {
+        load_chunks<T, N, 0, CN>(rs, lane, rec);
+#pragma unroll
+        for (int e = 0; e < CN * EPC; ++e) lds[lane * IO::PITCH + e] = rec[e];
+    }
+    if (pdiag) {
+        load_chunks<T, N, CN, RC::NCH>(rs, lane, rec + CN * EPC);
+#pragma unroll
+        for (int e = CN * EPC; e < IO::NR; ++e) lds[lane * IO::PITCH + e] = rec[e];
+    }
+    __syncthreads();
+    if (nominal)
+        for (int o = lane; o < nvalid * 19; o += BLOCK) {
+            const int f = o / 19, i = o - f * 19;
+            nominal[f0 * 19 + o] = lds[f * IO::PITCH + IO::nom_elem(i)];
+        }
+    if (pdiag)
+        for (int o = lane; o < nvalid * N; o += BLOCK) {
+            const int f = o / N, i = o - f * N;
+            pdiag[f0 * N + o] = lds[f * IO::PITCH + IO::cov_elem(i * N + i)];
+        }
+    if (applied && lane < nvalid) applied[f0 + lane] = d_applied[f0 + lane];
 }
 
 template <typename T, int N>

@@ -44,6 +44,12 @@ template <typename T, int N, int D>
 void launch_frames_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
                      const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
                      const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc);
+// the same window writing frame f's trajectory row [f][B][.] to each non-null output (kernels_tu.hip family 10: frames_kernel with TrajOut)
+template <typename T, int N, int D>
+void launch_frames_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
+                          const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, T* out_nominal, T* out_pdiag,
+                          unsigned char* out_applied);
 
 // ---- team kernels (ekf_team.hpp): several waves per 64-filter tile, fp32 only -------------------------------------------
 // roles: waves per tile (predict 2..4, predict_n always 4); policy as in launch_predict_k
@@ -101,5 +107,12 @@ void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned ch
                          int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size, double r_meas,
                          double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
                          const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd);
+// a window (F > 1) of such frames writing frame f's trajectory row to each non-null output (kernels_tu.hip family 11: frame_meas_kernel with TrajOut)
+template <typename T, int N, int D>
+void launch_frame_meas_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt,
+                              int dt_stride, int kind, int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size,
+                              double r_meas, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                              const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd, T* out_nominal,
+                              T* out_pdiag, unsigned char* out_applied);
 
 }  // namespace fbus

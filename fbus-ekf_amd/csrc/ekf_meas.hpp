@@ -1736,14 +1736,19 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
 // =================================================================================
 template <typename T> struct QDiag { T qd[4]; };      // (MEAS_PIXELS / MEAS_CORNERS: ekf_launch.hpp)
 
-template <typename T, int N, int DIALECT, int KIND, bool NZ, bool WINDOW = false, int CAM = 0>
+// TJ = TrajOut<T> (fbus_ekf_frames_meas_fused_traj_dev; WINDOW only, instantiated in a family of its own: kernels_tu.hip "fmeast"): frame
+// f's trajectory row goes out from the resident registers once its update has been applied, or the predicted record where it was not.
+// The empty pack is the kernel without rows.
+template <typename T, int N, int DIALECT, int KIND, bool NZ, bool WINDOW = false, int CAM = 0, typename... TJ>
 __global__ void __launch_bounds__(64)
 frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __restrict__ accel, const T* __restrict__ gyro,
                   const T* __restrict__ dt, int dt_stride, int M, const int* __restrict__ ids, const T* __restrict__ left,
                   const T* __restrict__ right, int geometry, int mode, double size, double r_meas, double switch_thres,
                   const unsigned char* __restrict__ skip, unsigned char* __restrict__ applied, const short* __restrict__ id2slot,
-                  MeasConst mc, VisConst<double> vc, VisConst<T> vct, QDiag<T> qd)
+                  MeasConst mc, VisConst<double> vc, VisConst<T> vct, QDiag<T> qd, TJ... traj)
 {
+    constexpr bool TRAJ = sizeof...(TJ) > 0;
+    static_assert(!TRAJ || WINDOW, "trajectory rows are written by the window form");
     using L = Lay<N>;
     using RC = Rec<T, N>;
     constexpr int EPC = RC::EPC, CN = RC::CH_NOM;
@@ -1982,6 +1987,10 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
         } else {
             // the next frame's ImuUpdates read the predict-invariant tail as well: back from the record (current: see below)
             if constexpr (RC::CH_VAR_END < RC::NCH) load_chunks<T, N, RC::CH_VAR_END, RC::NCH>(rs, lane, P + PCH * EPC);
+            // (M = 0: no frame of the window writes d_applied -- get_applied keeps reporting what it did before the window)
+            // (the rows between fences: left to the scheduler they were interleaved with the loads above and the N = 18 kernels spilled
+            // 90-300 bytes; fenced, none spills)
+            if constexpr (TRAJ) { order_fence(); traj_row<T, N>(traj..., fo + b, nom, P, M > 0 ? 0 : applied[b]); order_fence(); }
             continue;
         }
     }
@@ -2014,6 +2023,7 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
         // the update changed the predict-invariant tail too, and the next frame's tail fetches it from the record again: out it goes
         // (ten chunks; a later load of this wave from the same addresses returns what was stored: vector memory operations of one wave
         // are served in order -- frame2_kernel relies on the same)
+        if constexpr (TRAJ) { order_fence(); traj_row<T, N>(traj..., fo + b, nom, P, 1); order_fence(); }
         if constexpr (RC::CH_VAR_END < RC::NCH) {
             if (f + 1 < F) store_chunks<T, N, RC::CH_VAR_END, RC::NCH, FBUS_X_FMEAS_ST>(rs, lane, P + PCH * EPC);
         }

@@ -485,6 +485,36 @@ int launch_frames(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, c
     DISPATCH(h, launch_frames_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip);
 }
 
+// Output slices of a trajectory window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): [nframes][B][19], [nframes][B][N],
+// [nframes][B]; any may be null
+struct TrajDst { void* nom; void* pdiag; uint8_t* applied; };
+
+// the window of frames_kernel with frame f's rows written from its registers (frames_kernel with TrajOut; the caller has checked that the
+// one-wave resident kernel applies: fp32, not (Joseph, nearest), not the team form)
+template <typename T, int N, int D>
+int launch_frames_traj_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+                         int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                         const TrajDst& tj)
+{
+    if constexpr (sizeof(T) == 4) {
+        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
+        h->records_warm = true;
+        launch_frames_traj_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                      dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                      h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h),
+                                      (T*)tj.nom, (T*)tj.pdiag, tj.applied);
+        timing_end(h, ev);
+        HIP_TRY(h, hipGetLastError());
+        return FBUS_OK;
+    }
+    return fail(h, FBUS_ERR_UNSUPPORTED, "frames_fused_traj: no resident fp64 window");
+}
+int launch_frames_traj(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
+                       const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, const TrajDst& tj)
+{
+    DISPATCH(h, launch_frames_traj_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip, tj);
+}
+
 
 template <typename T, int N>
 int pack_t(fbus_ekf_t h, const void* nom, const void* rot, const void* P, const int32_t* prev)
@@ -530,6 +560,36 @@ int reset_cov_t(fbus_ekf_t h)
 int do_pack(fbus_ekf_t h, const void* n, const void* r, const void* P, const int32_t* pv) { DISPATCH2(h, pack_t, h, n, r, P, pv); }
 int do_unpack(fbus_ekf_t h, void* n, void* r, void* P, int32_t* pv) { DISPATCH2(h, unpack_t, h, n, r, P, pv); }
 int do_reset_cov(fbus_ekf_t h) { DISPATCH2(h, reset_cov_t, h); }
+
+template <typename T, int N>
+int snapshot_t(fbus_ekf_t h, void* nom, void* pdiag, uint8_t* applied)
+{
+    const int grid = (h->B + BLOCK - 1) / BLOCK;             // one wave per 64-filter tile, as unpack
+    hipLaunchKernelGGL((snapshot_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (const T*)h->recs, h->B, h->d_applied,
+                       (T*)nom, (T*)pdiag, applied);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int do_snapshot(fbus_ekf_t h, void* n, void* pd, uint8_t* a) { DISPATCH2(h, snapshot_t, h, n, pd, a); }
+// the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
+int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
+{
+    const size_t es = esize(h), rows = (size_t)f * h->B;
+    return do_snapshot(h, tj.nom ? (char*)tj.nom + rows * 19 * es : nullptr, tj.pdiag ? (char*)tj.pdiag + rows * h->N * es : nullptr,
+                       tj.applied ? tj.applied + rows : nullptr);
+}
+// outputs must not overlap the records (the kernels read the records while the rows go out); FBUS_ERR_INVALID otherwise
+int check_traj(fbus_ekf_t h, const TrajDst& tj, int nframes, const char* what)
+{
+    const size_t es = esize(h), rows = (size_t)nframes * h->B;
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes;
+    const struct { const void* p; size_t bytes; } outs[3] = { { tj.nom, rows * 19 * es }, { tj.pdiag, rows * h->N * es }, { tj.applied, rows } };
+    for (const auto& o : outs) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
+        if (o.p && a < r1 && a + o.bytes > r0) return fail(h, FBUS_ERR_INVALID, std::string(what) + ": an output overlaps the records");
+    }
+    return FBUS_OK;
+}
 
 template <typename T>
 VisConst<T> make_vc(const fbus_ekf* h)
@@ -765,6 +825,33 @@ int launch_frame_meas(fbus_ekf_t h, int F, const unsigned char* kc, const void* 
                       int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip)
 {
     DISPATCH(h, launch_frame_meas_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip);
+}
+// the resident window (F > 1) of launch_frame_meas_t with frame f's rows written from the registers (frame_meas_kernel with TrajOut)
+template <typename T, int N, int D>
+int launch_frame_meas_traj_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+                             int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                             int mode, const uint8_t* skip, const TrajDst& tj)
+{
+    if constexpr (sizeof(T) == 4) {
+        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
+        h->records_warm = h->warm_after_correct;
+        const DevConst<T> dc = make_dc<T>(h);
+        launch_frame_meas_traj_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                          dt_per_filter ? 1 : 0, kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                          h->prm.marker_size, kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres,
+                                          (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h),
+                                          make_vc<T>(h), dc.qd, (T*)tj.nom, (T*)tj.pdiag, tj.applied);
+        timing_end(h, ev);
+        HIP_TRY(h, hipGetLastError());
+        return FBUS_OK;
+    }
+    return fail(h, FBUS_ERR_UNSUPPORTED, "frames_meas_fused_traj: no resident fp64 window");
+}
+int launch_frame_meas_traj(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per,
+                           int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
+                           const uint8_t* skip, const TrajDst& tj)
+{
+    DISPATCH(h, launch_frame_meas_traj_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip, tj);
 }
 bool frame_meas_is_resident(const fbus_ekf* h, int kind, int M, int mode)
 {
@@ -1717,11 +1804,11 @@ int fbus_ekf_frame_meas_fused_dev(fbus_ekf_t h, int K, const void* accel, const 
     return launch_frame_meas(h, 1, &kc1, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip);
 }
 
-int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
-                                   int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
-                                   int mode, const uint8_t* skip)
+// fbus_ekf_frames_meas_fused_dev (tj = null) and fbus_ekf_frames_meas_fused_traj_dev: one validation, one choice of route
+static int frames_meas_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
+                            int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                            int mode, const uint8_t* skip, const TrajDst* tj)
 {
-    DeviceGuard guard_(h);
     if (!h || nframes < 0 || nframes > FBUS_MAX_WINDOW_FRAMES || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
     if (kind != FBUS_MEAS_PIXELS && kind != FBUS_MEAS_CORNERS) return FBUS_ERR_UNSUPPORTED;
     if (nframes > 0 && !kcount) return FBUS_ERR_INVALID;
@@ -1746,13 +1833,19 @@ int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kco
     // every frame's arrays start a multiple of 16 bytes behind the first (B M x 32 / 48 bytes x element size): one check covers the window
     if (M > 0 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_frames_meas_fused_dev: left / right must be 16-byte aligned device pointers");
+    if (tj) {
+        const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_meas_fused_traj_dev");
+        if (rc != FBUS_OK) return rc;
+    }
     // the resident window kernel where the frame form takes the resident kernel (fp32 records, one wave per tile); elsewhere frame by
-    // frame through the frame entry point's routes -- the same arithmetic
+    // frame through the frame entry point's routes -- the same arithmetic (with a trajectory: each frame's rows by the snapshot kernel)
     if (nframes > 1 && frame_meas_is_resident(h, kind, M, mode))
-        return launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip);
+        return tj ? launch_frame_meas_traj(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, *tj)
+                  : launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip);
     const size_t es = esize(h), B = (size_t)h->B;
     const size_t lw = (kind == FBUS_MEAS_CORNERS && geometry == FBUS_VIS_CORNERS3D) ? 12 : 8;
     size_t k0 = 0;
+    int rc2 = FBUS_OK;
     for (int f = 0; f < nframes; ++f) {
         const int rc = launch_frame_meas(h, 1, kc + f, (const char*)accel + k0 * B * 3 * es, (const char*)gyro + k0 * B * 3 * es,
                                          (const char*)dt + k0 * (dt_per_filter ? B : 1) * es, dt_per_filter, kind, M,
@@ -1760,16 +1853,37 @@ int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kco
                                          right ? (const char*)right + (size_t)f * B * M * 8 * es : nullptr, geometry, mode,
                                          skip ? skip + (size_t)f * B : nullptr);
         if (rc != FBUS_OK) return rc;
+        if (tj && (rc2 = snapshot_row(h, *tj, f)) != FBUS_OK) return rc2;
         k0 += kc[f];
     }
     return FBUS_OK;
 }
 
-int fbus_ekf_frames_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
-                              const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
-                              const void* quat, int mode, const uint8_t* skip)
+int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
+                                   int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                                   int mode, const uint8_t* skip)
 {
     DeviceGuard guard_(h);
+    return frames_meas_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, nullptr);
+}
+
+int fbus_ekf_frames_meas_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                                        const void* dt, int dt_per_filter, int kind, int M, const int32_t* ids, const void* left,
+                                        const void* right, int geometry, int mode, const uint8_t* skip, void* out_nominal, void* out_pdiag,
+                                        uint8_t* out_applied)
+{
+    DeviceGuard guard_(h);
+    const TrajDst tj{ out_nominal, out_pdiag, out_applied };
+    const bool any = out_nominal || out_pdiag || out_applied;
+    return frames_meas_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip,
+                            any ? &tj : nullptr);
+}
+
+// fbus_ekf_frames_fused_dev (tj = null) and fbus_ekf_frames_fused_traj_dev
+static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
+                       int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                       const TrajDst* tj)
+{
     if (!h || nframes < 0 || nframes > FBUS_MAX_WINDOW_FRAMES || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
     if (nframes > 0 && !kcount) return FBUS_ERR_INVALID;
     if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
@@ -1785,20 +1899,62 @@ int fbus_ekf_frames_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, 
     if (nframes == 0) return FBUS_OK;
     // no resident-record kernel for fp64 and for (Joseph, nearest) -- see launch_frame_t: those windows run frame by frame,
     // the same arithmetic
+    if (tj) {
+        const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_fused_traj_dev");
+        if (rc != FBUS_OK) return rc;
+    }
     const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED);
-    if (resident) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
+    // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel
+    const bool team = resident && team_frames(h, mode);
+    if (resident && !team) return launch_frames_traj(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, *tj);
     const size_t es = esize(h), B = (size_t)h->B;
     size_t k0 = 0;
     for (int f = 0; f < nframes; ++f) {
-        const int rc = launch_frame(h, kc[f], (const char*)accel + k0 * B * 3 * es, (const char*)gyro + k0 * B * 3 * es,
-                                    (const char*)dt + k0 * (dt_per_filter ? B : 1) * es, dt_per_filter, M,
-                                    ids ? ids + (size_t)f * B * M : nullptr, pos ? (const char*)pos + (size_t)f * B * M * 3 * es : nullptr,
-                                    quat ? (const char*)quat + (size_t)f * B * M * 4 * es : nullptr, mode,
-                                    skip ? skip + (size_t)f * B : nullptr);
+        const char* a = (const char*)accel + k0 * B * 3 * es;
+        const char* g = (const char*)gyro + k0 * B * 3 * es;
+        const char* d = (const char*)dt + k0 * (dt_per_filter ? B : 1) * es;
+        const int32_t* fi = ids ? ids + (size_t)f * B * M : nullptr;
+        const char* fp = pos ? (const char*)pos + (size_t)f * B * M * 3 * es : nullptr;
+        const char* fq = quat ? (const char*)quat + (size_t)f * B * M * 4 * es : nullptr;
+        const uint8_t* fs = skip ? skip + (size_t)f * B : nullptr;
+        int rc = team ? launch_frames(h, 1, kc + f, a, g, d, dt_per_filter, M, fi, fp, fq, mode, fs)
+                      : launch_frame(h, kc[f], a, g, d, dt_per_filter, M, fi, fp, fq, mode, fs);
+        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
         if (rc != FBUS_OK) return rc;
         k0 += kc[f];
     }
     return FBUS_OK;
+}
+
+int fbus_ekf_frames_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                              const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
+                              const void* quat, int mode, const uint8_t* skip)
+{
+    DeviceGuard guard_(h);
+    return frames_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, nullptr);
+}
+
+int fbus_ekf_frames_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                                   const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
+                                   const void* quat, int mode, const uint8_t* skip, void* out_nominal, void* out_pdiag,
+                                   uint8_t* out_applied)
+{
+    DeviceGuard guard_(h);
+    const TrajDst tj{ out_nominal, out_pdiag, out_applied };
+    const bool any = out_nominal || out_pdiag || out_applied;
+    return frames_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, any ? &tj : nullptr);
+}
+
+int fbus_ekf_snapshot_dev(fbus_ekf_t h, void* nominal, void* pdiag, uint8_t* applied)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (!nominal && !pdiag && !applied) return FBUS_OK;
+    const TrajDst tj{ nominal, pdiag, applied };
+    int rc = check_traj(h, tj, 1, "fbus_ekf_snapshot_dev");
+    return rc != FBUS_OK ? rc : do_snapshot(h, nominal, pdiag, applied);
 }
 
 int fbus_ekf_frame_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter,

@@ -9,6 +9,8 @@
 //   7 correct from corner pixels / from stereo corners (ekf_meas.hpp: double-precision fold, non-cancelling update)
 //   9 correct from corner pixels with the update divided between the waves of a tile (ekf_meas_split.hpp; fp32 only)
 //   8 fused frame with that update (K predicts + correct_pixels / correct_corners in one launch; fp32 only)
+//  10 frame window with per-frame trajectory rows (frames_kernel with TrajOut; fp32 only)
+//  11 window of 8's frames with per-frame trajectory rows (frame_meas_kernel with TrajOut; fp32 only)
 // gfx950 only.
 #include <cstdlib>
 #include "ekf_kernels.hpp"
@@ -343,8 +345,72 @@ void launch_pixels_split_k(hipStream_t s, T* recs, int B, int M, const int* ids,
     template void launch_pixels_split_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
                                                                  const FBUS_TU_T*, int, double, double, const unsigned char*, \
                                                                  unsigned char*, const short*, const MeasConst&);
+#elif FBUS_TU_FAMILY == 10
+// the frame window with its trajectory rows (frames_kernel with TrajOut): the kernel choice of family 5
+template <typename T, int N, int D>
+void launch_frames_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
+                          const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, T* out_nominal, T* out_pdiag,
+                          unsigned char* out_applied)
+{
+    const int grid = (B + BLOCK - 1) / BLOCK;
+    const bool joint = mode == MODE_STACKED;
+    FrameCounts kc;
+    for (int f = 0; f < FBUS_MAX_WINDOW_FRAMES; ++f) kc.k[f] = f < F ? kcount[f] : 0;
+    const TrajOut<T> tj{ out_nominal, out_pdiag, out_applied };
+#define FBUS_LAUNCH_FRAMES(COV, JOINT)                                                                                \
+    hipLaunchKernelGGL((frames_kernel<T, N, D, COV, JOINT, TrajOut<T>>), dim3(grid), dim3(BLOCK), 0, s, recs, B, F, kc, accel, gyro, \
+                       dt, dt_stride, M, ids, pos, quat, mode, skip, applied, dc, tj)
+    if (joseph) { FBUS_LAUNCH_FRAMES(COV_JOSEPH, true); }
+    else        { if (joint) FBUS_LAUNCH_FRAMES(COV_SIMPLE, true); else FBUS_LAUNCH_FRAMES(COV_SIMPLE, false); }
+#undef FBUS_LAUNCH_FRAMES
+}
+#define FBUS_INST(D)                                                                                                  \
+    template void launch_frames_traj_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const unsigned char*, \
+                                                                const FBUS_TU_T*, const FBUS_TU_T*, const FBUS_TU_T*, int, \
+                                                                int, const int*, const FBUS_TU_T*, const FBUS_TU_T*, int, \
+                                                                bool, const unsigned char*, unsigned char*,            \
+                                                                const DevConst<FBUS_TU_T>&, FBUS_TU_T*, FBUS_TU_T*,    \
+                                                                unsigned char*);
+#elif FBUS_TU_FAMILY == 11
+// the north star's window with its trajectory rows (frame_meas_kernel with TrajOut): the kernel choice of family 8 for F > 1
+template <typename T, int N, int D>
+void launch_frame_meas_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt,
+                              int dt_stride, int kind, int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size,
+                              double r_meas, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                              const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd, T* out_nominal,
+                              T* out_pdiag, unsigned char* out_applied)
+{
+    const int tiles = (B + 63) / 64;
+    FrameCounts kc;
+    for (int f = 0; f < FBUS_MAX_WINDOW_FRAMES; ++f) kc.k[f] = f < F ? kcount[f] : 0;
+    QDiag<T> q;
+    for (int i = 0; i < 4; ++i) q.qd[i] = qd[i];
+    const TrajOut<T> tj{ out_nominal, out_pdiag, out_applied };
+    const bool nz = (kind == MEAS_PIXELS) ? (mc.n[0] == 0.0 && mc.n[1] == 0.0 && mc.n[2] == 1.0)
+                                          : (vc.nrm[0] == 0.0 && vc.nrm[1] == 0.0 && vc.nrm[2] == 1.0);
+#define FBUS_LAUNCH_FMT(KIND, NZF, CAM)                                                                                  \
+    hipLaunchKernelGGL((frame_meas_kernel<T, N, D, KIND, NZF, true, CAM, TrajOut<T>>), dim3(tiles), dim3(64), 0, s, recs, B, F, kc, accel, gyro, dt, \
+                       dt_stride, M, ids, left, right, geometry, mode, size, r_meas, switch_thres, skip, applied, id2slot, mc, vc, vct, q, tj)
+    if (kind == MEAS_PIXELS) {
+        if (nz) {
+            if (right) FBUS_LAUNCH_FMT(MEAS_PIXELS, true, 2);
+            else FBUS_LAUNCH_FMT(MEAS_PIXELS, true, 1);
+        } else FBUS_LAUNCH_FMT(MEAS_PIXELS, false, 0);
+    }
+    else                     { if (nz) FBUS_LAUNCH_FMT(MEAS_CORNERS, true, 0); else FBUS_LAUNCH_FMT(MEAS_CORNERS, false, 0); }
+#undef FBUS_LAUNCH_FMT
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_frame_meas_traj_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const unsigned char*, \
+                                                                    const FBUS_TU_T*, const FBUS_TU_T*, const FBUS_TU_T*, int, int, \
+                                                                    int, const int*, const FBUS_TU_T*, const FBUS_TU_T*, int, int, \
+                                                                    double, double, double, const unsigned char*, unsigned char*, \
+                                                                    const short*, const MeasConst&, const VisConst<double>&, \
+                                                                    const VisConst<FBUS_TU_T>&, const FBUS_TU_T*, FBUS_TU_T*, \
+                                                                    FBUS_TU_T*, unsigned char*);
 #else
-#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8 or 9"
+#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10 or 11"
 #endif
 
 FBUS_INST(DIALECT_MATLAB)

@@ -441,10 +441,12 @@ class BatchedFilter:
         self._order_out(cur)
 
     def frames_meas(self, kcount, accel, gyro, dt, ids, left, right=None, kind=capi.MEAS_PIXELS, geometry=capi.VIS_REFRACTIVE,
-                    mode=capi.MODE_STACKED, skip=None):
+                    mode=capi.MODE_STACKED, skip=None, record=False):
         """A window of camera frames with the north star's MeasureUpdate in ONE launch (fbus_ekf_frames_meas_fused_dev; device arrays):
         len(kcount) times { kcount[f] predicts, correct_pixels / correct_corners }.  accel, gyro: (sum kcount, B, 3); dt: (sum kcount,) or
-        (sum kcount, B); ids: (F, B, M); left / right: (F, B, M, 8) [(F, B, M, 12) for VIS_CORNERS3D]; skip: (F, B) or None."""
+        (sum kcount, B); ids: (F, B, M); left / right: (F, B, M, 8) [(F, B, M, 12) for VIS_CORNERS3D]; skip: (F, B) or None.
+        record=True: the window's trajectory as well (fbus_ekf_frames_meas_fused_traj_dev) -- returns (nominal (F, B, 19), pdiag (F, B, N),
+        applied (F, B)), torch tensors on the handle's device: the state after every frame (FBUS_EKF.m:201-204)."""
         B = self.B
         kcount = np.ascontiguousarray(kcount, np.int32)
         F, Kt = int(kcount.size), int(kcount.sum())
@@ -465,6 +467,15 @@ class BatchedFilter:
                 self._dev_checked(right, F * B * M * 8, "right")
         if skip is not None:
             self._dev_checked(skip, F * B, "skip")
+        if record:
+            out = self._traj_outputs(F)
+            cur = self._order_in(accel, gyro, dt, ids, left, right, skip, *out)
+            rc = self._lib.fbus_ekf_frames_meas_fused_traj_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
+                                                               self._p(gyro), self._p(dt), per, kind, M, self._p(ids), self._p(left),
+                                                               self._p(right), geometry, mode, self._p(skip), *[self._p(o) for o in out])
+            self._check(rc, "frames_meas_fused_traj_dev")
+            self._order_out(cur)
+            return out
         cur = self._order_in(accel, gyro, dt, ids, left, right, skip)
         rc = self._lib.fbus_ekf_frames_meas_fused_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel), self._p(gyro),
                                                       self._p(dt), per, kind, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
@@ -472,11 +483,13 @@ class BatchedFilter:
         self._check(rc, "frames_meas_fused_dev")
         self._order_out(cur)
 
-    def frames(self, kcount, accel, gyro, dt, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
+    def frames(self, kcount, accel, gyro, dt, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None, record=False):
         """A window of camera frames in ONE launch (device arrays): len(kcount) times { kcount[f] predicts, one correct }
         with the records resident in registers in between -- the frame loop of FBUS_EKF.m:151-210 over a recorded stretch.
         accel, gyro: (sum kcount, B, 3); dt: (sum kcount,) or (sum kcount, B); ids: (F, B, M); pos: (F, B, M, 3);
-        quat: (F, B, M, 4); skip: (F, B) or None.  applied() afterwards reports the last frame."""
+        quat: (F, B, M, 4); skip: (F, B) or None.  applied() afterwards reports the last frame.
+        record=True: the window's trajectory as well (fbus_ekf_frames_fused_traj_dev) -- returns (nominal (F, B, 19), pdiag (F, B, N),
+        applied (F, B)), torch tensors on the handle's device: the state after every frame (FBUS_EKF.m:201-204)."""
         B = self.B
         kcount = np.ascontiguousarray(kcount, np.int32)
         F, Kt = int(kcount.size), int(kcount.sum())
@@ -495,12 +508,40 @@ class BatchedFilter:
             self._dev_checked(quat, F * B * M * 4, "quat")
         if skip is not None:
             self._dev_checked(skip, F * B, "skip")
+        if record:
+            out = self._traj_outputs(F)
+            cur = self._order_in(accel, gyro, dt, ids, pos, quat, skip, *out)
+            rc = self._lib.fbus_ekf_frames_fused_traj_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
+                                                          self._p(gyro), self._p(dt), per, M, self._p(ids), self._p(pos), self._p(quat),
+                                                          mode, self._p(skip), *[self._p(o) for o in out])
+            self._check(rc, "frames_fused_traj_dev")
+            self._order_out(cur)
+            return out
         cur = self._order_in(accel, gyro, dt, ids, pos, quat, skip)
         rc = self._lib.fbus_ekf_frames_fused_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
                                                  self._p(gyro), self._p(dt), per, M, self._p(ids), self._p(pos), self._p(quat),
                                                  mode, self._p(skip))
         self._check(rc, "frames_fused_dev")
         self._order_out(cur)
+
+    def _traj_outputs(self, F):
+        """(nominal (F, B, 19), pdiag (F, B, N), applied (F, B)) on the handle's device, kept alive until the next sync()"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        tt = torch.float32 if self.dtype == 32 else torch.float64
+        out = (torch.empty((F, self.B, 19), dtype=tt, device=dev), torch.empty((F, self.B, self.N), dtype=tt, device=dev),
+               torch.empty((F, self.B), dtype=torch.uint8, device=dev))
+        self._keep.extend(out)
+        return out
+
+    def snapshot(self):
+        """The pose and its sigma of every filter without the full covariance (fbus_ekf_snapshot_dev): (nominal (B, 19), pdiag (B, N),
+        applied (B,)), torch tensors on the handle's device -- equal to get_state()'s nominal and diag(P) and to applied(), bit for bit."""
+        nominal, pdiag, applied = (o[0] for o in self._traj_outputs(1))
+        cur = self._order_in(nominal, pdiag, applied)
+        self._check(self._lib.fbus_ekf_snapshot_dev(self._h, self._p(nominal), self._p(pdiag), self._p(applied)), "snapshot_dev")
+        self._order_out(cur)
+        return nominal, pdiag, applied
 
     # ---- init / reset / front door (host arrays) --------------------------------------------
     def init_gravity_bias(self, accel, gyro):

@@ -177,14 +177,23 @@ def plan_windows(imu, image, max_frames=None, matlab_reset=True, max_window=64):
     return plan
 
 
-def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64):
+def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, trajectory=False, corners=None, stereo=True):
     """The recording through the Matlab loop on `flt` (a BatchedFilter of B filters, every one of them fed the same recording:
     config 1 at batch scale) with each stretch of consecutive frames as ONE launch of the frame-window kernel
     (fbus_ekf_frames_fused_dev) instead of one launch per EKF step.  Returns the number of EKF steps per filter; the state is
-    read with flt.get_state().  Same arithmetic as replay(); the results agree to fp32 rounding (resident vs streamed predict)."""
+    read with flt.get_state().  Same arithmetic as replay(); the results agree to fp32 rounding (resident vs streamed predict).
+    trajectory=True: returns (steps, rows) instead, rows[k] = [t, nominal(19), diag P(N)] of filter 0 after frame k -- the
+    reference's per-frame output (FBUS_EKF.m:201-204, filter.cpp:238-248; fusion_rows() reads it as it reads replay()'s rows),
+    from the windows' own trajectory outputs (fbus_ekf_frames_*_traj_dev) and, for a reset frame, flt.snapshot() after the reset.
+    corners (optional): the rows of corners.txt for the rows of image, as in replay(corners=...): every MeasureUpdate becomes the
+    north star's, the windows run through fbus_ekf_frames_meas_fused_dev with the corner pixels (stereo=False: left camera only)."""
     import torch
     imu = np.asarray(imu, float)
     image = np.asarray(image, float)
+    if corners is not None:
+        corners = np.asarray(corners, float)
+        if len(corners) != len(image) or np.abs(corners[:, 0] - image[:, 0]).max() > 1e-9:
+            raise ValueError("corners rows must be the rows of image (same time stamps)")
     B, N = flt.B, flt.N
     dev = torch.device("cuda", flt.device) if hasattr(flt, "device") else torch.device("cuda:0")
     tt = torch.float32 if flt.np_dtype == np.float32 else torch.float64
@@ -196,10 +205,16 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64):
     meas0 = image[0:1, 1:9]
     flt.pose_init(rep(meas0[:, 0].astype(np.int32)[None]), rep(meas0[None, :, 1:4]), rep(meas0[None, :, 4:8]), 0)
     steps = 0
+    rows_out = []           # (t, nominal (19,) or (F, 19) device tensor, pdiag ...) of filter 0, read once at the end
+    row0 = 0                # the first image row of the next frame (plan_windows consumes the frames in order)
     for item in plan_windows(imu, image, max_frames, True, max_window):
         if item[0] == "reset":
             meas = item[1]
             flt.pose_init(rep(meas[:, 0].astype(np.int32)[None]), rep(meas[None, :, 1:4]), rep(meas[None, :, 4:8]), 1)
+            if trajectory:
+                nom, pd, _ = flt.snapshot()
+                rows_out.append((image[row0:row0 + 1, 0], nom[None, 0].clone(), pd[None, 0].clone()))
+            row0 += len(meas)
             continue
         up = lambda a, t=tt: torch.from_numpy(np.ascontiguousarray(a)).to(dev).to(t)
         if item[0] == "predict":
@@ -215,20 +230,42 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64):
             continue
         _, kcount, rows, dts, frames = item
         F, M = len(frames), max(len(m) for m in frames)
-        ids = np.full((F, 1, M), -1, np.int32); pos = np.zeros((F, 1, M, 3)); quat = np.zeros((F, 1, M, 4)); quat[..., 0] = 1
-        for f, m in enumerate(frames):
-            ids[f, 0, :len(m)] = m[:, 0].astype(np.int32); pos[f, 0, :len(m)] = m[:, 1:4]; quat[f, 0, :len(m)] = m[:, 4:8]
+        t_frames = np.array([image[r, 0] for r in np.cumsum([row0] + [len(m) for m in frames[:-1]])])
         d_acc = up(imu[rows, 1:4])[:, None, :].expand(len(rows), B, 3).contiguous()
         d_gyr = up(imu[rows, 4:7])[:, None, :].expand(len(rows), B, 3).contiguous()
-        d_ids = torch.from_numpy(ids).to(dev).expand(F, B, M).contiguous()
-        d_pos = up(pos).expand(F, B, M, 3).contiguous()
-        d_quat = up(quat).expand(F, B, M, 4).contiguous()
         d_dt = up(dts)
-        flt.wait_stream(torch.cuda.current_stream())          # the uploads above ran on torch's stream
-        flt.frames(kcount, d_acc, d_gyr, d_dt, d_ids, d_pos, d_quat, 0)
+        if corners is None:
+            ids = np.full((F, 1, M), -1, np.int32); pos = np.zeros((F, 1, M, 3)); quat = np.zeros((F, 1, M, 4)); quat[..., 0] = 1
+            for f, m in enumerate(frames):
+                ids[f, 0, :len(m)] = m[:, 0].astype(np.int32); pos[f, 0, :len(m)] = m[:, 1:4]; quat[f, 0, :len(m)] = m[:, 4:8]
+            d_ids = torch.from_numpy(ids).to(dev).expand(F, B, M).contiguous()
+            d_pos = up(pos).expand(F, B, M, 3).contiguous()
+            d_quat = up(quat).expand(F, B, M, 4).contiguous()
+            flt.wait_stream(torch.cuda.current_stream())          # the uploads above ran on torch's stream
+            out = flt.frames(kcount, d_acc, d_gyr, d_dt, d_ids, d_pos, d_quat, 0, record=trajectory)
+        else:
+            # the corner rows of each frame (those of its image rows), slots past the frame's markers absent (id -1)
+            ids = np.full((F, 1, M), -1, np.int32); lft = np.zeros((F, 1, M, 8)); rgt = np.zeros((F, 1, M, 8))
+            r = row0
+            for f, m in enumerate(frames):
+                c = corners[r:r + len(m)]
+                ids[f, 0, :len(m)] = c[:, 1].astype(np.int32); lft[f, 0, :len(m)] = c[:, 2:10]; rgt[f, 0, :len(m)] = c[:, 10:18]
+                r += len(m)
+            d_ids = torch.from_numpy(ids).to(dev).expand(F, B, M).contiguous()
+            d_l = up(lft).expand(F, B, M, 8).contiguous()
+            d_r = up(rgt).expand(F, B, M, 8).contiguous() if stereo else None
+            flt.wait_stream(torch.cuda.current_stream())
+            out = flt.frames_meas(kcount, d_acc, d_gyr, d_dt, d_ids, d_l, d_r, record=trajectory)
+        if trajectory:
+            rows_out.append((t_frames, out[0][:, 0], out[1][:, 0]))
+        row0 += sum(len(m) for m in frames)
         steps += int(kcount.sum()) + F
     flt.sync()
-    return steps
+    if not trajectory:
+        return steps
+    torch.cuda.synchronize(dev)
+    rows = [np.concatenate([t[:, None], nom.double().cpu().numpy(), pd.double().cpu().numpy()], axis=1) for t, nom, pd in rows_out]
+    return steps, (np.concatenate(rows) if rows else np.zeros((0, 20 + N)))
 
 
 def replay_cpp_loop(engine, imu, image, params, max_frames=None, n_init=500):

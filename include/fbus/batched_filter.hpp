@@ -109,6 +109,16 @@ public:
         check(fbus_ekf_frames_fused_dev(h_, int(kcount.size()), kcount.data(), accel, gyro, dt, 0, M, ids, pos, quat, int(mode), skip),
               "frames_fused_dev");
     }
+    // the same window with its trajectory (fbus_ekf_frames_fused_traj_dev): device outputs [F][B][19], [F][B][N], [F][B], each may be null
+    void frames_fused_dev(const std::vector<int32_t>& kcount, const Real* accel, const Real* gyro, const Real* dt, int M,
+                          const int32_t* ids, const Real* pos, const Real* quat, Mode mode, const uint8_t* skip,
+                          Real* out_nominal, Real* out_pdiag, uint8_t* out_applied)
+    {
+        check(fbus_ekf_frames_fused_traj_dev(h_, int(kcount.size()), kcount.data(), accel, gyro, dt, 0, M, ids, pos, quat, int(mode), skip,
+                                             out_nominal, out_pdiag, out_applied), "frames_fused_traj_dev");
+    }
+    // nominal (B, 19), diag(P) (B, N), applied (B) of the current records into device buffers (fbus_ekf_snapshot_dev; each may be null)
+    void snapshot_dev(Real* nominal, Real* pdiag, uint8_t* applied) { check(fbus_ekf_snapshot_dev(h_, nominal, pdiag, applied), "snapshot_dev"); }
 
     // correct() from corner pixels (north-star extension): left / right (B, M, 8) normalised image points, right may be null
     void correct_pixels(int M, const int32_t* ids, const Real* left, const Real* right = nullptr, const uint8_t* skip = nullptr)
@@ -138,6 +148,14 @@ public:
     {
         check(fbus_ekf_frames_meas_fused_dev(h_, int(kcount.size()), kcount.data(), accel, gyro, dt, 0, kind, M, ids, left, right, geometry,
                                              int(mode), skip), "frames_meas_fused_dev");
+    }
+    // ... with its trajectory (fbus_ekf_frames_meas_fused_traj_dev): device outputs [F][B][19], [F][B][N], [F][B], each may be null
+    void frames_meas_fused_dev(const std::vector<int32_t>& kcount, const Real* accel, const Real* gyro, const Real* dt, int kind, int M,
+                               const int32_t* ids, const Real* left, const Real* right, int geometry, Mode mode, const uint8_t* skip,
+                               Real* out_nominal, Real* out_pdiag, uint8_t* out_applied)
+    {
+        check(fbus_ekf_frames_meas_fused_traj_dev(h_, int(kcount.size()), kcount.data(), accel, gyro, dt, 0, kind, M, ids, left, right,
+                                                  geometry, int(mode), skip, out_nominal, out_pdiag, out_applied), "frames_meas_fused_traj_dev");
     }
 
     // waves per 64-filter tile (fbus_ekf_set_team): 0 = chosen per launch, 1 = always one, 2..4 = always that many

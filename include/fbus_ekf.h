@@ -105,12 +105,14 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  * the caller's compile-time sizeof(fbus_params) and FBUS_ABI_VERSION to fbus_ekf_create_checked, which refuses a
  * mismatch with FBUS_ERR_ABI.  (Bindings that cannot use the macro -- ctypes, loadlibrary -- call
  * fbus_ekf_abi_version() / fbus_params_size() once after loading and compare; the Python mirror does.)
+ *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
+ *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
  *   4  round 4: fbus_ekf_set_policy_batch, fbus_ekf_launch_info (struct unchanged)
  *   3  round 3: FBUS_ERR_ABI, create_checked, team kernels (fbus_ekf_set_team), fbus_ekf_gather
  *   2  round 2: r_pix in fbus_params, set_stream(NULL) = legacy default stream
  *   1  round 1 */
-#define FBUS_ABI_VERSION 6
+#define FBUS_ABI_VERSION 7
 int fbus_ekf_abi_version(void);
 size_t fbus_params_size(void);
 
@@ -341,6 +343,33 @@ int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kco
 int fbus_ekf_frames_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
                               const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
                               const void* quat, int mode, const uint8_t* skip);
+
+/* The two windows above WITH THEIR TRAJECTORY: one state per camera frame, the reference's product -- matlab/FBUS_EKF.m:201-204 appends
+ * ekfState (p, v, q, ba, bg, g) to EKFResults after every frame, C++/src/filter.cpp:238-248 one fusion.txt row.  Arguments before the
+ * three outputs: those of the twin, with the same checks (all made before the first launch).  Outputs, device memory, each may be NULL
+ * (not written):
+ *   out_nominal  [nframes][B][19] in the handle's dtype, the get_state order p3 v3 q4(wxyz) ba3 bg3 g3
+ *   out_pdiag    [nframes][B][N]  the diagonal of P
+ *   out_applied  [nframes][B]     1 where frame f's update ran: what fbus_ekf_get_applied would report after frame f alone
+ * Row f is the state after frame f's update (after its predicts where the update did not run: skip, no usable marker, M = 0).  The
+ * records, fbus_ekf_get_applied and every other effect are bit-identical to the twin's on the same inputs; with all three outputs NULL
+ * the call IS the twin.  Row f equals what fbus_ekf_get_state (nominal, diag P) / fbus_ekf_get_applied report after the same frame run
+ * alone, bit for bit wherever the twin's window equals its frames bit for bit.  The one-wave resident window kernels write the rows
+ * from their registers; every other route (fp64 records, Joseph + nearest, team / small launches, nframes == 1 for the pixel / corner
+ * rows) already runs frame by frame and adds fbus_ekf_snapshot_dev's kernel behind each frame.
+ * The outputs must not overlap the records (FBUS_ERR_INVALID) nor any input array (not checked). */
+int fbus_ekf_frames_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                                   const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
+                                   const void* quat, int mode, const uint8_t* skip,
+                                   void* out_nominal, void* out_pdiag, uint8_t* out_applied);
+int fbus_ekf_frames_meas_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                                        const void* dt, int dt_per_filter, int kind, int M, const int32_t* ids, const void* left,
+                                        const void* right, int geometry, int mode, const uint8_t* skip,
+                                        void* out_nominal, void* out_pdiag, uint8_t* out_applied);
+/* The pose and its sigma of every filter from the current records, without the full covariance of fbus_ekf_get_state_dev: nominal
+ * B x 19 (get_state order), pdiag B x N = diag(P), applied B (= fbus_ekf_get_applied).  Device pointers, each may be NULL;
+ * stream-ordered.  Equal to get_state's nominal and diag(P) bit for bit (the same index map).  Outputs must not overlap the records. */
+int fbus_ekf_snapshot_dev(fbus_ekf_t h, void* nominal, void* pdiag, uint8_t* applied);
 
 /* ---- initialisation / reset (the callers' side of the path) ------------------- */
 /* Replaces: InitGravityAndGyrobias (matlab/InitGravityAndGyrobias.m:36-40) /
