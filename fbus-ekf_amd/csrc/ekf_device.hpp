@@ -1201,6 +1201,97 @@ struct InfoAcc {
     }
 };
 
+// a value of the update handed to the NIS arithmetic through an empty asm: the widening to double must not give a product of the update a
+// second user (the compiler then stops contracting it into an fma, and the update's rounding changes)
+template <typename T> __device__ __forceinline__ double nis_in(T x) { asm("" : "+v"(x)); return (double)x; }
+
+// ---- NIS outputs of the update kernels (fbus_ekf_correct*_nis*): a trailing kernel parameter pack NO... = NisOut<T>, empty for the
+// existing instantiations.  nis [B] in T, dof [B] int32 (each may be null); thr: the handle's gate table on the device
+template <typename T> struct NisOut { T* nis; int* dof; const double* thr; };
+template <typename T> __device__ __forceinline__ NisOut<T> nis_out() { return NisOut<T>{ nullptr, nullptr, nullptr }; }
+template <typename T> __device__ __forceinline__ NisOut<T> nis_out(const NisOut<T>& o) { return o; }
+template <typename T>
+__device__ __forceinline__ void nis_write(const NisOut<T>& o, int b, double nis, int dof)
+{
+    if (o.nis) o.nis[b] = (T)nis;
+    if (o.dof) o.dof[b] = dof;
+}
+
+// NIS of the pose rows at the prior: sumw - b' (P_JJ^-1 + Lam)^-1 b  (sumw = sum w res^2; Lam, b of the fold), in double.
+// With P_JJ = C C' and K = I + C' Lam C = D D' (eigenvalues >= 1: no pivoting needed), (P_JJ^-1 + Lam)^-1 = C K^-1 C', so the
+// subtracted term is |D^-1 C' b|^2 -- the same value as b' y with (I + P_JJ Lam) y = P_JJ b.  A pivot of P_JJ that is not positive
+// drops its column (no prior uncertainty in that direction: the term has nothing to take from it).
+template <typename T>
+__device__ __forceinline__ double pose_nis(const InfoAcc<T>& acc, const double* PJJ, double sumw)
+{
+    double C[36];
+#pragma unroll
+    for (int i = 0; i < 36; ++i) C[i] = 0.0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double piv = PJJ[6 * a + a];
+#pragma unroll
+        for (int k = 0; k < a; ++k) piv -= C[6 * a + k] * C[6 * a + k];
+        const bool ok = piv > 0.0;
+        const double sq = ok ? sqrt(piv) : 0.0, is = ok ? 1.0 / sq : 0.0;
+        C[6 * a + a] = sq;
+#pragma unroll
+        for (int i = a + 1; i < 6; ++i) {
+            double v = PJJ[6 * i + a];
+#pragma unroll
+            for (int k = 0; k < a; ++k) v -= C[6 * i + k] * C[6 * a + k];
+            C[6 * i + a] = v * is;
+        }
+    }
+    double LC[36];                                        // Lam C
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            double v = 0.0;
+#pragma unroll
+            for (int k = j; k < 6; ++k) v += nis_in(acc.Lam[i <= k ? lidx(i, k) : lidx(k, i)]) * C[6 * k + j];
+            LC[6 * i + j] = v;
+        }
+    double K[36];                                         // I + C' Lam C (lower triangle), then its Cholesky factor D in place
+#pragma unroll
+    for (int i = 0; i < 6; ++i)
+#pragma unroll
+        for (int j = 0; j <= i; ++j) {
+            double v = (i == j) ? 1.0 : 0.0;
+#pragma unroll
+            for (int k = i; k < 6; ++k) v += C[6 * k + i] * LC[6 * k + j];
+            K[6 * i + j] = v;
+        }
+#pragma unroll
+    for (int a = 0; a < 6; ++a) {
+        double piv = K[6 * a + a];
+#pragma unroll
+        for (int k = 0; k < a; ++k) piv -= K[6 * a + k] * K[6 * a + k];
+        const double sq = sqrt(piv), is = 1.0 / sq;
+        K[6 * a + a] = sq;
+#pragma unroll
+        for (int i = a + 1; i < 6; ++i) {
+            double v = K[6 * i + a];
+#pragma unroll
+            for (int k = 0; k < a; ++k) v -= K[6 * i + k] * K[6 * a + k];
+            K[6 * i + a] = v * is;
+        }
+    }
+    double v[6], q = 0.0;                                 // v = D^-1 C' b
+#pragma unroll
+    for (int i = 0; i < 6; ++i) {
+        double u = 0.0;
+#pragma unroll
+        for (int k = i; k < 6; ++k) u += C[6 * k + i] * nis_in(acc.b[k]);
+#pragma unroll
+        for (int k = 0; k < i; ++k) u -= K[6 * i + k] * v[k];
+        v[i] = u / K[6 * i + i];
+        q += v[i] * v[i];
+    }
+    return sumw - q;
+}
+
 // the 7 rows of one marker into the accumulator
 template <typename T, int N, int DIALECT>
 __device__ __forceinline__ void marker_info(InfoAcc<T>& acc, const T* pqr, const DevConst<T>& dc, const MarkerCommon<T, N>& mc,
@@ -1228,8 +1319,16 @@ __device__ __forceinline__ void marker_info(InfoAcc<T>& acc, const T* pqr, const
 //     The C++ dialect still needs the residual: b_theta += w s M1' (Rq(Qm)' rq).
 // Per marker ~75 (Matlab) / ~135 (C++) instructions instead of ~275.
 // --------------------------------------------------------------------------------
-template <typename T, int N, int DIALECT>
-struct PoseFold {
+// NIS (the NIS kernels only): also sum rp^2 over the position rows and, C++ dialect, rq^2 over the quaternion rows, in double
+// (sr2p / sr2q of the base PoseNisSums<true>; empty otherwise, so the existing instantiations keep their layout and code; not among
+// the NVAL exchange values -- the NIS kernels run one wave per filter)
+template <bool NIS> struct PoseNisSums {};
+template <> struct PoseNisSums<true> {
+    double sr2p, sr2q;
+    __device__ __forceinline__ void clear_nis() { sr2p = 0.0; sr2q = 0.0; }
+};
+template <typename T, int N, int DIALECT, bool NIS = false>
+struct PoseFold : PoseNisSums<NIS> {
     T sH[9], sr[3], Ltt[6], bt[3], csum, cnt, btq[3];
     __device__ __forceinline__ void clear()
     {
@@ -1268,6 +1367,10 @@ struct PoseFold {
             Hpt[3 * i + 0] = l1 * ru[2] - l2 * ru[1];
             Hpt[3 * i + 1] = l2 * ru[0] - l0 * ru[2];
             Hpt[3 * i + 2] = l0 * ru[1] - l1 * ru[0];
+        }
+        if constexpr (NIS) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { const double r = nis_in(rp[i]); this->sr2p = __builtin_fma(r, r, this->sr2p); }
         }
 #pragma unroll
         for (int i = 0; i < 9; ++i) sH[i] += Hpt[i];
@@ -1316,6 +1419,10 @@ struct PoseFold {
             T rq[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) rq[i] = yq[i] - sq * hq[i];
+            if constexpr (NIS) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { const double r = nis_in(rq[i]); this->sr2q = __builtin_fma(r, r, this->sr2q); }
+            }
             // v = Rq(Qm)' rq   (Rq as in marker_rows: rows (w -x -y -z ; x w z -y ; y -z w x ; z y -x w))
             const T v[4] = { Qm[0] * rq[0] + Qm[1] * rq[1] + Qm[2] * rq[2] + Qm[3] * rq[3],
                              -Qm[1] * rq[0] + Qm[0] * rq[1] - Qm[3] * rq[2] + Qm[2] * rq[3],

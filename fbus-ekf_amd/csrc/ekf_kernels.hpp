@@ -577,14 +577,22 @@ predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, 
 // then runs while the covariance is still on its way in.  Lanes that are skipped or past B run along with no markers
 // and leave before the stores: an early exit in front of the loads would let the compiler sink loads into the live
 // branch, behind the covariance stream.
-template <typename T, int N, int DIALECT, int COV, bool JOINT, bool SPLIT = (sizeof(T) == 8)>
+// NO = NisOut<T> (fbus_ekf_correct_nis*; kernels_tu.hip family 13, never the fp32 row-split form): the NIS and dof of the applied rows
+// (pose_nis, from the fold's Lam / b and P_JJ, in double) and the gate, decided in front of the first store of every route.
+template <typename T, int N, int DIALECT, int COV, bool JOINT, bool SPLIT = (sizeof(T) == 8), typename... NO>
 __global__ void __launch_bounds__(BLOCK, FBUS_X_CORRECT_WAVES)
 correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ pos,
                const T* __restrict__ quat, int mode, const unsigned char* __restrict__ skip,
-               unsigned char* __restrict__ applied, DevConst<T> dc)
+               unsigned char* __restrict__ applied, DevConst<T> dc, NO... no)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
+    constexpr bool NIS = sizeof...(NO) > 0;
+    static_assert(!NIS || sizeof(T) == 8 || !SPLIT, "the fp32 NIS kernels are the one-wave forms");
+    const NisOut<T> nout = nis_out<T>(no...);
+    double nisv = 0.0;
+    int dofv = 0;
+    constexpr int ROWS = DIALECT == DIALECT_CPP ? 7 : 3;             // rows with a residual per marker (Matlab: q residual zeroed)
     constexpr int G = FBUS_MARKER_GROUP;
     const bool vec = (mode & MODE_MEAS_VEC) != 0;     // set by the launcher: 16-byte loads of the measurement inputs are legal
     mode &= ~MODE_MEAS_VEC;
@@ -665,6 +673,30 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         load_chunks<T, N, C_E, RC::NCH, AUX_NT>(rs, my_lane(), P + (C_E - RC::CH_NOM) * RC::EPC);
         if (go) joint_apply_late<T, N, COV, RS>(P, dx, stash);
     };
+    // NIS of nm markers' folded rows at the prior and the gate: true = rejected.  P_JJ from the registers, or (LEAN: the covariance is
+    // not loaded yet) from the record.  Branch-free, and called unconditionally: a branch between the fold and the update splits the
+    // blocks the compiler contracts products within, and the update would round differently from the twin's
+    auto nis_gate = [&](const InfoAcc<T>& acc, const auto& fold, int nm, bool from_regs) __attribute__((always_inline)) {
+        double PJJ[36];
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) {
+                const int o = pidx<N>(jcol(i), jcol(j));
+                const double v = from_regs ? (double)P[o] : (double)recs[elem_index<T, N>(bc, L::OFF_COV + o)];
+                PJJ[6 * i + j] = v; PJJ[6 * j + i] = v;
+            }
+        const double sumw = (double)fb_rcp1(dc.r_pos) * fold.sr2p + (DIALECT == DIALECT_CPP ? (double)fb_rcp1(dc.r_quat) * fold.sr2q : 0.0);
+        nisv = pose_nis<T>(acc, PJJ, sumw);
+        dofv = ROWS * nm;
+        return nisv > nout.thr[dofv];                                  // (the launcher always passes the handle's table: +inf without one)
+    };
+    // the statistic folds the rows a second time from an opaque copy of the nominal state: shared with the update's fold, the fold's
+    // products would gain users in the NIS arithmetic and the compiler would contract them differently (the update must stay the twin's)
+    auto opaque_nom = [&](T* c) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < L::NNOM; ++i) { T x = nom[i]; asm("" : "+v"(x)); c[i] = x; }
+    };
 
     if constexpr (JOINT) {
         // all visible markers: their rows are folded into the 6x6 information matrix while the covariance is still
@@ -674,12 +706,17 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         fold.clear();
         MarkerCommon<T, N> mc;
         mc.build(nom, dc);
+        T nomn[NIS ? L::NNOM : 1];                        // (NIS: the statistic's own fold, see opaque_nom)
+        PoseFold<T, N, DIALECT, true> fold2;
+        MarkerCommon<T, N> mc2;
+        if constexpr (NIS) { opaque_nom(nomn); fold2.clear(); fold2.clear_nis(); mc2.build(nomn, dc); }
         auto fold_group = [&]() {
             mg.resolve(tbl);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 if (mg.slot[g] < 0) continue;
                 fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
+                if constexpr (NIS) fold2.add(nomn, dc, mc2, mg.mk[g], mg.yp[g], mg.yq[g]);
                 ++used;
             }
         };
@@ -691,13 +728,17 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
             fold_group();
         }
         fold.finish(acc, nom, dc, mc);
+        InfoAcc<T> acc2;
+        if constexpr (NIS) fold2.finish(acc2, nomn, dc, mc2);
         if constexpr (LEAN) {
             InfoFactors<T> fac;
+            if constexpr (NIS) { const bool rj = nis_gate(acc2, fold2, used, false); used = rj ? 0 : used; }
             if (used > 0) joint_factor<T>(acc, fac);
             lean_passes(fac, used > 0);
         } else {
             order_fence();
             load_chunks<T, N, C_SPLIT, RC::NCH, FBUS_X_CORRECT_LD>(rs, my_lane(), P + (C_SPLIT - RC::CH_NOM) * RC::EPC);
+            if constexpr (NIS) { const bool rj = nis_gate(acc2, fold2, used, true); used = rj ? 0 : used; }
             // the last of the six passes stores every covariance chunk as soon as its rows are final (FBUS_X_STREAM_ST)
             if (used > 0) {
                 if constexpr (STREAM_ST) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
@@ -765,30 +806,71 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
                 fold.finish(acc, nom, dc, mc);
                 joint_factor<T>(acc, fac);
                 used = 1;
+                if constexpr (NIS) {                                                   // (the statistic's own fold, see opaque_nom)
+                    T nomn[L::NNOM];
+                    opaque_nom(nomn);
+                    MarkerCommon<T, N> mc2;
+                    mc2.build(nomn, dc);
+                    InfoAcc<T> acc2;
+                    PoseFold<T, N, DIALECT, true> fold2;
+                    fold2.clear();
+                    fold2.clear_nis();
+                    fold2.add(nomn, dc, mc2, mk, min_y, min_y + 3);
+                    fold2.finish(acc2, nomn, dc, mc2);
+                    const bool rj = nis_gate(acc2, fold2, 1, false);
+                    used = rj ? 0 : 1;
+                    new_prev = rj ? -1 : new_prev;
+                }
             }
             lean_passes(fac, used > 0);
-        } else if (slot >= 0) {
-            if (DIALECT == DIALECT_CPP) new_prev = min_id;                           // filter.cpp:675
-            T mk[MK_STRIDE];
+        } else {
+            // (NIS: the statistic of the chosen marker -- slot 0's frame where there is none -- in front of the one branch the twin has
+            // too, which then also takes the gate: no branch of its own between the fold and the update, see nis_gate)
+            bool rej = false;
+            if constexpr (NIS) {
+                const int sl = slot >= 0 ? slot : 0;
+                T mk[MK_STRIDE];
 #pragma unroll
-            for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[slot * MK_STRIDE + k];
-            MarkerCommon<T, N> mc;
-            mc.build(nom, dc);
-            if constexpr (NEAREST_INFO) {
+                for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[sl * MK_STRIDE + k];
+                T nomn[L::NNOM];
+                opaque_nom(nomn);
+                MarkerCommon<T, N> mc;
+                mc.build(nomn, dc);
                 InfoAcc<T> acc;
-                PoseFold<T, N, DIALECT> fold;
+                PoseFold<T, N, DIALECT, true> fold;
                 fold.clear();
-                fold.add(nom, dc, mc, mk, min_y, min_y + 3);
-                fold.finish(acc, nom, dc, mc);
-                if constexpr (STREAM_ST) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
-                else joint_update<T, N, COV>(P, dx, acc);
-            } else {
-                marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mk, min_y, min_y + 3);
+                fold.clear_nis();
+                fold.add(nomn, dc, mc, mk, min_y, min_y + 3);
+                fold.finish(acc, nomn, dc, mc);
+                rej = nis_gate(acc, fold, slot >= 0 ? 1 : 0, true);
+                nisv = slot >= 0 ? nisv : 0.0;
             }
-            used = 1;
+            if (slot >= 0 && !rej) {
+                if (DIALECT == DIALECT_CPP) new_prev = min_id;                       // filter.cpp:675
+                T mk[MK_STRIDE];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[slot * MK_STRIDE + k];
+                MarkerCommon<T, N> mc;
+                mc.build(nom, dc);
+                if constexpr (NEAREST_INFO) {
+                    InfoAcc<T> acc;
+                    PoseFold<T, N, DIALECT> fold;
+                    fold.clear();
+                    fold.add(nom, dc, mc, mk, min_y, min_y + 3);
+                    fold.finish(acc, nom, dc, mc);
+                    if constexpr (STREAM_ST) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
+                    else joint_update<T, N, COV>(P, dx, acc);
+                } else {
+                    marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mk, min_y, min_y + 3);
+                }
+                used = 1;
+            }
         }
     }
-    if (used == 0) { if (b < B) applied[b] = 0; return; }
+    if (used == 0) {
+        if (b < B) { applied[b] = 0; if constexpr (NIS) nis_write(nout, b, nisv, dofv); }
+        return;
+    }
     if constexpr (LEAN) {               // the nominal state was not held across the passes: read it again (L2-hot)
         order_fence();
         load_chunks<T, N, 0, RC::CH_NOM>(rs, my_lane(), nom);
@@ -801,6 +883,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     constexpr int C_REST = LEAN ? Hook::fin(RS) : (STREAM_ST ? Hook::streamed_end() : RC::CH_NOM);
     store_chunks<T, N, C_REST, RC::NCH, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (C_REST - RC::CH_NOM) * RC::EPC);
     applied[b] = 1;
+    if constexpr (NIS) nis_write(nout, b, nisv, dofv);
 }
 
 // One camera frame in ONE launch: K ImuUpdates then one MeasureUpdate with the record resident in

@@ -33,6 +33,12 @@ void launch_predict_k(hipStream_t s, T* recs, int B, int K, int policy, const T*
 template <typename T, int N, int D>
 void launch_correct_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode,
                       bool joseph, const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp);
+// the same update with the NIS output and the gate (kernels_tu.hip family 13: correct_kernel with NisOut; fp32 never row-split):
+// nis [B] in T, dof [B] (device, each may be null), thr: the handle's gate table on the device
+template <typename T, int N, int D>
+void launch_correct_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                          const double* thr);
 
 template <typename T, int N, int D>
 void launch_frame_k(hipStream_t s, T* recs, int B, int K, const T* accel, const T* gyro, const T* dt, int dt_stride,
@@ -97,6 +103,17 @@ template <typename T, int N, int D>
 void launch_corners2_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
                        int roles, double size, double r_pos, double switch_thres, const unsigned char* skip, unsigned char* applied,
                        const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct);
+// the two updates above with the NIS output and the gate (kernels_tu.hip family 12: NisOut, one wave per tile): nis [B] in T and dof [B]
+// (device, each may be null); thr: the handle's gate table on the device (null: no gate; its length was checked against the largest dof)
+template <typename T, int N, int D>
+void launch_pixels2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size, double r_pix,
+                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                          const double* thr);
+template <typename T, int N, int D>
+void launch_corners2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                           double size, double r_pos, double switch_thres, const unsigned char* skip, unsigned char* applied,
+                           const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof,
+                           const double* thr);
 
 // ---- one camera frame with the north star's MeasureUpdate in one launch (ekf_meas.hpp::frame_meas_kernel; fp32) -----------------
 // kind: corner pixels (geometry / mode ignored; right == nullptr: left camera) or stereo corners (geometry, mode as correct_corners)

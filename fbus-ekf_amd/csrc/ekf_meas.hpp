@@ -194,6 +194,10 @@ __device__ __forceinline__ void port_start_f32(const MeasConst& mc, const double
 struct PixAcc {
     double Saa[6], Sac[9], Scc[6], sa[3], sc[3];          // symmetric ones in the order 00 01 02 11 12 22
     static constexpr int NVAL = 27;
+    // the NIS kernels only (fold<..., NIS = true>): sum w_row res^2 over the rows (weight 0 / 1 per row, w = 1 / r left out) and their
+    // count; not among the NVAL partial sums -- the NIS kernels run one wave per tile
+    double sr2, nrow;
+    __device__ __forceinline__ void clear_nis() { sr2 = 0.0; nrow = 0.0; }
     __device__ __forceinline__ void clear()
     {
 #pragma unroll
@@ -432,7 +436,9 @@ __device__ __forceinline__ void filter_pil(const double* R, const double* P_IL, 
 // 906 -> 825 arithmetic instructions per marker in the compiled loop (EXPERIMENTS -1.12).  The same rows for BOTH cameras (the right camera's
 // taken to the left camera's frame, 15 operations per projection) was built and is slower: the stereo fold goes corner by corner over N' =
 // sum j j' (PixAcc::add_corner), where the sparse rows save little, and its two halves would each form the Y_k.
-template <int NCAM, typename T, bool NZ, int NK = 4, int K0 = 0, bool CF = false>
+// NIS: also sum vis res^2 and count the rows of non-zero weight (PixAcc::sr2 / nrow; the camera-frame rows are a rotation of the image
+// residual, whose norm they keep, so the sum is taken on the image residual in every form)
+template <int NCAM, typename T, bool NZ, int NK = 4, int K0 = 0, bool CF = false, bool NIS = false>
 __device__ __forceinline__ void pixel_fold_marker(PixAcc& acc, const double* p, const double* R, const double* pil,
                                                   const MeasConst& mc, const double* mkc, const T* yl, const T* yr, double size, double wgt = 1.0)
 {
@@ -591,6 +597,7 @@ __device__ __forceinline__ void pixel_fold_marker(PixAcc& acc, const double* p, 
         for (int q = 0; q < NP; ++q) {
             const int k = K0 + q;
             const double r0 = (double)yl[2 * k] - uv[q][0], r1 = (double)yl[2 * k + 1] - uv[q][1];
+            if constexpr (NIS) { acc.sr2 += vis[q] * __builtin_fma(r1, r1, r0 * r0); acc.nrow += vis[q] != 0.0 ? 2.0 : 0.0; }
             const double jr = iLt[q] * vis[q], kv = kk[q] * vis[q];
             const double jrad[3] = { jr * e[q][0], jr * e[q][1], -(c2[q] * vis[q]) };
             acc.add_row_cf(jrad, __builtin_fma(e[q][1], r1, e[q][0] * r0), Yc[q]);                                  // res_rad = e . res
@@ -665,6 +672,13 @@ __device__ __forceinline__ void pixel_fold_marker(PixAcc& acc, const double* p, 
             }
         }
     }
+    if constexpr (NIS) {
+#pragma unroll
+        for (int q = 0; q < NP; ++q) {
+            acc.sr2 += vis[q] * __builtin_fma(res[q][1], res[q][1], res[q][0] * res[q][0]);
+            acc.nrow += vis[q] != 0.0 ? 2.0 : 0.0;
+        }
+    }
     if constexpr (NCAM == 1) {
         // two rows per corner: straight into the sums (PixAcc::add_row)
 #pragma unroll
@@ -699,14 +713,14 @@ __device__ __forceinline__ void pixel_fold_marker(PixAcc& acc, const double* p, 
 
 // one marker, both cameras, as two passes of two corners each (see NK, K0 above): the same projections, rows and sums, corner by corner
 // in the same order -- bit-equal to pixel_fold_marker<2, T, NZ>
-template <typename T, bool NZ>
+template <typename T, bool NZ, bool NIS = false>
 __device__ __forceinline__ void pixel_fold_marker_stereo_halves(PixAcc& acc, const double* p, const double* R, const double* pil,
                                                                 const MeasConst& mc, const double* mkc, const T* yl, const T* yr, double size,
                                                                 double wgt = 1.0)
 {
-    pixel_fold_marker<2, T, NZ, 2, 0>(acc, p, R, pil, mc, mkc, yl, yr, size, wgt);
+    pixel_fold_marker<2, T, NZ, 2, 0, false, NIS>(acc, p, R, pil, mc, mkc, yl, yr, size, wgt);
     order_fence();
-    pixel_fold_marker<2, T, NZ, 2, 2>(acc, p, R, pil, mc, mkc, yl, yr, size, wgt);
+    pixel_fold_marker<2, T, NZ, 2, 2, false, NIS>(acc, p, R, pil, mc, mkc, yl, yr, size, wgt);
 }
 
 
@@ -854,6 +868,8 @@ __device__ __forceinline__ void tri_corners_refractive(const VisConst<double>& v
 // the four corner positions C (left camera frame, as triangulated) of one marker as 12 position-type rows:
 //   h_k = R_IL (ru_k - P_IL),  rows a_i = (R_IL)_i' for every corner:  N' = R_IL' R_IL (constant, mc.NI),  n' = R_IL' (C_k - h_k)
 // (MeasureUpdate.m:67,72-73 with the corner in place of the marker origin; oracle: fbo_correct_corners)
+// NIS: also sum |C - h|^2 (F is a sign flip: |F res| = |res|) and count the 12 rows (PixAcc::sr2 / nrow)
+template <bool NIS = false>
 __device__ __forceinline__ void corner_fold_marker(PixAcc& acc, const double* p, const double* R, const double* pil,
                                                    const MeasConst& mc, const double* mkc, const double (&C)[4][3], double size)
 {
@@ -888,6 +904,7 @@ __device__ __forceinline__ void corner_fold_marker(PixAcc& acc, const double* p,
 #pragma unroll
         for (int j = 0; j < 3; ++j) np[j] = mc.McL[j] * fr[0] + mc.McL[3 + j] * fr[1] + mc.McL[6 + j] * fr[2];
         acc.add_corner_const(np, ru[k]);                  // (the caller expands the sums with mc.NI before the 6 x 6 stage)
+        if constexpr (NIS) { acc.sr2 += PixAcc::dp3(fr[0], fr[0], fr[1], fr[1], fr[2], fr[2]); acc.nrow += 3.0; }
     }
 }
 
@@ -895,8 +912,9 @@ __device__ __forceinline__ void corner_fold_marker(PixAcc& acc, const double* p,
 // in: Lam (21, lidx order), b (6), PJJ (36, full symmetric);  out: G = (I + P_JJ Lam)^-1 (36), Sinv = (Lam^-1 + P_JJ)^-1 (21,
 // lidx order), m = G' b (6)
 __host__ __device__ constexpr int ltx(int i, int j) { return i * (i + 1) / 2 + j; }      // lower triangle, j <= i
-template <typename T>
-__device__ __forceinline__ void info_solve(const double* Lam, const double* b, const double* PJJ, T* G, T* Sinv, T* m)
+// MD (the NIS kernels): m in double as well, md = G' b before the cast to T
+template <typename T, bool MD = false>
+__device__ __forceinline__ void info_solve(const double* Lam, const double* b, const double* PJJ, T* G, T* Sinv, T* m, double* md = nullptr)
 {
     // Lam = Lc Lc' (no pivoting: Lam is positive semi-definite; a pivot that is not clearly positive relative to its original
     // diagonal carries no information and its column is dropped -- joint_factor's rule)
@@ -991,6 +1009,7 @@ __device__ __forceinline__ void info_solve(const double* Lam, const double* b, c
 #pragma unroll
         for (int i = 0; i < 6; ++i) s += Gd[6 * i + j] * b[i];
         m[j] = (T)s;
+        if constexpr (MD) md[j] = s;
     }
 #pragma unroll
     for (int i = 0; i < 36; ++i) G[i] = (T)Gd[i];
@@ -1288,12 +1307,31 @@ __device__ __forceinline__ void meas_solve_update(T* P, const PixAcc& acc, const
 // (Round 6 tried two things around it, both measured slower and kept as patches only: the covariance through LDS while the fold runs --
 // gfx950's direct-to-LDS 16-byte loads, requested at the top of the kernel or behind the last marker's fetch, tools/patches/
 // r06_meas_lds_prefetch.diff -- and the left camera's markers two at a time, tools/patches/r06_meas_pair.diff; EXPERIMENTS -1.5.)
-template <typename T, int N>
+// The NIS kernels (NIS = true, ns != null): the normalised innovation squared of the stacked rows at the prior, in double --
+//     NIS = r' S^-1 r = w sum res^2 - b' P_JJ m     (S^-1 r = R^-1 (r - H dx),  dx_J = P_JJ m,  m = G' b)
+// -- and the gate: NIS > ns->thr leaves the record alone (nothing below the 6 x 6 stage runs: no covariance store, no injection).
+struct NisState { double thr, nis; bool reject; };
+template <typename T, int N, bool NIS = false>
 __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs, unsigned lane, const PixAcc& acc, const double* Rd, double w,
-                                                 int new_prev, T* gpark /* fp64 records: this lane's column of 36 x 64 values in LDS */)
+                                                 int new_prev, T* gpark /* fp64 records: this lane's column of 36 x 64 values in LDS */,
+                                                 NisState* ns = nullptr)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
+    // NIS from the 6 x 6 stage's inputs and its m in double (see NisState); true: the gate rejects the update
+    auto nis_gate = [&](const double* bv, const double* PJJ, const double* md) __attribute__((always_inline)) {
+        double bPm = 0.0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            double s = 0.0;
+#pragma unroll
+            for (int k = 0; k < 6; ++k) s = __builtin_fma(PJJ[6 * i + k], md[k], s);
+            bPm = __builtin_fma(bv[i], s, bPm);
+        }
+        ns->nis = w * acc.sr2 - bPm;
+        ns->reject = ns->nis > ns->thr;
+        return ns->reject;
+    };
     if constexpr (sizeof(T) == 8) {
         // fp64 records (round 5): 171 covariance doubles are 342 registers, the 6 x 6 stage wants ~220 and the update 63 coefficients
         // (126 registers) beside the covariance: held all at once the kernels spilled 650-790 bytes per lane.  So:
@@ -1315,7 +1353,13 @@ __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
                     for (int j = 0; j < 6; ++j) PJJ[6 * i + j] = (double)P[pidx<N>(jcol(i), jcol(j))];
-                info_solve<T>(Lam, bv, PJJ, G, cs.s, cs.m_);
+                if constexpr (NIS) {
+                    double md[6];
+                    info_solve<T, true>(Lam, bv, PJJ, G, cs.s, cs.m_, md);
+                    if (nis_gate(bv, PJJ, md)) return;          // in front of the first store
+                } else {
+                    info_solve<T>(Lam, bv, PJJ, G, cs.s, cs.m_);
+                }
             }
 #pragma unroll
             for (int i = 0; i < 36; ++i) gpark[i * 64] = G[i];
@@ -1364,7 +1408,13 @@ __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs
             for (int i = 0; i < 6; ++i)
 #pragma unroll
                 for (int j = 0; j < 6; ++j) PJJ[6 * i + j] = (double)P[pidx<N>(jcol(i), jcol(j))];
-            info_solve<T>(Lam, bv, PJJ, G, Sinv, m);
+            if constexpr (NIS) {
+                double md[6];
+                info_solve<T, true>(Lam, bv, PJJ, G, Sinv, m, md);
+                if (nis_gate(bv, PJJ, md)) return;              // in front of the update and every store
+            } else {
+                info_solve<T>(Lam, bv, PJJ, G, Sinv, m);
+            }
         }
         RegCoef<T> cf;
         cf.set(G, Sinv, m);
@@ -1392,15 +1442,39 @@ struct alignas(16) MeasLDS {
 // correct() from corner pixels: all visible markers, 2 (left camera) or 4 (stereo) reprojection rows per corner, one
 // linearisation point.  One filter per lane; NR waves ("roles") per 64-filter tile divide the markers among themselves
 // (role r folds markers r, r + NR, ...; their sums meet in LDS, in role order) and role 0 applies the update.
+// NO = NisOut<T> (fbus_ekf_correct_pixels_nis*, fbus_ekf_correct_corners_nis*; NR = 1 only, instantiated in a family of its own:
+// kernels_tu.hip "measnis"): the NIS and the dof of every filter, and the gate (meas_update_tail's NisState).
 // =================================================================================
-template <typename T, int N, int NR, bool NZ, int CAM = 0>
+// the filters that leave without an update: nis = 0, dof = 0
+template <typename T>
+__device__ __forceinline__ void nis_none(const NisOut<T>& o, int b)
+{
+    if (o.nis) o.nis[b] = T(0);
+    if (o.dof) o.dof[b] = 0;
+}
+// the gate of dof rows (+inf without a table), the tail, then the outputs; returns whether the update was applied
+template <typename T, int N>
+__device__ __forceinline__ bool nis_tail(const NisOut<T>& o, int b, const __amdgpu_buffer_rsrc_t rs, unsigned lane, const PixAcc& acc,
+                                         const double* Rd, double w, int new_prev, T* gpark)
+{
+    const int dof = (int)acc.nrow;
+    NisState ns{ o.thr ? o.thr[dof] : __builtin_inf(), 0.0, false };
+    meas_update_tail<T, N, true>(rs, lane, acc, Rd, w, new_prev, gpark, &ns);
+    if (o.nis) o.nis[b] = (T)ns.nis;
+    if (o.dof) o.dof[b] = dof;
+    return !ns.reject;
+}
+template <typename T, int N, int NR, bool NZ, int CAM = 0, typename... NO>
 __global__ void __launch_bounds__(64 * NR)
 correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ left,
                        const T* __restrict__ right, double size, double r_pix, const unsigned char* __restrict__ skip,
-                       unsigned char* __restrict__ applied, const short* __restrict__ id2slot, MeasConst mc)
+                       unsigned char* __restrict__ applied, const short* __restrict__ id2slot, MeasConst mc, NO... no)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
+    constexpr bool NIS = sizeof...(NO) > 0;
+    static_assert(!NIS || NR == 1, "the NIS kernels run one wave per tile");
+    const NisOut<T> nout = nis_out<T>(no...);
     constexpr int NT = 64 * NR;
     const unsigned role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lane = threadIdx.x & 63u;
@@ -1476,6 +1550,7 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
     filter_pil(Rd, mc.P_IL, pil);
     PixAcc acc;
     acc.clear();
+    if constexpr (NIS) acc.clear_nis();
     double nfold = 0.0;                                          // markers of the map this role has folded
     const int last = live ? M : 0;
 #pragma unroll 1
@@ -1498,10 +1573,10 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
             for (int k = 0; k < 8; ++k) yl_[k] = slot >= 0 ? cur.l[k] : T(0);
 #pragma unroll
             for (int k = 0; k < NRR; ++k) yr_[k] = slot >= 0 ? cur.r[k] : T(0);
-            if constexpr (CAM == 1) pixel_fold_marker<1, T, NZ, 4, 0, true>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-            else if constexpr (CAM == 2) pixel_fold_marker_stereo_halves<T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-            else if (stereo) pixel_fold_marker_stereo_halves<T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-            else pixel_fold_marker<1, T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
+            if constexpr (CAM == 1) pixel_fold_marker<1, T, NZ, 4, 0, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
+            else if constexpr (CAM == 2) pixel_fold_marker_stereo_halves<T, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
+            else if (stereo) pixel_fold_marker_stereo_halves<T, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
+            else pixel_fold_marker<1, T, NZ, 4, 0, false, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
             nfold += wgt;
         }
         cur = nxt;
@@ -1525,15 +1600,20 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
             nfold += part[PixAcc::NVAL * 64];
         }
     }
-    if (!live || nfold == 0.0) { if (b < B) applied[b] = 0; return; }
-    if constexpr (CAM == 1) {                                           // (the left-only kernel folds in the camera frame)
+    if (!live || nfold == 0.0) {
+        if (b < B) { applied[b] = 0; if constexpr (NIS) nis_none(nout, b); }
+        return;
+    }
+    if constexpr (CAM == 1 && NZ) {                                     // (the left-only kernel folds in the camera frame; square port)
         acc.to_imu_frame(mc.adjL);
         double RM[9];
         PixAcc::camera_rotation(Rd, mc.McL, RM);
+        if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, RM, 1.0 / r_pix, -1, gpark_mem + lane) ? 1 : 0; return; }
         meas_update_tail<T, N>(rs, lane, acc, RM, 1.0 / r_pix, -1, gpark_mem + lane);
         applied[b] = 1;
         return;
     }
+    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / r_pix, -1, gpark_mem + lane) ? 1 : 0; return; }
     meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / r_pix, -1, gpark_mem + lane);
     applied[b] = 1;
 }
@@ -1544,15 +1624,18 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
 // nearest marker (by its first corner; C++ dialect: hysteresis against the previous one, filter.cpp:639-664) or all of them.
 // Same structure as correct_pixels2_kernel; the triangulation of the refractive geometry runs in double.
 // =================================================================================
-template <typename T, int N, int NR, bool NZ>
+template <typename T, int N, int NR, bool NZ, typename... NO>
 __global__ void __launch_bounds__(64 * NR)
 correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ left,
                         const T* __restrict__ right, int geometry, int mode, int dialect, double size, double r_pos,
                         double switch_thres, const unsigned char* __restrict__ skip, unsigned char* __restrict__ applied,
-                        const short* __restrict__ id2slot, MeasConst mc, VisConst<double> vc, VisConst<T> vct)
+                        const short* __restrict__ id2slot, MeasConst mc, VisConst<double> vc, VisConst<T> vct, NO... no)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
+    constexpr bool NIS = sizeof...(NO) > 0;                  // (see correct_pixels2_kernel)
+    static_assert(!NIS || NR == 1, "the NIS kernels run one wave per tile");
+    const NisOut<T> nout = nis_out<T>(no...);
     constexpr int NT = 64 * NR;
     const unsigned role = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lane = threadIdx.x & 63u;
@@ -1644,6 +1727,7 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
     filter_pil(Rd, mc.P_IL, pil);
     PixAcc acc;
     acc.clear();
+    if constexpr (NIS) acc.clear_nis();
     double nfold = 0.0;
     int new_prev = -1;
     auto fold_marker = [&](const Meas& mm) __attribute__((always_inline)) {
@@ -1654,7 +1738,7 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
 #pragma unroll
         for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[slot * MKC_STRIDE + q];
         corners(mm, C);
-        corner_fold_marker(acc, pd, Rd, pil, mc, mk, C, size);
+        corner_fold_marker<NIS>(acc, pd, Rd, pil, mc, mk, C, size);
         return true;
     };
     if (mode == MODE_NEAREST) {
@@ -1708,8 +1792,12 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
             nfold += part[PixAcc::NVAL * 64];
         }
     }
-    if (!live || nfold == 0.0) { if (b < B) applied[b] = 0; return; }
+    if (!live || nfold == 0.0) {
+        if (b < B) { applied[b] = 0; if constexpr (NIS) nis_none(nout, b); }
+        return;
+    }
     acc.expand_const(mc.NI);
+    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / r_pos, new_prev, gpark_mem + lane) ? 1 : 0; return; }
     meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / r_pos, new_prev, gpark_mem + lane);
     applied[b] = 1;
 }

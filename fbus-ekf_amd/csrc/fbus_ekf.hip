@@ -25,6 +25,7 @@
 #include <new>
 #include <string>
 #include <vector>
+#include <limits>
 
 using namespace fbus;
 
@@ -148,6 +149,10 @@ struct fbus_ekf {
     double* d_mkc = nullptr;            // HostConst::mkc on the device
     short* d_id2slot = nullptr;
     unsigned char* d_applied = nullptr;
+    // the NIS gate (fbus_ekf_set_gate): FBUS_GATE_MAX_DOF + 1 thresholds on the device, +inf past gate_n (gate_n = 0: no table); allocated
+    // at create and never moved, so a captured _nis_dev call reads the table that is current at its replay
+    double* d_gate = nullptr;
+    int gate_n = 0;
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
@@ -864,6 +869,76 @@ int launch_correct_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* 
     DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip);
 }
 
+// the pose update with the NIS output and the gate (kernels_tu.hip family 13)
+template <typename T, int N, int D>
+int launch_correct_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                         void* nis, int32_t* dof)
+{
+    const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
+    h->records_warm = h->warm_after_correct;
+    launch_correct_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                  h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
+                                  (T*)nis, (int*)dof, h->d_gate);
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                       void* nis, int32_t* dof)
+{
+    DISPATCH(h, launch_correct_nis_t, h, M, ids, pos, quat, mode, skip, nis, dof);
+}
+
+// the pixel / corner updates with the NIS output and the gate (kernels_tu.hip family 12): always the one-wave-per-tile kernels
+template <typename T, int N, int D>
+int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
+                                void* nis, int32_t* dof)
+{
+    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
+        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels_nis: left / right must be 16-byte aligned device pointers");
+    const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
+    h->records_warm = h->warm_after_correct;
+    launch_pixels2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, h->prm.marker_size,
+                                  h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis, (int*)dof,
+                                  h->d_gate);
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
+                              void* nis, int32_t* dof)
+{
+    DISPATCH(h, launch_correct_pixels_nis_t, h, M, ids, left, right, skip, nis, dof);
+}
+template <typename T, int N, int D>
+int launch_correct_corners_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
+                                 const uint8_t* skip, void* nis, int32_t* dof)
+{
+    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
+        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_corners_nis: left / right must be 16-byte aligned device pointers");
+    const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
+    h->records_warm = h->warm_after_correct;
+    launch_corners2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                   h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied,
+                                   h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, h->d_gate);
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
+                               const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DISPATCH(h, launch_correct_corners_nis_t, h, M, ids, left, right, geometry, mode, skip, nis, dof);
+}
+// a call whose largest possible dof has no entry in the gate table is refused (before anything is launched)
+int check_gate_dof(fbus_ekf_t h, int max_dof, const char* where)
+{
+    if (h->gate_n > 0 && max_dof >= h->gate_n)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": the gate table has " + std::to_string(h->gate_n) +
+                                         " entries, the call can reach dof " + std::to_string(max_dof));
+    return FBUS_OK;
+}
+
 int ensure_stage(fbus_ekf_t h, int slot, size_t bytes)
 {
     if (bytes <= h->stage_cap[slot]) return FBUS_OK;
@@ -1163,6 +1238,11 @@ int fbus_ekf_create(fbus_ekf_t* out, const fbus_params* prm, int batch, int devi
     const size_t lut = h->hc.id2slot.size() * sizeof(short);
     if (hipMalloc((void**)&h->d_id2slot, lut) != hipSuccess) return bail(FBUS_ERR_NOMEM);
     if (hipMemcpy(h->d_id2slot, h->hc.id2slot.data(), lut, hipMemcpyHostToDevice) != hipSuccess) return bail(FBUS_ERR_HIP);
+    {
+        const std::vector<double> none(FBUS_GATE_MAX_DOF + 1, std::numeric_limits<double>::infinity());
+        if (hipMalloc((void**)&h->d_gate, none.size() * sizeof(double)) != hipSuccess) return bail(FBUS_ERR_NOMEM);
+        if (hipMemcpy(h->d_gate, none.data(), none.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return bail(FBUS_ERR_HIP);
+    }
     if (hipStreamSynchronize(h->stream) != hipSuccess) return bail(FBUS_ERR_HIP);
     *out = h;
     return FBUS_OK;
@@ -1190,6 +1270,7 @@ int fbus_ekf_destroy(fbus_ekf_t h)
     if (h->d_mk) (void)hipFree(h->d_mk);
     if (h->d_mkc) (void)hipFree(h->d_mkc);
     if (h->d_id2slot) (void)hipFree(h->d_id2slot);
+    if (h->d_gate) (void)hipFree(h->d_gate);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     (void)fbus_ekf_comm_destroy(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1747,6 +1828,126 @@ int fbus_ekf_correct_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void*
     if ((rc = stage_in(h, 2, right, right ? B * M * 8 * es : 0, &dr)) != FBUS_OK) return rc;
     if ((rc = stage_in(h, 3, skip, skip ? B : 0, &ds)) != FBUS_OK) return rc;
     if ((rc = fbus_ekf_correct_pixels_dev(h, M, (const int32_t*)di, dl, dr, (const uint8_t*)ds)) != FBUS_OK) return rc;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FBUS_OK;
+}
+
+int fbus_ekf_set_gate(fbus_ekf_t h, int n, const double* thresholds)
+{
+    DeviceGuard guard_(h);
+    if (!h || n < 0) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_gate: not between graph_begin and graph_end");
+    if (!thresholds) n = 0;
+    if (n > FBUS_GATE_MAX_DOF + 1) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_gate: more than FBUS_GATE_MAX_DOF + 1 thresholds");
+    std::vector<double> thr(FBUS_GATE_MAX_DOF + 1, std::numeric_limits<double>::infinity());
+    for (int i = 0; i < n; ++i) {
+        if (!(thresholds[i] >= 0.0)) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_gate: thresholds must be >= 0 (+inf allowed, NaN not)");
+        thr[i] = thresholds[i];
+    }
+    HIP_TRY(h, hipMemcpyAsync(h->d_gate, thr.data(), thr.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (thr is a local)
+    h->gate_n = n;
+    return FBUS_OK;
+}
+
+int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                             void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
+    const int rows = h->prm.dialect == FBUS_DIALECT_CPP ? 7 : 3;
+    const int rc = check_gate_dof(h, rows * (mode == FBUS_MODE_NEAREST ? 1 : M), "fbus_ekf_correct_nis");
+    return rc != FBUS_OK ? rc : launch_correct_nis(h, M, ids, pos, quat, mode, skip, nis, dof);
+}
+
+int fbus_ekf_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                         void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    const size_t es = esize(h), B = (size_t)h->B;
+    const void *di, *dp, *dq, *ds;
+    int rc;
+    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 1, pos, B * M * 3 * es, &dp)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 2, quat, B * M * 4 * es, &dq)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
+    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
+    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
+    if ((rc = fbus_ekf_correct_nis_dev(h, M, (const int32_t*)di, dp, dq, mode, (const uint8_t*)ds, nis ? h->stage[4] : nullptr,
+                                       dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK) return rc;
+    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
+    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FBUS_OK;
+}
+
+int fbus_ekf_correct_pixels_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
+                                    void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
+    const int rc = check_gate_dof(h, M * 8 * (right ? 2 : 1), "fbus_ekf_correct_pixels_nis");
+    return rc != FBUS_OK ? rc : launch_correct_pixels_nis(h, M, ids, left, right, skip, nis, dof);
+}
+
+int fbus_ekf_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
+                                void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    const size_t es = esize(h), B = (size_t)h->B;
+    const void *di, *dl, *dr, *ds;
+    int rc;
+    if ((rc = stage_in(h, 0, ids, B * M * sizeof(int32_t), &di)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 1, left, B * M * 8 * es, &dl)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 2, right, right ? B * M * 8 * es : 0, &dr)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 3, skip, skip ? B : 0, &ds)) != FBUS_OK) return rc;
+    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
+    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
+    if ((rc = fbus_ekf_correct_pixels_nis_dev(h, M, (const int32_t*)di, dl, dr, (const uint8_t*)ds, nis ? h->stage[4] : nullptr,
+                                              dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK) return rc;
+    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
+    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FBUS_OK;
+}
+
+int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                                     int mode, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D)
+        return FBUS_ERR_UNSUPPORTED;
+    if (geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
+    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
+    const int rc = check_gate_dof(h, 12 * (mode == FBUS_MODE_NEAREST ? 1 : M), "fbus_ekf_correct_corners_nis");
+    return rc != FBUS_OK ? rc : launch_correct_corners_nis(h, M, ids, left, right, geometry, mode, skip, nis, dof);
+}
+
+int fbus_ekf_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                                 int mode, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    const size_t es = esize(h), B = (size_t)h->B;
+    const size_t lw = geometry == FBUS_VIS_CORNERS3D ? 12 : 8;
+    const void *di, *dl, *dr, *ds;
+    int rc;
+    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 1, left, B * M * lw * es, &dl)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 2, geometry == FBUS_VIS_CORNERS3D ? nullptr : right, B * M * 8 * es, &dr)) != FBUS_OK) return rc;
+    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
+    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
+    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
+    if ((rc = fbus_ekf_correct_corners_nis_dev(h, M, (const int32_t*)di, dl, dr, geometry, mode, (const uint8_t*)ds,
+                                               nis ? h->stage[4] : nullptr, dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK)
+        return rc;
+    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
+    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return FBUS_OK;
 }

@@ -11,6 +11,8 @@
 //   8 fused frame with that update (K predicts + correct_pixels / correct_corners in one launch; fp32 only)
 //  10 frame window with per-frame trajectory rows (frames_kernel with TrajOut; fp32 only)
 //  11 window of 8's frames with per-frame trajectory rows (frame_meas_kernel with TrajOut; fp32 only)
+//  12 7's updates with the NIS output and the gate (correct_pixels2_kernel / correct_corners2_kernel with NisOut; one wave per tile)
+//  13 2's update with the NIS output and the gate (correct_kernel with NisOut; fp32: never the row-split form)
 // gfx950 only.
 #include <cstdlib>
 #include "ekf_kernels.hpp"
@@ -409,8 +411,78 @@ void launch_frame_meas_traj_k(hipStream_t s, T* recs, int B, int F, const unsign
                                                                     const short*, const MeasConst&, const VisConst<double>&, \
                                                                     const VisConst<FBUS_TU_T>&, const FBUS_TU_T*, FBUS_TU_T*, \
                                                                     FBUS_TU_T*, unsigned char*);
+#elif FBUS_TU_FAMILY == 12
+// family 7's updates with NisOut: always one wave per tile (NR = 1), the kernel choice of family 7's one-wave launch
+template <typename T, int N, int D>
+void launch_pixels2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size, double r_pix,
+                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                          const double* thr)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = mc.n[0] == 0.0 && mc.n[1] == 0.0 && mc.n[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+#define FBUS_LAUNCH_PXN(NZF, CAM)                                                                                        \
+    hipLaunchKernelGGL((correct_pixels2_kernel<T, N, 1, NZF, CAM, NisOut<T>>), dim3(tiles), dim3(64), 0, s, recs, B, M, ids, left, right, \
+                       size, r_pix, skip, applied, id2slot, mc, no)
+    // (the left-camera and the stereo update apart for the tilted port too: the combined kernel spilled 36 bytes with the NIS sums)
+    if (nz) { if (right) FBUS_LAUNCH_PXN(true, 2); else FBUS_LAUNCH_PXN(true, 1); }
+    else    { if (right) FBUS_LAUNCH_PXN(false, 2); else FBUS_LAUNCH_PXN(false, 1); }
+#undef FBUS_LAUNCH_PXN
+}
+template <typename T, int N, int D>
+void launch_corners2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                           double size, double r_pos, double switch_thres, const unsigned char* skip, unsigned char* applied,
+                           const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof,
+                           const double* thr)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = vc.nrm[0] == 0.0 && vc.nrm[1] == 0.0 && vc.nrm[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+#define FBUS_LAUNCH_CRN(NZF)                                                                                             \
+    hipLaunchKernelGGL((correct_corners2_kernel<T, N, 1, NZF, NisOut<T>>), dim3(tiles), dim3(64), 0, s, recs, B, M, ids, left, right, \
+                       geometry, mode, D, size, r_pos, switch_thres, skip, applied, id2slot, mc, vc, vct, no)
+    if (nz) FBUS_LAUNCH_CRN(true); else FBUS_LAUNCH_CRN(false);
+#undef FBUS_LAUNCH_CRN
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_pixels2_nis_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                const FBUS_TU_T*, double, double, const unsigned char*, \
+                                                                unsigned char*, const short*, const MeasConst&, FBUS_TU_T*, \
+                                                                int*, const double*);                                  \
+    template void launch_corners2_nis_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                 const FBUS_TU_T*, int, int, double, double, double,   \
+                                                                 const unsigned char*, unsigned char*, const short*,   \
+                                                                 const MeasConst&, const VisConst<double>&,            \
+                                                                 const VisConst<FBUS_TU_T>&, FBUS_TU_T*, int*, const double*);
+#elif FBUS_TU_FAMILY == 13
+// family 2's kernel choice with NisOut, except the fp32 row-split form (> 1024 waves, stacked, simple form): the one-wave kernel instead
+template <typename T, int N, int D>
+void launch_correct_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                          const double* thr)
+{
+    const int grid = (B + BLOCK - 1) / BLOCK;
+    const bool joint = mode == MODE_STACKED;
+    if (M % 4 == 0 && ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(quat)) & 15) == 0 &&
+        lp.meas_vec)
+        mode |= MODE_MEAS_VEC;
+    const NisOut<T> no{ nis, dof, thr };
+    constexpr bool SPLIT = sizeof(T) == 8;
+#define FBUS_LAUNCH_CORRECTN(COV, JOINT)                                                                             \
+    hipLaunchKernelGGL((correct_kernel<T, N, D, COV, JOINT, SPLIT, NisOut<T>>), dim3(grid), dim3(BLOCK), 0, s, recs, B, M, ids, pos, \
+                       quat, mode, skip, applied, dc, no)
+    if (joseph) { if (joint) FBUS_LAUNCH_CORRECTN(COV_JOSEPH, true); else FBUS_LAUNCH_CORRECTN(COV_JOSEPH, false); }
+    else        { if (joint) FBUS_LAUNCH_CORRECTN(COV_SIMPLE, true); else FBUS_LAUNCH_CORRECTN(COV_SIMPLE, false); }
+#undef FBUS_LAUNCH_CORRECTN
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_correct_nis_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*,         \
+                                                                const FBUS_TU_T*, const FBUS_TU_T*, int, bool,         \
+                                                                const unsigned char*, unsigned char*,                  \
+                                                                const DevConst<FBUS_TU_T>&, const LaunchPolicy&,       \
+                                                                FBUS_TU_T*, int*, const double*);
 #else
-#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10 or 11"
+#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12 or 13"
 #endif
 
 FBUS_INST(DIALECT_MATLAB)

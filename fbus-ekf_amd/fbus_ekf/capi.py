@@ -22,8 +22,9 @@ STREAM_OWN = (1 << 64) - 1         # FBUS_STREAM_OWN = (void*)-1
 # fbus_ekf_launch_info (include/fbus_ekf.h)
 (INFO_SIMDS, INFO_ONE_ROUND_FILTERS, INFO_TWO_WAVE_MIN_B, INFO_BIG_RECORDS_MB, INFO_MALL_MB, INFO_L2_KB, INFO_POLICY_BATCH,
  INFO_ROLES_PREDICT, INFO_ROLES_MEAS, INFO_TEAM_FRAMES, INFO_MEAS_SPLIT) = range(11)
-ABI_VERSION = 7                    # FBUS_ABI_VERSION of the header this mirror was written against
+ABI_VERSION = 8                    # FBUS_ABI_VERSION of the header this mirror was written against
 ERR_ABI = 6
+GATE_MAX_DOF = 256                 # FBUS_GATE_MAX_DOF: a full gate table has 257 entries
 
 
 class FbusError(RuntimeError):
@@ -142,6 +143,13 @@ def load_library():
         "fbus_ekf_frames_meas_fused_traj_dev": ([H, C.c_int, ip, vp, vp, vp, C.c_int, C.c_int, C.c_int, ip, vp, vp, C.c_int, C.c_int, u8p,
                                                  vp, vp, u8p], C.c_int),
         "fbus_ekf_snapshot_dev": ([H, vp, vp, u8p], C.c_int),
+        "fbus_ekf_set_gate": ([H, C.c_int, C.POINTER(C.c_double)], C.c_int),
+        "fbus_ekf_correct_nis": ([H, C.c_int, ip, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_nis_dev": ([H, C.c_int, ip, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_pixels_nis": ([H, C.c_int, ip, vp, vp, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_pixels_nis_dev": ([H, C.c_int, ip, vp, vp, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_corners_nis": ([H, C.c_int, ip, vp, vp, C.c_int, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_corners_nis_dev": ([H, C.c_int, ip, vp, vp, C.c_int, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

@@ -381,6 +381,110 @@ class BatchedFilter:
         rc = self._lib.fbus_ekf_correct_pixels(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip))
         self._check(rc, "correct_pixels")
 
+    # ---- NIS and chi-square gating of the measurement updates (include/fbus_ekf.h) --------------------------------
+    def set_gate(self, thresholds=None):
+        """The gate table thr[dof] (e.g. gating.chi2_gate(0.999)); None or empty: no gate.  The *_nis updates leave a filter
+        untouched (applied = 0) when its nis > thr[dof]; the other updates ignore the table."""
+        if thresholds is None or len(thresholds) == 0:
+            return self._check(self._lib.fbus_ekf_set_gate(self._h, 0, None), "set_gate")
+        thr = np.ascontiguousarray(thresholds, np.float64).ravel()
+        self._check(self._lib.fbus_ekf_set_gate(self._h, int(thr.size), thr.ctypes.data_as(C.POINTER(C.c_double))), "set_gate")
+
+    def _nis_outputs(self, dev_like):
+        if dev_like is not None:
+            import torch
+            dt = torch.float32 if self.dtype == 32 else torch.float64
+            return (torch.empty(self.B, dtype=dt, device=dev_like.device), torch.empty(self.B, dtype=torch.int32, device=dev_like.device))
+        return np.empty(self.B, self.np_dtype), np.empty(self.B, np.int32)
+
+    def correct_nis(self, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
+        """correct() that also returns (nis, dof) per filter and applies the gate (set_gate): numpy arrays for host inputs,
+        device tensors for device inputs."""
+        B = self.B
+        if _is_dev(ids):
+            M = ids.numel() // B
+            self._dev_checked(ids, B * M, "ids"); self._dev_checked(pos, B * M * 3, "pos"); self._dev_checked(quat, B * M * 4, "quat")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            nis, dof = self._nis_outputs(ids)
+            self._keep += [nis, dof]
+            cur = self._order_in(ids, pos, quat, skip)
+            rc = self._lib.fbus_ekf_correct_nis_dev(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip),
+                                                    self._p(nis), self._p(dof))
+            self._check(rc, "correct_nis_dev")
+            self._order_out(cur)
+            return nis, dof
+        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
+        M = ids.shape[1]
+        pos = self._host(pos, (B, M, 3))
+        quat = self._host(quat, (B, M, 4))
+        skip = None if skip is None else self._host(skip, (B,), np.uint8)
+        nis, dof = self._nis_outputs(None)
+        rc = self._lib.fbus_ekf_correct_nis(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip),
+                                            self._p(nis), self._p(dof))
+        self._check(rc, "correct_nis")
+        return nis, dof
+
+    def correct_pixels_nis(self, ids, left, right=None, skip=None):
+        """correct_pixels() that also returns (nis, dof) per filter and applies the gate (set_gate): numpy arrays for host
+        inputs, device tensors for device inputs."""
+        B = self.B
+        if _is_dev(ids):
+            M = ids.numel() // B
+            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * 8, "left")
+            if right is not None:
+                self._dev_checked(right, B * M * 8, "right")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            nis, dof = self._nis_outputs(ids)
+            self._keep += [nis, dof]
+            cur = self._order_in(ids, left, right, skip)
+            rc = self._lib.fbus_ekf_correct_pixels_nis_dev(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip),
+                                                           self._p(nis), self._p(dof))
+            self._check(rc, "correct_pixels_nis_dev")
+            self._order_out(cur)
+            return nis, dof
+        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
+        M = ids.shape[1]
+        left = self._host(left, (B, M, 8))
+        right = None if right is None else self._host(right, (B, M, 8))
+        skip = None if skip is None else self._host(skip, (B,), np.uint8)
+        nis, dof = self._nis_outputs(None)
+        rc = self._lib.fbus_ekf_correct_pixels_nis(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip),
+                                                   self._p(nis), self._p(dof))
+        self._check(rc, "correct_pixels_nis")
+        return nis, dof
+
+    def correct_corners_nis(self, ids, left, right=None, geometry=capi.VIS_REFRACTIVE, mode=capi.MODE_NEAREST, skip=None):
+        """correct_corners() that also returns (nis, dof) per filter and applies the gate (set_gate)."""
+        B = self.B
+        w = 12 if geometry == capi.VIS_CORNERS3D else 8
+        if _is_dev(ids):
+            M = ids.numel() // B
+            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * w, "left")
+            if right is not None:
+                self._dev_checked(right, B * M * 8, "right")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            nis, dof = self._nis_outputs(ids)
+            self._keep += [nis, dof]
+            cur = self._order_in(ids, left, right, skip)
+            rc = self._lib.fbus_ekf_correct_corners_nis_dev(self._h, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
+                                                            self._p(skip), self._p(nis), self._p(dof))
+            self._check(rc, "correct_corners_nis_dev")
+            self._order_out(cur)
+            return nis, dof
+        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
+        M = ids.shape[1]
+        left = self._host(left, (B, M, w))
+        right = None if right is None else self._host(right, (B, M, 8))
+        skip = None if skip is None else self._host(skip, (B,), np.uint8)
+        nis, dof = self._nis_outputs(None)
+        rc = self._lib.fbus_ekf_correct_corners_nis(self._h, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
+                                                    self._p(skip), self._p(nis), self._p(dof))
+        self._check(rc, "correct_corners_nis")
+        return nis, dof
+
     def applied(self):
         out = np.empty(self.B, np.uint8)
         self._check(self._lib.fbus_ekf_get_applied(self._h, self._p(out)), "get_applied")

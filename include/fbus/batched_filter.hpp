@@ -130,6 +130,26 @@ public:
                          const uint8_t* skip = nullptr)
     { check(fbus_ekf_correct_corners(h_, M, ids, left, right, geometry, int(mode), skip), "correct_corners"); }
 
+    // NIS and gating of correct() and the two updates above (include/fbus_ekf.h): the gate table indexed by dof (empty: no gate), then the
+    // updates writing nis (B values) and dof (B int32) per filter, each may be null -- host arrays here, device arrays for _nis_dev
+    void set_gate(const std::vector<double>& thresholds)
+    { check(fbus_ekf_set_gate(h_, int(thresholds.size()), thresholds.empty() ? nullptr : thresholds.data()), "set_gate"); }
+    void correct(int M, const int32_t* ids, const Real* pos, const Real* quat, Mode mode, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_nis(h_, M, ids, pos, quat, int(mode), skip, nis, dof), "correct_nis"); }
+    void correct_nis_dev(int M, const int32_t* ids, const Real* pos, const Real* quat, Mode mode, const uint8_t* skip, Real* nis,
+                         int32_t* dof)
+    { check(fbus_ekf_correct_nis_dev(h_, M, ids, pos, quat, int(mode), skip, nis, dof), "correct_nis_dev"); }
+    void correct_pixels(int M, const int32_t* ids, const Real* left, const Real* right, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_pixels_nis(h_, M, ids, left, right, skip, nis, dof), "correct_pixels_nis"); }
+    void correct_pixels_nis_dev(int M, const int32_t* ids, const Real* left, const Real* right, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_pixels_nis_dev(h_, M, ids, left, right, skip, nis, dof), "correct_pixels_nis_dev"); }
+    void correct_corners(int M, const int32_t* ids, const Real* left, const Real* right, int geometry, Mode mode, const uint8_t* skip,
+                         Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_corners_nis(h_, M, ids, left, right, geometry, int(mode), skip, nis, dof), "correct_corners_nis"); }
+    void correct_corners_nis_dev(int M, const int32_t* ids, const Real* left, const Real* right, int geometry, Mode mode,
+                                 const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_corners_nis_dev(h_, M, ids, left, right, geometry, int(mode), skip, nis, dof), "correct_corners_nis_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

@@ -105,6 +105,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  * the caller's compile-time sizeof(fbus_params) and FBUS_ABI_VERSION to fbus_ekf_create_checked, which refuses a
  * mismatch with FBUS_ERR_ABI.  (Bindings that cannot use the macro -- ctypes, loadlibrary -- call
  * fbus_ekf_abi_version() / fbus_params_size() once after loading and compare; the Python mirror does.)
+ *   8  fbus_ekf_set_gate, fbus_ekf_correct_nis[_dev], fbus_ekf_correct_pixels_nis[_dev], fbus_ekf_correct_corners_nis[_dev]
+ *      (struct unchanged)
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -112,7 +114,7 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *   3  round 3: FBUS_ERR_ABI, create_checked, team kernels (fbus_ekf_set_team), fbus_ekf_gather
  *   2  round 2: r_pix in fbus_params, set_stream(NULL) = legacy default stream
  *   1  round 1 */
-#define FBUS_ABI_VERSION 7
+#define FBUS_ABI_VERSION 8
 int fbus_ekf_abi_version(void);
 size_t fbus_params_size(void);
 
@@ -465,6 +467,53 @@ int fbus_ekf_correct_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void*
                             const uint8_t* skip);
 int fbus_ekf_correct_pixels_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
                                 const uint8_t* skip);
+
+/* ---- NIS output and chi-square gating of the measurement updates ---------------------------------------------------
+ * fbus_ekf_correct (the pose rows), fbus_ekf_correct_pixels and fbus_ekf_correct_corners with, per filter, the normalised innovation squared of the rows the update applies, evaluated at the prior,
+ *     nis = r' S^-1 r,   S = H P H' + R      (the matrix MeasureUpdate.m:84 inverts; filter.cpp:709-712 solves with LDLT)
+ * and its dof = the number of rows that carry a residual:
+ *   pixel rows   2 per projection the fold gives non-zero weight (in front of the port and inside its field of view, marker in the
+ *                map): at most 8 per marker for the left camera, 16 for stereo;
+ *   corner rows  3 per corner of each used marker (12 per marker; nearest mode: the chosen marker only);
+ *   pose rows    3 per used marker in the Matlab dialect (its quaternion residual is zeroed, MeasureUpdate.m:88: those rows enter S
+ *                but carry no residual), 7 in the C++ dialect; nearest mode: the chosen marker only.
+ * A filter that is skipped or has no usable marker reports nis = 0, dof = 0 and is left untouched, as by the twin.  No S is formed:
+ * with Lam = H_J' R^-1 H_J, b = H_J' R^-1 r (the 6 x 6 fold the update already builds) and m = (I + P_JJ Lam)^-T b,
+ *     nis = sum res^2 / r - b' P_JJ m          (S^-1 r = R^-1 (r - H dx), dx_J = P_JJ m), in double for both record types;
+ * the pose rows:  nis = sum w res^2 - b' (P_JJ^-1 + Lam)^-1 b, through P_JJ = C C' and the Cholesky factor of I + C' Lam C.
+ * GATE: fbus_ekf_set_gate stores a table thr[0 .. n-1] indexed by dof.  With a table, a filter whose update would run is left
+ * untouched when nis > thr[dof]: its record stays bit-identical (the C++ dialect's previous-marker id included), applied = 0, and
+ * nis / dof are still reported.  The decision is made after the 6 x 6 stage, in front of the first store.  +inf entries never
+ * reject; NaN or negative entries are refused (FBUS_ERR_INVALID, table unchanged), as are n > FBUS_GATE_MAX_DOF + 1 entries.
+ * n = 0 or thresholds = NULL: no gate.  A call whose largest possible dof (M x 8 x cameras; corners: 12, or 12 M stacked; pose: 3 / 7,
+ * or 3 M / 7 M stacked) has no
+ * entry (>= n) fails with FBUS_ERR_INVALID before anything is launched.  set_gate copies the table into handle-owned device
+ * memory in order on the handle's stream and waits for the copy; it is refused between graph_begin and graph_end; a captured
+ * _nis_dev call reads the table that is current when the graph is replayed (entries past the current n read as +inf).
+ * The existing entry points ignore the table.
+ * nis: B values in the handle's dtype, dof: B int32; either may be NULL; host pointers for the host forms, device pointers for
+ * _dev.  Arguments, checks and alignment rules are those of each twin.  With no table, records and applied equal the twin's bit for
+ * bit on the route the twin takes for one wave per tile.  The pixel / corner forms always run that route; on small launches
+ * (fewer tiles than half the chip's SIMDs, unless fbus_ekf_set_team(h, ., 1)) the twins divide the markers among 2-4 waves per tile
+ * and add their sums in another order, and the two agree to rounding (the single-step gate).  The pose form takes the twin's
+ * kernel choice except the fp32 row-split kernel of stacked, simple-form launches of more than one wave per SIMD (> 65 536 filters
+ * on a 256-CU part), where it keeps the one-wave kernel: a different pass order, equal to rounding.  One pose route is not bit-identical
+ * even so: fp64 records, C++ dialect, stacked mode -- the covariance is, the nominal state differs from the twin's in the last bits
+ * (measured <= 2e-15 absolute; the single-step gate holds). */
+#define FBUS_GATE_MAX_DOF 256      /* largest dof: 16 markers x 4 corners x 2 cameras x 2 rows; a full table has 257 entries */
+int fbus_ekf_set_gate(fbus_ekf_t h, int n, const double* thresholds /* host, n entries; n = 0 or NULL: no gate */);
+int fbus_ekf_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
+                         const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
+                             const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
+                                const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_pixels_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
+                                    const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                                 int mode, const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
+                                     int mode, const uint8_t* skip, void* nis, int32_t* dof);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
