@@ -1,14 +1,15 @@
 #!/usr/bin/env python3
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
-The library is 37 translation units compiled in parallel and linked into one shared object:
+The library is 49 translation units compiled in parallel and linked into one shared object:
   fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose)
-  kernels_tu.hip x 36                   one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
+  kernels_tu.hip x 48                   one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
                                         float: predict / correct / frame / frames / team / meas / fmeas / msplit / framest / fmeast
-                                        / measnis / correctnis (12 x 2 = 24; framest / fmeast: the windows with per-frame trajectory rows,
-                                        measnis / correctnis: the pixel / corner and the pose updates with the NIS output and the gate),
-                                        double: predict / correct / frame / meas / measnis / correctnis (6 x 2 = 12; len(units()) == 37
-                                        with fbus_ekf.hip)
+                                        / measnis / correctnis / prednz / measnz / correctnz (15 x 2 = 30; framest / fmeast: the windows
+                                        with per-frame trajectory rows, measnis / correctnis: the pixel / corner and the pose updates with
+                                        the NIS output and the gate, prednz / measnz / correctnz: predict and the NIS updates with
+                                        per-filter noise), double: predict / correct / frame / meas / measnis / correctnis / prednz /
+                                        measnz / correctnz (9 x 2 = 18; len(units()) == 49 with fbus_ekf.hip)
 Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.
   python build.py [--force] [--only f32_18_correct,...] [--jobs N]
 FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds (A/B of differently built kernels via FBUS_EKF_LIB).
@@ -25,7 +26,8 @@ HEADERS = [os.path.join(CSRC, h) for h in ("ekf_kernels.hpp", "ekf_device.hpp", 
 OUT = os.environ.get("FBUS_OUT") or os.path.join(HERE, "lib", "libfbus_ekf.so")   # FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds
 OBJDIR = os.environ.get("FBUS_OBJDIR") or os.path.join(os.path.dirname(OUT), "obj" if not os.environ.get("FBUS_OUT") else
                                                        "obj_" + os.path.splitext(os.path.basename(OUT))[0])
-FAMILIES = {"predict": 1, "correct": 2, "frame": 3, "frames": 5, "team": 6, "meas": 7, "fmeas": 8, "msplit": 9, "framest": 10, "fmeast": 11, "measnis": 12, "correctnis": 13}
+FAMILIES = {"predict": 1, "correct": 2, "frame": 3, "frames": 5, "team": 6, "meas": 7, "fmeas": 8, "msplit": 9, "framest": 10, "fmeast": 11, "measnis": 12, "correctnis": 13,
+            "prednz": 14, "measnz": 15, "correctnz": 16}
 # Per-family scheduler choice (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
 # max-ILP strategy of the AMDGPU machine scheduler shortens the per-call kernels, where one wave per SIMD has nothing
 # but its own independent instructions to cover dependent-issue stalls (predict 13.4 -> 13.05 us, stacked correct
@@ -39,12 +41,15 @@ FAMILY_FLAGS = {"predict": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-
                 # the trajectory windows (families 10 / 11) are built with the flags of the windows they extend
                 "framest": os.environ.get("FBUS_FRAMES_FLAGS", "").split(), "fmeast": os.environ.get("FBUS_FMEAS_FLAGS", "").split(),
                 # the NIS updates (families 12 / 13) with the flags of the updates they extend, both record types
-                "measnis": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnis": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+                "measnis": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnis": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+                # the per-filter noise kernels (families 14-16) with the flags of the kernels they extend, both record types
+                "prednz": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
+                "measnz": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnz": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 # fp64 units.  meas (correct_pixels2 / correct_corners2 <double>, 512 registers + scratch): the max-memory-clause strategy leaves them
 # 28-136 bytes of scratch instead of 136-340 and is 4-11 % faster (profiles/r05_f64_sched.txt); FBUS_F64_FLAGS_<FAMILY> overrides
 F64_FAMILY_FLAGS = {fam: os.environ.get("FBUS_F64_FLAGS_" + fam.upper(),
-                                        "-mllvm -amdgpu-sched-strategy=max-memory-clause" if fam in ("meas", "measnis") else "").split()
-                    for fam in ("predict", "correct", "frame", "meas", "measnis", "correctnis")}
+                                        "-mllvm -amdgpu-sched-strategy=max-memory-clause" if fam in ("meas", "measnis", "measnz") else "").split()
+                    for fam in ("predict", "correct", "frame", "meas", "measnis", "correctnis", "prednz", "measnz", "correctnz")}
 TYPES = {"f32": "float", "f64": "double"}
 
 

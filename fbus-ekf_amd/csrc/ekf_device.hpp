@@ -464,8 +464,8 @@ __device__ __forceinline__ void cov_stage_p(T* P, const PredictCoef<T>& k)
 }
 
 // rows v:  E_v (row part and the symmetric v,v block), then the theta-column of rows v, + Q on the v diagonal
-template <typename T, int N, int PK = FBUS_X_PACK>
-__device__ __forceinline__ void cov_stage_v(T* P, const PredictCoef<T>& k, const T* qd)
+template <typename T, int N, int PK = FBUS_X_PACK, typename QD = const T*>
+__device__ __forceinline__ void cov_stage_v(T* P, const PredictCoef<T>& k, QD qd)
 {
     constexpr bool G = (N == 18);
     constexpr int NC = N - 6;                       // columns theta .. end
@@ -669,8 +669,8 @@ __host__ __device__ constexpr bool th_pair_cols(int c)
         && is_pair<N>(6, c) && is_pair<N>(7, c) && is_pair<N>(8, c);
 }
 // rows theta:  E_theta on the remaining columns, + Fi Q Fi' (not scaled by dt; ImuUpdate.m:70-73 ; filter.cpp:609-610)
-template <typename T, int N, int PK = FBUS_X_PACK>
-__device__ __forceinline__ void cov_stage_th(T* P, const PredictCoef<T>& k, const T* qd)
+template <typename T, int N, int PK = FBUS_X_PACK, typename QD = const T*>
+__device__ __forceinline__ void cov_stage_th(T* P, const PredictCoef<T>& k, QD qd)
 {
     const T dt = k.dt;
     const T (&Th)[9] = k.Th;
@@ -913,8 +913,8 @@ __device__ __forceinline__ void predict_nominal(T* nom, const T* accel, const T*
 }
 
 // One ImuUpdate with everything resident: nom = the 28 nominal + rotation elements, P = packed covariance.
-template <typename T, int N, int DIALECT, int PK = FBUS_X_PACK>
-__device__ __forceinline__ void predict_step(T* nom, T* P, const T* accel, const T* gyro, T dt, const T* qd)
+template <typename T, int N, int DIALECT, int PK = FBUS_X_PACK, typename QD = const T*>
+__device__ __forceinline__ void predict_step(T* nom, T* P, const T* accel, const T* gyro, T dt, QD qd)
 {
     PredictCoef<T> k;
     predict_nominal<T, N, DIALECT, PK>(nom, accel, gyro, dt, k);
@@ -1215,6 +1215,54 @@ __device__ __forceinline__ void nis_write(const NisOut<T>& o, int b, double nis,
 {
     if (o.nis) o.nis[b] = (T)nis;
     if (o.dof) o.dof[b] = dof;
+}
+
+// ---- per-filter noise (fbus_ekf_set_noise): a trailing kernel parameter NoiseIn, behind the NisOut of the update kernels (the tabled routes
+// run the plain updates through the NIS kernels with null outputs) and alone behind predict_kernel's arguments.  tab: the handle's table
+// as fp64 fields [FBUS_NOISE_COLS][B] (q_v q_theta q_ba q_bg r_pos r_quat r_pix); lane b reads field c at tab[c * B + b], one
+// coalesced 512-byte access per wave.  (T) of the double equals the host's (T)prm field: the twin's arithmetic on the lane's own value.
+struct NoiseIn { const double* tab; int B; };
+enum { NOISE_QV = 0, NOISE_QTH = 1, NOISE_QBA = 2, NOISE_QBG = 3, NOISE_RPOS = 4, NOISE_RQUAT = 5, NOISE_RPIX = 6 };
+template <typename T> __device__ __forceinline__ NisOut<T> nis_out(const NisOut<T>& o, const NoiseIn&) { return o; }
+template <typename... NO> constexpr bool has_noise() { return (std::is_same<NO, NoiseIn>::value || ... || false); }
+__device__ __forceinline__ NoiseIn noise_in(const NoiseIn& n) { return n; }
+template <typename T> __device__ __forceinline__ NoiseIn noise_in(const NisOut<T>&, const NoiseIn& n) { return n; }
+// field c of filter b (b < B: the caller clamps the lanes past the batch)
+__device__ __forceinline__ double noise_ld(const NoiseIn& n, int c, int b) { return n.tab[(size_t)c * (size_t)n.B + (size_t)b]; }
+// the update's noise: the kernel argument without a table, the lane's field with one
+template <typename... NO>
+__device__ __forceinline__ double noise_col(double uniform, int c, int b, const NO&... no)
+{
+    if constexpr (has_noise<NO...>()) return noise_ld(noise_in(no...), c, b);
+    else return uniform;
+}
+template <typename T, typename... NZ>
+__device__ __forceinline__ void noise_q(DevConst<T>& dc, int b, const NZ&... nz)
+{
+    const NoiseIn n = noise_in(nz...);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) dc.qd[i] = (T)noise_ld(n, NOISE_QV + i, b);
+}
+// q of one lane parked in LDS and read there at each use (qd[i], i = 0..3; the parked predict_n, whose 256 registers have no room for four
+// values held across the K-step loop).  q: the block's [4][64] array, lane = this lane's column; the empty asm on the index makes every use
+// a read of its own (hoisted out of the loop, the four values would be live across it again)
+template <typename T>
+struct LdsQ {
+    T* q;
+    int lane;
+    __device__ __forceinline__ T operator[](int i) const
+    {
+        int o = i * 64 + lane;
+        asm volatile("" : "+v"(o));
+        return q[o];
+    }
+};
+template <typename T, typename... NO>
+__device__ __forceinline__ void noise_pose(DevConst<T>& dc, int b, const NO&... no)
+{
+    const NoiseIn n = noise_in(no...);
+    dc.r_pos = (T)noise_ld(n, NOISE_RPOS, b);
+    dc.r_quat = (T)noise_ld(n, NOISE_RQUAT, b);
 }
 
 // NIS of the pose rows at the prior: sumw - b' (P_JJ^-1 + Lam)^-1 b  (sumw = sum w res^2; Lam, b of the fold), in double.

@@ -414,9 +414,9 @@ struct StepPark {
 
 // K ImuUpdates with the record resident in registers (predict_n, fused frame)
 struct NoMidHook { __device__ __forceinline__ void operator()() const {} };
-template <typename T, int N, int DIALECT, typename MID = NoMidHook, typename PARK = NoStepPark, int PK = FBUS_X_PACK>
+template <typename T, int N, int DIALECT, typename MID = NoMidHook, typename PARK = NoStepPark, int PK = FBUS_X_PACK, typename QD = const T*>
 __device__ __forceinline__ void predict_steps(T* nom, T* P, int K, const T* accel, const T* gyro, const T* dt, int dt_stride,
-                                              int B, int b, const T* qd, const MID& mid_last = MID(), const PARK& park = PARK())
+                                              int B, int b, QD qd, const MID& mid_last = MID(), const PARK& park = PARK())
 {
 #if FBUS_X_IMU_PREFETCH
     // The sample of step k + 1 is requested as soon as step k's kinematics have consumed sample k, i.e. ~700 VALU
@@ -504,10 +504,12 @@ constexpr int PARK_NOM_CHUNKS = 4;
 #define FBUS_X_PREDICT_TWO 0
 #endif
 template <typename T> constexpr int park_nom_chunks() { return sizeof(T) == 8 ? FBUS_X_PARK_NOM_F64 : PARK_NOM_CHUNKS; }
-template <typename T, int N, int DIALECT, bool MULTI, int LD = AUX_NT, int ST = FBUS_X_PREDICT_ST, bool PARK = false>
+// NZ = NoiseIn (fbus_ekf_set_noise; kernels_tu.hip family 14, every form the launcher picks): this lane's q_v q_theta q_ba q_bg in place of
+// the handle's, requested with the prologue (ahead of the record stream) and used where dc.qd is
+template <typename T, int N, int DIALECT, bool MULTI, int LD = AUX_NT, int ST = FBUS_X_PREDICT_ST, bool PARK = false, typename... NZ>
 __global__ void __launch_bounds__(BLOCK, (sizeof(T) == 4 && (PARK || (!MULTI && FBUS_X_PREDICT_TWO))) ? 2 : 1)
 predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, const T* __restrict__ gyro,
-               const T* __restrict__ dt, int dt_stride, DevConst<T> dc)
+               const T* __restrict__ dt, int dt_stride, DevConst<T> dc, NZ... nz)
 {
     // (round 5, measured and NOT kept: the tiles beyond the last whole round of waves as sub-tile waves of 16 / 32 active lanes spread
     // over all CUs -- no gain at any size, one extra tile costs +3.4 us however it is cut: profiles/r05_tail_split.txt, commit b55c4d4)
@@ -515,14 +517,25 @@ predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, 
     if (b >= B) return;
     using RC = Rec<T, N>;
     constexpr int EPC = RC::EPC, CN = RC::CH_NOM;
+    constexpr bool NOISE = sizeof...(NZ) > 0;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
     T nom[Lay<N>::NNOM], P[RC::NCOVP];
+    // (NOISE: this lane's q written into the by-value constants -- the instantiations without a table stay as they were)
     if (MULTI) {
+        if constexpr (NOISE && !PARK) noise_q<T>(dc, b, nz...);
         load_chunks<T, N, 0, CN, AUX_NT>(rs, my_lane(), nom);
         load_chunks<T, N, CN, RC::NCH, AUX_NT>(rs, my_lane(), P);
         if constexpr (PARK) {
             using Park = StepPark<T, N, park_nom_chunks<T>()>;
             __shared__ u32x4 park_mem[Park::NCHUNK * BLOCK];
+            if constexpr (NOISE) {      // (q parked in LDS, read at each use: LdsQ)
+                __shared__ T q_mem[4 * BLOCK];
+                const NoiseIn n = noise_in(nz...);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) q_mem[i * BLOCK + threadIdx.x] = (T)noise_ld(n, NOISE_QV + i, b);
+                predict_steps<T, N, DIALECT, NoMidHook, Park>(nom, P, K, accel, gyro, dt, dt_stride, B, b,
+                                                              LdsQ<T>{ q_mem, (int)threadIdx.x }, NoMidHook(), Park{ park_mem + threadIdx.x });
+            } else
             predict_steps<T, N, DIALECT, NoMidHook, Park>(nom, P, K, accel, gyro, dt, dt_stride, B, b, dc.qd, NoMidHook(),
                                                           Park{ park_mem + threadIdx.x });
         } else
@@ -544,6 +557,7 @@ predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, 
         const T w[3] = { ld_once(gyro + o), ld_once(gyro + o + 1), ld_once(gyro + o + 2) };
         constexpr int LDP = LD, STP = ST;
         const T h = dt_stride ? ld_once(dt + b) : dt[0];
+        if constexpr (NOISE) noise_q<T>(dc, b, nz...);
         load_chunks<T, N, 0, CN, LDP>(rs, my_lane(), nom);
         load_chunks<T, N, C_DG0, C_DG1, LDP>(rs, my_lane(), P + (C_DG0 - CN) * EPC);
         load_chunks<T, N, CN, C_PV_IN, LDP>(rs, my_lane(), P);
@@ -599,6 +613,9 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     const int b = blockIdx.x * BLOCK + threadIdx.x;
     const bool live = b < B && !(skip && skip[b < B ? b : 0]);
     const int bc = live ? b : 0;
+    // NO = (NisOut<T>, NoiseIn) (fbus_ekf_set_noise; kernels_tu.hip family 16): this lane's r_pos / r_quat in place of the handle's, requested
+    // in front of the record stream (written into the by-value constants: the instantiations without a table stay as they were)
+    if constexpr (has_noise<NO...>()) noise_pose<T>(dc, b < B ? b : B - 1, no...);
     const int* my_ids = ids + (size_t)bc * M;
     const T* my_pos = pos + (size_t)bc * M * 3;
     const T* my_quat = quat + (size_t)bc * M * 4;

@@ -115,6 +115,28 @@ void launch_corners2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids,
                            const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof,
                            const double* thr);
 
+// ---- per-filter noise (fbus_ekf_set_noise): the one-wave forms with a trailing NoiseIn, noise = the handle's table [FBUS_NOISE_COLS][B] ----
+// the kernel choice of launch_predict_k (kernels_tu.hip family 14: predict_kernel with NoiseIn)
+template <typename T, int N, int D>
+void launch_predict_noise_k(hipStream_t s, T* recs, int B, int K, int policy, const T* accel, const T* gyro, const T* dt,
+                            int dt_stride, const DevConst<T>& dc, const LaunchPolicy& lp, const double* noise);
+// the kernel choice of launch_correct_nis_k (family 16: correct_kernel with NisOut and NoiseIn); the plain update passes null nis / dof and a
+// table of +inf for thr
+template <typename T, int N, int D>
+void launch_correct_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                            const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                            const double* thr, const double* noise);
+// the kernel choice of launch_pixels2_nis_k / launch_corners2_nis_k (family 15: NisOut and NoiseIn); the plain updates pass null nis / dof / thr
+template <typename T, int N, int D>
+void launch_pixels2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
+                            const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                            const double* thr, const double* noise);
+template <typename T, int N, int D>
+void launch_corners2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                             double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                             const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
+                             const double* noise);
+
 // ---- one camera frame with the north star's MeasureUpdate in one launch (ekf_meas.hpp::frame_meas_kernel; fp32) -----------------
 // kind: corner pixels (geometry / mode ignored; right == nullptr: left camera) or stereo corners (geometry, mode as correct_corners)
 enum { MEAS_PIXELS = 0, MEAS_CORNERS = 1 };

@@ -1482,6 +1482,8 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
     const int b = (int)(tile * 64u + lane);
     const bool live = b < B && !(skip && skip[b < B ? b : 0]);
     const int bc = b < B ? b : (int)(tile * 64u);
+    // NO = (NisOut<T>, NoiseIn) (fbus_ekf_set_noise; kernels_tu.hip family 15): this lane's r_pix, requested in front of the record stream
+    const double rpix = noise_col(r_pix, NOISE_RPIX, bc, no...);
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, tile);
     __shared__ MeasLDS tbl;
     // the roles' partial sums; fp64 records: behind them (role 0 has added them up by then) G waits here while the block outside J is updated
@@ -1608,13 +1610,13 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
         acc.to_imu_frame(mc.adjL);
         double RM[9];
         PixAcc::camera_rotation(Rd, mc.McL, RM);
-        if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, RM, 1.0 / r_pix, -1, gpark_mem + lane) ? 1 : 0; return; }
-        meas_update_tail<T, N>(rs, lane, acc, RM, 1.0 / r_pix, -1, gpark_mem + lane);
+        if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
+        meas_update_tail<T, N>(rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane);
         applied[b] = 1;
         return;
     }
-    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / r_pix, -1, gpark_mem + lane) ? 1 : 0; return; }
-    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / r_pix, -1, gpark_mem + lane);
+    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
+    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane);
     applied[b] = 1;
 }
 
@@ -1643,6 +1645,7 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
     const int b = (int)(tile * 64u + lane);
     const bool live = b < B && !(skip && skip[b < B ? b : 0]);
     const int bc = b < B ? b : (int)(tile * 64u);
+    const double rpos = noise_col(r_pos, NOISE_RPOS, bc, no...);          // (NoiseIn: see correct_pixels2_kernel)
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, tile);
     __shared__ MeasLDS tbl;
     // the roles' partial sums; fp64 records: behind them (role 0 has added them up by then) G waits here while the block outside J is updated
@@ -1797,8 +1800,8 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
         return;
     }
     acc.expand_const(mc.NI);
-    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / r_pos, new_prev, gpark_mem + lane) ? 1 : 0; return; }
-    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / r_pos, new_prev, gpark_mem + lane);
+    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane) ? 1 : 0; return; }
+    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane);
     applied[b] = 1;
 }
 

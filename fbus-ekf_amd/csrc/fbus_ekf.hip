@@ -153,6 +153,11 @@ struct fbus_ekf {
     // at create and never moved, so a captured _nis_dev call reads the table that is current at its replay
     double* d_gate = nullptr;
     int gate_n = 0;
+    // per-filter noise (fbus_ekf_set_noise): the table as fields [FBUS_NOISE_COLS][B] in double, followed by FBUS_GATE_MAX_DOF + 1 entries
+    // of +inf (the "no gate" table of the plain pose update, which runs the NIS kernel on the tabled route); allocated at the first
+    // set_noise and never moved, so a captured call reads the values current at its replay.  noise_on: the tabled routes are taken
+    double* d_noise = nullptr;
+    bool noise_on = false;
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
@@ -287,7 +292,7 @@ int quarter_chip(const fbus_ekf* h) { return h->lp.simds / 4; }
 int half_chip(const fbus_ekf* h) { return h->lp.simds / 2; }
 int team_roles_predict(const fbus_ekf* h, int K)
 {
-    if (h->dtype != 32 || h->team_predict == 1) return 1;
+    if (h->dtype != 32 || h->team_predict == 1 || h->noise_on) return 1;      // (a noise table: the one-wave forms only)
     if (h->team_predict >= 2) return K > 1 ? 4 : (h->team_predict > 4 ? 4 : h->team_predict);
     const int tiles = policy_tiles(h);
     if (K > 1) return tiles <= half_chip(h) ? 4 : 1;
@@ -298,7 +303,7 @@ int team_roles_predict(const fbus_ekf* h, int K)
 // 0 = four up to a quarter of the chip, two up to half.  Both record types.
 int team_roles_pixels(const fbus_ekf* h, int M)
 {
-    if (M < 2 || h->team_correct == 1) return 1;
+    if (M < 2 || h->team_correct == 1 || h->noise_on) return 1;
     if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
     const int tiles = policy_tiles(h);
     return tiles <= quarter_chip(h) ? 4 : (tiles <= half_chip(h) ? 2 : 1);
@@ -310,7 +315,7 @@ int team_roles_pixels(const fbus_ekf* h, int M)
 int meas_split_roles(const fbus_ekf* h, int M)
 {
     const double* n = h->prm.port_normal;
-    if (h->dtype != 32 || M < 2 || h->team_correct == 1 || h->meas_split == 0) return 0;
+    if (h->dtype != 32 || M < 2 || h->team_correct == 1 || h->meas_split == 0 || h->noise_on) return 0;
     if (!(n[0] == 0.0 && n[1] == 0.0 && n[2] == 1.0)) return 0;
     if (h->meas_split > 0) return h->meas_split;
     if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
@@ -323,7 +328,7 @@ int meas_split_roles(const fbus_ekf* h, int M)
 // 32 768 filters, 0.8x at 40 960).
 bool team_frames(const fbus_ekf* h, int mode)
 {
-    if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH) return false;
+    if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH || h->noise_on) return false;
     if (mode != MODE_NEAREST && mode != MODE_STACKED) return false;
     if (h->team_frame == 1 || (h->team_frame == 0 && h->team_predict == 1)) return false;
     if (h->team_frame == 2 || h->team_predict >= 2) return true;
@@ -367,7 +372,10 @@ int launch_predict_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, c
             launch_predict_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, roles, policy, (const T*)accel, (const T*)gyro,
                                            (const T*)dt, dt_per_filter ? 1 : 0, make_dc<T>(h));
     }
-    if (roles <= 1 || sizeof(T) != 4)
+    if (h->noise_on)                // (roles == 1) the same kernel choice with this filter's q (kernels_tu.hip family 14)
+        launch_predict_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                        dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp, h->d_noise);
+    else if (roles <= 1 || sizeof(T) != 4)
         launch_predict_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
                                   dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp);
     timing_end(h, ev);
@@ -381,6 +389,11 @@ int launch_correct_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, c
 {
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;   // false: written through (sc1), the next predict streams them like any other
+    if (h->noise_on)                            // the NIS kernel with no outputs and the +inf table: this filter's r_pos / r_quat
+        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
+                                        nullptr, nullptr, h->d_noise + (size_t)FBUS_NOISE_COLS * h->B, h->d_noise);
+    else
     launch_correct_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                   h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp);
     timing_end(h, ev);
@@ -419,7 +432,8 @@ int launch_frame_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, con
                    const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
     const bool f64_fused = sizeof(T) == 8 && mode == MODE_STACKED && h->prm.cov_form != FBUS_COV_JOSEPH && K > 0 && K <= 255;
-    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED)) {
+    // (a noise table: no fused kernel reads it -- predict_n + the per-call update, which do)
+    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || h->noise_on) {
         // no fused kernel for fp64 outside (stacked, simple) and none for the Joseph form with the reference mode's 7 row-by-row
         // updates (it spilled): those frames are one predict_n launch and one correct launch -- the same arithmetic
         int rc = FBUS_OK;
@@ -747,6 +761,11 @@ int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void
     // triangulation and fold in double, non-cancelling update (ekf_meas.hpp); records written through (sc1) as correct_kernel's
     h->records_warm = h->warm_after_correct;
     const int roles = mode == MODE_STACKED ? team_roles_pixels(h, M) : 1;
+    if (h->noise_on)                    // the NIS kernel with no outputs and no gate: this filter's r_pos (kernels_tu.hip family 15)
+        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
+                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), nullptr, nullptr, nullptr, h->d_noise);
+    else
     launch_corners2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
                                roles, h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
                                h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h));
@@ -770,7 +789,11 @@ int launch_correct_pixels_t(fbus_ekf_t h, int M, const int32_t* ids, const void*
             launch_pixels_split_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, split,
                                            h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
     }
-    if (split == 0 || sizeof(T) != 4) {
+    if (h->noise_on) {                  // (split == 0) the NIS kernel with no outputs and no gate: this filter's r_pix (family 15)
+        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
+                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), nullptr,
+                                        nullptr, nullptr, h->d_noise);
+    } else if (split == 0 || sizeof(T) != 4) {
         const int roles = team_roles_pixels(h, M);
         launch_pixels2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, roles,
                                   h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
@@ -795,7 +818,7 @@ template <typename T>
 bool frame_meas_resident(const fbus_ekf* h, int kind, int M, int mode)
 {
     const int roles = (kind == MEAS_CORNERS && mode != MODE_STACKED) ? 1 : team_roles_pixels(h, M);
-    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas;
+    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas && !h->noise_on;
 }
 template <typename T, int N, int D>
 int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
@@ -876,6 +899,11 @@ int launch_correct_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* po
 {
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;
+    if (h->noise_on)
+        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
+                                        (T*)nis, (int*)dof, h->d_gate, h->d_noise);
+    else
     launch_correct_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                   h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
                                   (T*)nis, (int*)dof, h->d_gate);
@@ -898,6 +926,11 @@ int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const v
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
+    if (h->noise_on)
+        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
+                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
+                                        (int*)dof, h->d_gate, h->d_noise);
+    else
     launch_pixels2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, h->prm.marker_size,
                                   h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis, (int*)dof,
                                   h->d_gate);
@@ -918,6 +951,11 @@ int launch_correct_corners_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const 
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_corners_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
+    if (h->noise_on)
+        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
+                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, h->d_gate, h->d_noise);
+    else
     launch_corners2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
                                    h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied,
                                    h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, h->d_gate);
@@ -1271,6 +1309,7 @@ int fbus_ekf_destroy(fbus_ekf_t h)
     if (h->d_mkc) (void)hipFree(h->d_mkc);
     if (h->d_id2slot) (void)hipFree(h->d_id2slot);
     if (h->d_gate) (void)hipFree(h->d_gate);
+    if (h->d_noise) (void)hipFree(h->d_noise);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     (void)fbus_ekf_comm_destroy(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1850,6 +1889,94 @@ int fbus_ekf_set_gate(fbus_ekf_t h, int n, const double* thresholds)
     return FBUS_OK;
 }
 
+// ---- per-filter noise (fbus_ekf_set_noise*, include/fbus_ekf.h) ----
+namespace {
+// B x FBUS_NOISE_COLS row-major -> fields [FBUS_NOISE_COLS][B] (fbus_ekf_set_noise_dev; one thread per entry, reads coalesced)
+__global__ void noise_fields_kernel(const double* __restrict__ rows, double* __restrict__ fields, int B)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * FBUS_NOISE_COLS) return;
+    const size_t b = i / FBUS_NOISE_COLS, c = i % FBUS_NOISE_COLS;
+    fields[c * (size_t)B + b] = rows[i];
+}
+const char* const kNoiseCols[FBUS_NOISE_COLS] = { "q_v", "q_theta", "q_ba", "q_bg", "r_pos", "r_quat", "r_pix" };
+// the table buffer, allocated once (the +inf gate table behind the fields written with it)
+int ensure_noise(fbus_ekf_t h)
+{
+    if (h->d_noise) return FBUS_OK;
+    const size_t nf = (size_t)FBUS_NOISE_COLS * h->B;
+    double* d = nullptr;
+    if (hipMalloc((void**)&d, (nf + FBUS_GATE_MAX_DOF + 1) * sizeof(double)) != hipSuccess)
+        return fail(h, FBUS_ERR_NOMEM, "fbus_ekf_set_noise: device allocation");
+    const std::vector<double> none(FBUS_GATE_MAX_DOF + 1, std::numeric_limits<double>::infinity());
+    if (hipMemcpyAsync(d + nf, none.data(), none.size() * sizeof(double), hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+        (void)hipFree(d);
+        return fail(h, FBUS_ERR_HIP, "fbus_ekf_set_noise: copy of the +inf gate table");
+    }
+    h->d_noise = d;
+    return FBUS_OK;
+}
+}  // namespace
+
+int fbus_ekf_set_noise(fbus_ekf_t h, const double* table)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_noise: not between graph_begin and graph_end");
+    if (!table) { h->noise_on = false; return FBUS_OK; }
+    const size_t B = (size_t)h->B;
+    std::vector<double> fields((size_t)FBUS_NOISE_COLS * B);
+    for (size_t b = 0; b < B; ++b)
+        for (int c = 0; c < FBUS_NOISE_COLS; ++c) {
+            const double v = table[b * FBUS_NOISE_COLS + c];
+            const bool ok = std::isfinite(v) && (c < 4 ? v >= 0.0 : v > 0.0);     // as fbus_params_validate: q >= 0, r > 0
+            if (!ok) {
+                char msg[160];
+                std::snprintf(msg, sizeof msg, "fbus_ekf_set_noise: row %zu column %d (%s) = %g: must be finite and %s", b, c,
+                              kNoiseCols[c], v, c < 4 ? ">= 0" : "> 0");
+                return fail(h, FBUS_ERR_INVALID, msg);
+            }
+            fields[(size_t)c * B + b] = v;
+        }
+    int rc = ensure_noise(h);
+    if (rc != FBUS_OK) return rc;
+    HIP_TRY(h, hipMemcpyAsync(h->d_noise, fields.data(), fields.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));       // (fields is a local)
+    h->noise_on = true;
+    return FBUS_OK;
+}
+
+int fbus_ekf_set_noise_dev(fbus_ekf_t h, const double* table)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_noise_dev: not between graph_begin and graph_end");
+    if (!table) { h->noise_on = false; return FBUS_OK; }
+    int rc = ensure_noise(h);
+    if (rc != FBUS_OK) return rc;
+    const size_t n = (size_t)FBUS_NOISE_COLS * h->B;
+    hipLaunchKernelGGL(noise_fields_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, table, h->d_noise, h->B);
+    HIP_TRY(h, hipGetLastError());
+    h->noise_on = true;
+    return FBUS_OK;
+}
+
+int fbus_ekf_get_noise(fbus_ekf_t h, double* table)
+{
+    DeviceGuard guard_(h);
+    if (!h || !table) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_get_noise: not between graph_begin and graph_end");
+    if (!h->noise_on) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_get_noise: no noise table is set");
+    const size_t B = (size_t)h->B;
+    std::vector<double> fields((size_t)FBUS_NOISE_COLS * B);
+    HIP_TRY(h, hipMemcpyAsync(fields.data(), h->d_noise, fields.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b)
+        for (int c = 0; c < FBUS_NOISE_COLS; ++c) table[b * FBUS_NOISE_COLS + c] = fields[(size_t)c * B + b];
+    return FBUS_OK;
+}
+
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                              void* nis, int32_t* dof)
 {
@@ -2104,7 +2231,8 @@ static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const v
         const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_fused_traj_dev");
         if (rc != FBUS_OK) return rc;
     }
-    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED);
+    // (a noise table: frame by frame, through the per-call kernels that read it)
+    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) && !h->noise_on;
     if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
     // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
     // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel

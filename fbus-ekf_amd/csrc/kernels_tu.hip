@@ -13,6 +13,9 @@
 //  11 window of 8's frames with per-frame trajectory rows (frame_meas_kernel with TrajOut; fp32 only)
 //  12 7's updates with the NIS output and the gate (correct_pixels2_kernel / correct_corners2_kernel with NisOut; one wave per tile)
 //  13 2's update with the NIS output and the gate (correct_kernel with NisOut; fp32: never the row-split form)
+//  14 1's kernels with per-filter process noise (predict_kernel with NoiseIn; every form of 1's choice, no team form)
+//  15 12's updates with per-filter r_pix / r_pos (NisOut and NoiseIn; the plain updates of a tabled handle run here with null outputs)
+//  16 13's update with per-filter r_pos / r_quat (NisOut and NoiseIn; likewise)
 // gfx950 only.
 #include <cstdlib>
 #include "ekf_kernels.hpp"
@@ -481,8 +484,116 @@ void launch_correct_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, 
                                                                 const unsigned char*, unsigned char*,                  \
                                                                 const DevConst<FBUS_TU_T>&, const LaunchPolicy&,       \
                                                                 FBUS_TU_T*, int*, const double*);
+#elif FBUS_TU_FAMILY == 14
+template <typename T, int N> constexpr bool park_noise() { return N == 15; }      // (see launch_predict_noise_k)
+// family 1's kernel choice with NoiseIn (per-filter q); no team forms
+template <typename T, int N, int D>
+void launch_predict_noise_k(hipStream_t s, T* recs, int B, int K, int policy, const T* accel, const T* gyro, const T* dt,
+                            int dt_stride, const DevConst<T>& dc, const LaunchPolicy& lp, const double* noise)
+{
+    const int grid = (B + BLOCK - 1) / BLOCK;
+    const NoiseIn nz{ noise, B };
+    if (K == 1) {
+#define FBUS_LAUNCH_PREDICTZ(LD, ST)                                                                                    \
+    hipLaunchKernelGGL((predict_kernel<T, N, D, false, LD, ST, false, NoiseIn>), dim3(grid), dim3(BLOCK), 0, s, recs, B, K, accel, gyro, \
+                       dt, dt_stride, dc, nz)
+        if (policy == 2) FBUS_LAUNCH_PREDICTZ(FBUS_X_PREDICT_LD_BIG, FBUS_X_PREDICT_ST_BIG);
+        else if (policy == 1) FBUS_LAUNCH_PREDICTZ(FBUS_X_PREDICT_LD_WARM, AUX_NT);
+        else FBUS_LAUNCH_PREDICTZ(FBUS_X_PREDICT_LD, FBUS_X_PREDICT_ST);
+#undef FBUS_LAUNCH_PREDICTZ
+    } else if constexpr (sizeof(T) == 8) {
+        hipLaunchKernelGGL((predict_kernel<T, N, D, true, AUX_NT, FBUS_X_PREDICT_ST, true, NoiseIn>), dim3(grid), dim3(BLOCK), 0, s, recs,
+                           B, K, accel, gyro, dt, dt_stride, dc, nz);
+    } else if (park_noise<T, N>() && lp.two_wave(B)) {
+        // (fp32 N = 18: the parked loop sits at 256 registers already and spilled 12-36 bytes with the lane's q, in registers or read from
+        // LDS at each use -- a table runs that batch on the one-wave loop, 256 + 87 registers and no scratch, one wave per SIMD)
+        if constexpr (park_noise<T, N>())
+            hipLaunchKernelGGL((predict_kernel<T, N, D, true, AUX_NT, FBUS_X_PREDICT_ST, true, NoiseIn>), dim3(grid), dim3(BLOCK), 0, s,
+                               recs, B, K, accel, gyro, dt, dt_stride, dc, nz);
+    } else {
+        hipLaunchKernelGGL((predict_kernel<T, N, D, true, AUX_NT, FBUS_X_PREDICT_ST, false, NoiseIn>), dim3(grid), dim3(BLOCK), 0, s, recs,
+                           B, K, accel, gyro, dt, dt_stride, dc, nz);
+    }
+}
+#define FBUS_INST(D)                                                                                                  \
+    template void launch_predict_noise_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, int, const FBUS_TU_T*, \
+                                                                  const FBUS_TU_T*, const FBUS_TU_T*, int,            \
+                                                                  const DevConst<FBUS_TU_T>&, const LaunchPolicy&, const double*);
+#elif FBUS_TU_FAMILY == 15
+// family 12's kernel choice with NoiseIn (per-filter r_pix / r_pos): one wave per tile
+template <typename T, int N, int D>
+void launch_pixels2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
+                            const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                            const double* thr, const double* noise)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = mc.n[0] == 0.0 && mc.n[1] == 0.0 && mc.n[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+#define FBUS_LAUNCH_PXZ(NZF, CAM)                                                                                        \
+    hipLaunchKernelGGL((correct_pixels2_kernel<T, N, 1, NZF, CAM, NisOut<T>, NoiseIn>), dim3(tiles), dim3(64), 0, s, recs, B, M, ids, \
+                       left, right, size, 1.0, skip, applied, id2slot, mc, no, ni)
+    if (nz) { if (right) FBUS_LAUNCH_PXZ(true, 2); else FBUS_LAUNCH_PXZ(true, 1); }
+    else    { if (right) FBUS_LAUNCH_PXZ(false, 2); else FBUS_LAUNCH_PXZ(false, 1); }
+#undef FBUS_LAUNCH_PXZ
+}
+template <typename T, int N, int D>
+void launch_corners2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                             double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                             const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
+                             const double* noise)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = vc.nrm[0] == 0.0 && vc.nrm[1] == 0.0 && vc.nrm[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+#define FBUS_LAUNCH_CRZ(NZF)                                                                                             \
+    hipLaunchKernelGGL((correct_corners2_kernel<T, N, 1, NZF, NisOut<T>, NoiseIn>), dim3(tiles), dim3(64), 0, s, recs, B, M, ids, left, \
+                       right, geometry, mode, D, size, 1.0, switch_thres, skip, applied, id2slot, mc, vc, vct, no, ni)
+    if (nz) FBUS_LAUNCH_CRZ(true); else FBUS_LAUNCH_CRZ(false);
+#undef FBUS_LAUNCH_CRZ
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_pixels2_noise_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                  const FBUS_TU_T*, double, const unsigned char*,      \
+                                                                  unsigned char*, const short*, const MeasConst&, FBUS_TU_T*, \
+                                                                  int*, const double*, const double*);                 \
+    template void launch_corners2_noise_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                   const FBUS_TU_T*, int, int, double, double,         \
+                                                                   const unsigned char*, unsigned char*, const short*, \
+                                                                   const MeasConst&, const VisConst<double>&,          \
+                                                                   const VisConst<FBUS_TU_T>&, FBUS_TU_T*, int*, const double*, \
+                                                                   const double*);
+#elif FBUS_TU_FAMILY == 16
+// family 13's kernel choice with NoiseIn (per-filter r_pos / r_quat)
+template <typename T, int N, int D>
+void launch_correct_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                            const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                            const double* thr, const double* noise)
+{
+    const int grid = (B + BLOCK - 1) / BLOCK;
+    const bool joint = mode == MODE_STACKED;
+    if (M % 4 == 0 && ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(quat)) & 15) == 0 &&
+        lp.meas_vec)
+        mode |= MODE_MEAS_VEC;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+    constexpr bool SPLIT = sizeof(T) == 8;
+#define FBUS_LAUNCH_CORRECTZ(COV, JOINT)                                                                             \
+    hipLaunchKernelGGL((correct_kernel<T, N, D, COV, JOINT, SPLIT, NisOut<T>, NoiseIn>), dim3(grid), dim3(BLOCK), 0, s, recs, B, M, ids, \
+                       pos, quat, mode, skip, applied, dc, no, ni)
+    if (joseph) { if (joint) FBUS_LAUNCH_CORRECTZ(COV_JOSEPH, true); else FBUS_LAUNCH_CORRECTZ(COV_JOSEPH, false); }
+    else        { if (joint) FBUS_LAUNCH_CORRECTZ(COV_SIMPLE, true); else FBUS_LAUNCH_CORRECTZ(COV_SIMPLE, false); }
+#undef FBUS_LAUNCH_CORRECTZ
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_correct_noise_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*,       \
+                                                                  const FBUS_TU_T*, const FBUS_TU_T*, int, bool,       \
+                                                                  const unsigned char*, unsigned char*,                \
+                                                                  const DevConst<FBUS_TU_T>&, const LaunchPolicy&,     \
+                                                                  FBUS_TU_T*, int*, const double*, const double*);
 #else
-#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12 or 13"
+#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15 or 16"
 #endif
 
 FBUS_INST(DIALECT_MATLAB)

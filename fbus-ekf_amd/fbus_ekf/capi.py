@@ -25,6 +25,7 @@ STREAM_OWN = (1 << 64) - 1         # FBUS_STREAM_OWN = (void*)-1
 ABI_VERSION = 8                    # FBUS_ABI_VERSION of the header this mirror was written against
 ERR_ABI = 6
 GATE_MAX_DOF = 256                 # FBUS_GATE_MAX_DOF: a full gate table has 257 entries
+NOISE_COLS = 7                     # FBUS_NOISE_COLS: q_v q_theta q_ba q_bg r_pos r_quat r_pix (fbus_ekf_set_noise)
 
 
 class FbusError(RuntimeError):
@@ -150,6 +151,9 @@ def load_library():
         "fbus_ekf_correct_pixels_nis_dev": ([H, C.c_int, ip, vp, vp, u8p, vp, ip], C.c_int),
         "fbus_ekf_correct_corners_nis": ([H, C.c_int, ip, vp, vp, C.c_int, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_correct_corners_nis_dev": ([H, C.c_int, ip, vp, vp, C.c_int, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_set_noise": ([H, C.POINTER(C.c_double)], C.c_int),
+        "fbus_ekf_set_noise_dev": ([H, vp], C.c_int),
+        "fbus_ekf_get_noise": ([H, C.POINTER(C.c_double)], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

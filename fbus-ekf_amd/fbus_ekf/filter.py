@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from .noise import COLUMNS
 
 
 def _is_dev(x):
@@ -389,6 +390,41 @@ class BatchedFilter:
             return self._check(self._lib.fbus_ekf_set_gate(self._h, 0, None), "set_gate")
         thr = np.ascontiguousarray(thresholds, np.float64).ravel()
         self._check(self._lib.fbus_ekf_set_gate(self._h, int(thr.size), thr.ctypes.data_as(C.POINTER(C.c_double))), "set_gate")
+
+    def set_noise(self, table=None):
+        """Per-filter process and measurement noise (fbus_ekf_set_noise): a (B, 7) table, columns noise.COLUMNS (q_v q_theta q_ba q_bg
+        r_pos r_quat r_pix, the fbus_params fields of the same names); row b replaces those fields for filter b.  A numpy array (or
+        anything np.asarray takes) goes through the host form, which validates every entry; a contiguous float64 device tensor through
+        the device form, validated here with torch first.  None: no table (back to the handle's parameters)."""
+        if table is None:
+            return self._check(self._lib.fbus_ekf_set_noise(self._h, None), "set_noise")
+        B, NC = self.B, capi.NOISE_COLS
+        if _is_dev(table):
+            import torch
+            if table.dtype != torch.float64 or tuple(table.shape) != (B, NC) or not table.is_contiguous():
+                raise ValueError(f"set_noise: expected a contiguous float64 ({B}, {NC}) tensor, got {table.dtype} {tuple(table.shape)}")
+            bad = ~torch.isfinite(table)
+            bad[:, :4] |= table[:, :4] < 0
+            bad[:, 4:] |= table[:, 4:] <= 0
+            if bool(bad.any()):
+                r, c = (int(v) for v in bad.nonzero()[0])
+                raise ValueError(f"set_noise: row {r} column {c} ({COLUMNS[c]}) = {float(table[r, c])}: must be finite and "
+                                 f"{'>= 0' if c < 4 else '> 0'}")
+            self._keep.append(table)
+            cur = self._order_in(table)
+            self._check(self._lib.fbus_ekf_set_noise_dev(self._h, self._p(table)), "set_noise_dev")
+            self._order_out(cur)
+            return
+        t = np.ascontiguousarray(table, np.float64)
+        if t.shape != (B, NC):
+            raise ValueError(f"set_noise: expected ({B}, {NC}), got {t.shape}")
+        self._check(self._lib.fbus_ekf_set_noise(self._h, t.ctypes.data_as(C.POINTER(C.c_double))), "set_noise")
+
+    def get_noise(self):
+        """The current noise table, (B, 7) float64; raises FbusError when none is set."""
+        t = np.empty((self.B, capi.NOISE_COLS), np.float64)
+        self._check(self._lib.fbus_ekf_get_noise(self._h, t.ctypes.data_as(C.POINTER(C.c_double))), "get_noise")
+        return t
 
     def _nis_outputs(self, dev_like):
         if dev_like is not None:

@@ -1,0 +1,45 @@
+"""Per-filter noise tables for BatchedFilter.set_noise (fbus_ekf_set_noise): one row per filter, the columns below.
+
+A noise sweep evaluates G hypotheses on one recording in one batch: noise.grid builds the Cartesian product of per-column
+scale factors around a parameter set and assigns it to the filters round-robin (filter b gets hypothesis b mod G), so every
+hypothesis is run by B / G filters.  numpy only.
+"""
+import itertools
+
+import numpy as np
+
+# the fbus_params fields, in the table's column order (FBUS_NOISE_COLS = 7)
+COLUMNS = ("q_v", "q_theta", "q_ba", "q_bg", "r_pos", "r_quat", "r_pix")
+
+
+def row_of(params):
+    """the parameters' own values as one table row (q_diag[0..3], r_pos, r_quat, r_pix)"""
+    q = list(params.q_diag)
+    return np.array([q[0], q[1], q[2], q[3], params.r_pos, params.r_quat, params.r_pix], np.float64)
+
+
+def from_params(params, B):
+    """(B, 7): every filter with the parameters' own noise (the table that changes nothing)"""
+    return np.tile(row_of(params), (int(B), 1))
+
+
+def grid(params, B, **scales):
+    """Cartesian product of per-column scale factors, e.g. grid(prm, B, r_pix=[0.5, 1, 2], q_v=[0.1, 1, 10]) -> 9 hypotheses.
+    Columns not named keep the parameters' value.  Returns (table (B, 7), hyp (B,) int, rows (G, 7)): filter b runs hypothesis
+    hyp[b] = b mod G, whose row is rows[hyp[b]]; the hypotheses are ordered as itertools.product over the named columns in
+    COLUMNS order."""
+    unknown = set(scales) - set(COLUMNS)
+    if unknown:
+        raise ValueError(f"grid: unknown columns {sorted(unknown)}; expected some of {COLUMNS}")
+    base = row_of(params)
+    named = [c for c in COLUMNS if c in scales]
+    factors = [np.asarray(scales[c], np.float64).ravel() for c in named]
+    rows = []
+    for combo in itertools.product(*factors):
+        r = base.copy()
+        for c, f in zip(named, combo):
+            r[COLUMNS.index(c)] *= f
+        rows.append(r)
+    rows = np.array(rows, np.float64).reshape(-1, len(COLUMNS))
+    hyp = np.arange(int(B)) % len(rows)
+    return rows[hyp], hyp, rows

@@ -150,6 +150,22 @@ public:
                                  const uint8_t* skip, Real* nis, int32_t* dof)
     { check(fbus_ekf_correct_corners_nis_dev(h_, M, ids, left, right, geometry, int(mode), skip, nis, dof), "correct_corners_nis_dev"); }
 
+    // per-filter noise (include/fbus_ekf.h): a batch() x FBUS_NOISE_COLS table, row-major, columns q_v q_theta q_ba q_bg r_pos r_quat r_pix;
+    // an empty table: none (back to fbus_params).  set_noise_dev: a device table, stream-ordered, not inspected
+    void set_noise(const std::vector<double>& table)
+    {
+        if (!table.empty() && table.size() != size_t(batch_) * FBUS_NOISE_COLS)
+            throw std::invalid_argument("fbus::BatchedFilter::set_noise: expected batch() x FBUS_NOISE_COLS entries");
+        check(fbus_ekf_set_noise(h_, table.empty() ? nullptr : table.data()), "set_noise");
+    }
+    void set_noise_dev(const double* table) { check(fbus_ekf_set_noise_dev(h_, table), "set_noise_dev"); }
+    std::vector<double> get_noise() const
+    {
+        std::vector<double> t(size_t(batch_) * FBUS_NOISE_COLS);
+        check(fbus_ekf_get_noise(h_, t.data()), "get_noise");
+        return t;
+    }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

@@ -106,7 +106,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  * mismatch with FBUS_ERR_ABI.  (Bindings that cannot use the macro -- ctypes, loadlibrary -- call
  * fbus_ekf_abi_version() / fbus_params_size() once after loading and compare; the Python mirror does.)
  *   8  fbus_ekf_set_gate, fbus_ekf_correct_nis[_dev], fbus_ekf_correct_pixels_nis[_dev], fbus_ekf_correct_corners_nis[_dev]
- *      (struct unchanged)
+ *      (struct unchanged); added under 8 without a bump: fbus_ekf_set_noise[_dev], fbus_ekf_get_noise (per-filter noise; no
+ *      existing meaning changed -- callers detect the feature by the symbol)
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -514,6 +515,37 @@ int fbus_ekf_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const 
                                  int mode, const uint8_t* skip, void* nis, int32_t* dof);
 int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                                      int mode, const uint8_t* skip, void* nis, int32_t* dof);
+
+/* ---- per-filter process and measurement noise -------------------------------------------------------------------------
+ * Every filter of a handle takes q_diag, r_pos, r_quat and r_pix from fbus_params until a table is set.  fbus_ekf_set_noise
+ * gives each filter its own: a B x FBUS_NOISE_COLS table, row-major, fp64 for both record types, columns
+ *     q_v q_theta q_ba q_bg r_pos r_quat r_pix      (= fbus_params q_diag[0..3], r_pos, r_quat, r_pix)
+ * Filter b then runs the arithmetic of a handle whose fbus_params hold row b's values: the kernels convert each entry to the record
+ * type as the handle converts fbus_params ((T)q on the device equals the host's (T)prm.q_diag[i]; 1 / r_pix and 1 / r_pos are formed
+ * from the same double).  The NIS forms use the filter's own R in S = H P H' + R.  What stays shared: the gate table (indexed by dof),
+ * switch_thres, p0_diag (fbus_ekf_set_state takes per-filter P), the camera, port and marker constants.
+ * STORAGE: the handle owns one device buffer, allocated at the first set_noise and kept until destroy, holding the table as fields
+ * [FBUS_NOISE_COLS][B] in double; later calls rewrite the same buffer in place.  A captured graph (fbus_ekf_graph_*) that ran with a
+ * table therefore sees the values current at its replay.  A graph captured without a table keeps the kernels it captured (it reads
+ * fbus_params as they were at capture).  set_noise / set_noise_dev / get_noise are refused between graph_begin and graph_end.
+ * ROUTES with a table: the one-wave-per-tile kernels only.  The team forms (fbus_ekf_set_team is ignored while a table is set, and
+ * fbus_ekf_launch_info reports ROLES_* = 1, TEAM_FRAMES = 0, MEAS_SPLIT = 0), the divided pixel update and the resident window
+ * kernels are bypassed; fbus_ekf_frame*_fused_dev and the windows run frame by frame (predict_n + the per-call update; trajectory rows
+ * from the snapshot kernel).  The plain updates run the NIS kernels with no outputs and no gate: records equal a handle with the row's
+ * values in fbus_params on its one-wave route bit for bit, except fp64 C++-dialect stacked pose updates (nominal state within ~2e-15,
+ * see the NIS section above).
+ * fbus_ekf_set_noise     host table; every entry must be finite, q >= 0 and r > 0 (as fbus_params_validate).  A bad entry returns
+ *                        FBUS_ERR_INVALID with its row and column in fbus_ekf_last_error and leaves the previous table (or none) in
+ *                        force.  Copied in order on the handle's stream; returns after the copy.  NULL: no table (back to fbus_params).
+ * fbus_ekf_set_noise_dev device table, stream-ordered on the handle's stream (the caller keeps it alive until the stream has passed the
+ *                        call).  Like every _dev entry point it does NOT inspect the values: the caller validates them (the Python
+ *                        mirror does, with torch).  NULL: no table.
+ * fbus_ekf_get_noise     the current table into a host B x FBUS_NOISE_COLS array (waits for the stream); FBUS_ERR_INVALID when no table
+ *                        is set. */
+#define FBUS_NOISE_COLS 7   /* q_v q_theta q_ba q_bg r_pos r_quat r_pix -- the fbus_params fields of the same names */
+int fbus_ekf_set_noise(fbus_ekf_t h, const double* table);      /* host, B x 7 row-major; NULL = no table (back to fbus_params) */
+int fbus_ekf_set_noise_dev(fbus_ekf_t h, const double* table);  /* device, B x 7 row-major, stream-ordered; NULL = no table      */
+int fbus_ekf_get_noise(fbus_ekf_t h, double* table);            /* host, B x 7; FBUS_ERR_INVALID when no table is set          */
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
