@@ -1,15 +1,16 @@
 #!/usr/bin/env python3
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
-The library is 49 translation units compiled in parallel and linked into one shared object:
+The library is 57 translation units compiled in parallel and linked into one shared object:
   fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose)
-  kernels_tu.hip x 48                   one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
+  kernels_tu.hip x 56                   one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
                                         float: predict / correct / frame / frames / team / meas / fmeas / msplit / framest / fmeast
-                                        / measnis / correctnis / prednz / measnz / correctnz (15 x 2 = 30; framest / fmeast: the windows
+                                        / measnis / correctnis / prednz / measnz / correctnz / measlik / correctlik (17 x 2 = 34; framest / fmeast: the windows
                                         with per-frame trajectory rows, measnis / correctnis: the pixel / corner and the pose updates with
                                         the NIS output and the gate, prednz / measnz / correctnz: predict and the NIS updates with
-                                        per-filter noise), double: predict / correct / frame / meas / measnis / correctnis / prednz /
-                                        measnz / correctnz (9 x 2 = 18; len(units()) == 49 with fbus_ekf.hip)
+                                        per-filter noise, measlik / correctlik: the tabled NIS updates with the log-likelihood sums),
+                                        double: predict / correct / frame / meas / measnis / correctnis / prednz / measnz / correctnz /
+                                        measlik / correctlik (11 x 2 = 22; len(units()) == 57 with fbus_ekf.hip)
 Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.
   python build.py [--force] [--only f32_18_correct,...] [--jobs N]
 FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds (A/B of differently built kernels via FBUS_EKF_LIB).
@@ -27,7 +28,7 @@ OUT = os.environ.get("FBUS_OUT") or os.path.join(HERE, "lib", "libfbus_ekf.so") 
 OBJDIR = os.environ.get("FBUS_OBJDIR") or os.path.join(os.path.dirname(OUT), "obj" if not os.environ.get("FBUS_OUT") else
                                                        "obj_" + os.path.splitext(os.path.basename(OUT))[0])
 FAMILIES = {"predict": 1, "correct": 2, "frame": 3, "frames": 5, "team": 6, "meas": 7, "fmeas": 8, "msplit": 9, "framest": 10, "fmeast": 11, "measnis": 12, "correctnis": 13,
-            "prednz": 14, "measnz": 15, "correctnz": 16}
+            "prednz": 14, "measnz": 15, "correctnz": 16, "measlik": 17, "correctlik": 18}
 # Per-family scheduler choice (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
 # max-ILP strategy of the AMDGPU machine scheduler shortens the per-call kernels, where one wave per SIMD has nothing
 # but its own independent instructions to cover dependent-issue stalls (predict 13.4 -> 13.05 us, stacked correct
@@ -44,12 +45,15 @@ FAMILY_FLAGS = {"predict": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-
                 "measnis": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnis": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
                 # the per-filter noise kernels (families 14-16) with the flags of the kernels they extend, both record types
                 "prednz": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
-                "measnz": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnz": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+                "measnz": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnz": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
+                # the log-likelihood kernels (families 17 / 18) with the flags of the tabled kernels they extend, both record types
+                "measlik": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctlik": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
 # fp64 units.  meas (correct_pixels2 / correct_corners2 <double>, 512 registers + scratch): the max-memory-clause strategy leaves them
 # 28-136 bytes of scratch instead of 136-340 and is 4-11 % faster (profiles/r05_f64_sched.txt); FBUS_F64_FLAGS_<FAMILY> overrides
 F64_FAMILY_FLAGS = {fam: os.environ.get("FBUS_F64_FLAGS_" + fam.upper(),
-                                        "-mllvm -amdgpu-sched-strategy=max-memory-clause" if fam in ("meas", "measnis", "measnz") else "").split()
-                    for fam in ("predict", "correct", "frame", "meas", "measnis", "correctnis", "prednz", "measnz", "correctnz")}
+                                        "-mllvm -amdgpu-sched-strategy=max-memory-clause" if fam in ("meas", "measnis", "measnz", "measlik") else "").split()
+                    for fam in ("predict", "correct", "frame", "meas", "measnis", "correctnis", "prednz", "measnz", "correctnz", "measlik",
+                                "correctlik")}
 TYPES = {"f32": "float", "f64": "double"}
 
 

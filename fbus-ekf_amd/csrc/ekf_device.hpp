@@ -1265,12 +1265,42 @@ __device__ __forceinline__ void noise_pose(DevConst<T>& dc, int b, const NO&... 
     dc.r_quat = (T)noise_ld(n, NOISE_RQUAT, b);
 }
 
+// ---- innovation log-likelihood (fbus_ekf_loglik_*): a trailing kernel parameter LikOut behind (NisOut, NoiseIn) -- the likelihood kernels
+// are always the tabled kind (kernels_tu.hip families 17 / 18).  acc: the handle's sums as fp64 fields [4][B] (ll, rows of S, applied,
+// rejected; the counts are exact in a double far beyond any run); lane b owns filter b and updates its four entries with ordinary loads
+// and stores, behind the gate decision: an applied update adds to the first three, a rejected one to the last alone.
+struct LikOut { double* acc; int B; };
+enum { LIK_LL = 0, LIK_ROWS = 1, LIK_APPLIED = 2, LIK_REJECTED = 3 };
+template <typename... NO> constexpr bool has_lik() { return (std::is_same<NO, LikOut>::value || ... || false); }
+template <typename T> __device__ __forceinline__ NisOut<T> nis_out(const NisOut<T>& o, const NoiseIn&, const LikOut&) { return o; }
+template <typename T> __device__ __forceinline__ NoiseIn noise_in(const NisOut<T>&, const NoiseIn& n, const LikOut&) { return n; }
+template <typename T> __device__ __forceinline__ LikOut lik_out(const NisOut<T>&, const NoiseIn&, const LikOut& l) { return l; }
+// a value of the 6 x 6 stage handed to the likelihood arithmetic (nis_in's reason: no second user for a value of the update)
+__device__ __forceinline__ double lik_in(double x) { asm("" : "+v"(x)); return x; }
+// one update of filter b.  ll = -1/2 (nis + log det S + rows ln 2 pi) with log det S = lndetR + ln detw (detw = det(I + P_JJ Lam), the
+// PRODUCT of the Cholesky pivots: one logarithm for the six of them; every pivot is >= 1 and the product of six stays far inside a double)
+__device__ __forceinline__ void lik_add(const LikOut& l, int b, bool applied, double nis, double lndetR, double detw, int rows)
+{
+    double* a = l.acc + b;
+    const size_t B = (size_t)l.B;
+    if (applied) {
+        const double ll = -0.5 * (nis + (lndetR + log(detw)) + (double)rows * 1.8378770664093454835606594728112);
+        a[LIK_LL * B] += ll;
+        a[LIK_ROWS * B] += (double)rows;
+        a[LIK_APPLIED * B] += 1.0;
+    } else {
+        a[LIK_REJECTED * B] += 1.0;
+    }
+}
+
 // NIS of the pose rows at the prior: sumw - b' (P_JJ^-1 + Lam)^-1 b  (sumw = sum w res^2; Lam, b of the fold), in double.
 // With P_JJ = C C' and K = I + C' Lam C = D D' (eigenvalues >= 1: no pivoting needed), (P_JJ^-1 + Lam)^-1 = C K^-1 C', so the
 // subtracted term is |D^-1 C' b|^2 -- the same value as b' y with (I + P_JJ Lam) y = P_JJ b.  A pivot of P_JJ that is not positive
 // drops its column (no prior uncertainty in that direction: the term has nothing to take from it).
-template <typename T>
-__device__ __forceinline__ double pose_nis(const InfoAcc<T>& acc, const double* PJJ, double sumw)
+// DET (the likelihood kernels): *detK = det K = det(I + P_JJ Lam), the product of D's squared pivots (a dropped pivot of P_JJ leaves a
+// unit pivot there: a factor 1)
+template <typename T, bool DET = false>
+__device__ __forceinline__ double pose_nis(const InfoAcc<T>& acc, const double* PJJ, double sumw, double* detK = nullptr)
 {
     double C[36];
 #pragma unroll
@@ -1317,6 +1347,7 @@ __device__ __forceinline__ double pose_nis(const InfoAcc<T>& acc, const double* 
 #pragma unroll
         for (int k = 0; k < a; ++k) piv -= K[6 * a + k] * K[6 * a + k];
         const double sq = sqrt(piv), is = 1.0 / sq;
+        if constexpr (DET) *detK = (a == 0) ? lik_in(piv) : *detK * lik_in(piv);
         K[6 * a + a] = sq;
 #pragma unroll
         for (int i = a + 1; i < 6; ++i) {

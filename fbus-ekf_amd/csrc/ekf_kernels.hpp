@@ -606,6 +606,10 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     const NisOut<T> nout = nis_out<T>(no...);
     double nisv = 0.0;
     int dofv = 0;
+    // NO = (NisOut<T>, NoiseIn, LikOut) (fbus_ekf_loglik_enable; kernels_tu.hip family 18): det(I + P_JJ Lam) from pose_nis's second
+    // factorisation; the filter's sums are updated behind the last store of each exit (lik_done)
+    constexpr bool LIK = has_lik<NO...>();
+    double detv = 1.0;
     constexpr int ROWS = DIALECT == DIALECT_CPP ? 7 : 3;             // rows with a residual per marker (Matlab: q residual zeroed)
     constexpr int G = FBUS_MARKER_GROUP;
     const bool vec = (mode & MODE_MEAS_VEC) != 0;     // set by the launcher: 16-byte loads of the measurement inputs are legal
@@ -704,12 +708,26 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
                 PJJ[6 * i + j] = v; PJJ[6 * j + i] = v;
             }
         const double sumw = (double)fb_rcp1(dc.r_pos) * fold.sr2p + (DIALECT == DIALECT_CPP ? (double)fb_rcp1(dc.r_quat) * fold.sr2q : 0.0);
-        nisv = pose_nis<T>(acc, PJJ, sumw);
+        if constexpr (LIK) nisv = pose_nis<T, true>(acc, PJJ, sumw, &detv);
+        else nisv = pose_nis<T>(acc, PJJ, sumw);
         dofv = ROWS * nm;
         return nisv > nout.thr[dofv];                                  // (the launcher always passes the handle's table: +inf without one)
     };
     // the statistic folds the rows a second time from an opaque copy of the nominal state: shared with the update's fold, the fold's
     // products would gain users in the NIS arithmetic and the compiler would contract them differently (the update must stay the twin's)
+    // the likelihood sums of this filter: all 7 rows of each used marker are rows of S in both dialects (Matlab: the quaternion residual
+    // is zeroed, its rows stay), so rows = 7 n where dof = ROWS n; log det R from the lane's own table fields, read here again
+    // rather than held across the update
+    auto lik_done = [&](bool was_applied) __attribute__((always_inline)) {
+        if constexpr (LIK) {
+            if (dofv > 0) {
+                const NoiseIn ni = noise_in(no...);
+                const int nm = dofv / ROWS;
+                const double lnr = 3.0 * log(noise_ld(ni, NOISE_RPOS, b)) + 4.0 * log(noise_ld(ni, NOISE_RQUAT, b));
+                lik_add(lik_out<T>(no...), b, was_applied, nisv, (double)nm * lnr, detv, 7 * nm);
+            }
+        }
+    };
     auto opaque_nom = [&](T* c) __attribute__((always_inline)) {
 #pragma unroll
         for (int i = 0; i < L::NNOM; ++i) { T x = nom[i]; asm("" : "+v"(x)); c[i] = x; }
@@ -885,7 +903,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         }
     }
     if (used == 0) {
-        if (b < B) { applied[b] = 0; if constexpr (NIS) nis_write(nout, b, nisv, dofv); }
+        if (b < B) { applied[b] = 0; if constexpr (NIS) nis_write(nout, b, nisv, dofv); lik_done(false); }
         return;
     }
     if constexpr (LEAN) {               // the nominal state was not held across the passes: read it again (L2-hot)
@@ -901,6 +919,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     store_chunks<T, N, C_REST, RC::NCH, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (C_REST - RC::CH_NOM) * RC::EPC);
     applied[b] = 1;
     if constexpr (NIS) nis_write(nout, b, nisv, dofv);
+    lik_done(true);
 }
 
 // One camera frame in ONE launch: K ImuUpdates then one MeasureUpdate with the record resident in

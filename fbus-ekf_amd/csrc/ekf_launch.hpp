@@ -137,6 +137,23 @@ void launch_corners2_noise_k(hipStream_t s, T* recs, int B, int M, const int* id
                              const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
                              const double* noise);
 
+// ---- innovation log-likelihood (fbus_ekf_loglik_enable): the tabled one-wave forms with a trailing LikOut, lik = the handle's sums [4][B]
+// (ll, rows, applied, rejected as doubles).  The kernel choice of the launchers above (kernels_tu.hip families 17 / 18); the plain
+// updates pass null nis / dof and the tabled routes' "no gate" thr.
+template <typename T, int N, int D>
+void launch_correct_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                          const double* thr, const double* noise, double* lik);
+template <typename T, int N, int D>
+void launch_pixels2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
+                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                          const double* thr, const double* noise, double* lik);
+template <typename T, int N, int D>
+void launch_corners2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                           double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                           const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
+                           const double* noise, double* lik);
+
 // ---- one camera frame with the north star's MeasureUpdate in one launch (ekf_meas.hpp::frame_meas_kernel; fp32) -----------------
 // kind: corner pixels (geometry / mode ignored; right == nullptr: left camera) or stereo corners (geometry, mode as correct_corners)
 enum { MEAS_PIXELS = 0, MEAS_CORNERS = 1 };

@@ -913,8 +913,11 @@ __device__ __forceinline__ void corner_fold_marker(PixAcc& acc, const double* p,
 // lidx order), m = G' b (6)
 __host__ __device__ constexpr int ltx(int i, int j) { return i * (i + 1) / 2 + j; }      // lower triangle, j <= i
 // MD (the NIS kernels): m in double as well, md = G' b before the cast to T
-template <typename T, bool MD = false>
-__device__ __forceinline__ void info_solve(const double* Lam, const double* b, const double* PJJ, T* G, T* Sinv, T* m, double* md = nullptr)
+// DET (the likelihood kernels): *icp = prod_a iC[a], the product of the reciprocal pivots of Cm: det(I + P_JJ Lam) = det Mt = 1 / icp^2
+// (a dropped pivot of Lam leaves Lam = Lc Lc' true, so the identity holds with invisible directions)
+template <typename T, bool MD = false, bool DET = false>
+__device__ __forceinline__ void info_solve(const double* Lam, const double* b, const double* PJJ, T* G, T* Sinv, T* m, double* md = nullptr,
+                                           double* icp = nullptr)
 {
     // Lam = Lc Lc' (no pivoting: Lam is positive semi-definite; a pivot that is not clearly positive relative to its original
     // diagonal carries no information and its column is dropped -- joint_factor's rule)
@@ -964,6 +967,7 @@ __device__ __forceinline__ void info_solve(const double* Lam, const double* b, c
     for (int a = 0; a < 6; ++a) {
         const double s = md_rsq(Cm[ltx(a, a)]);
         iC[a] = s;
+        if constexpr (DET) *icp = (a == 0) ? lik_in(s) : *icp * lik_in(s);
 #pragma unroll
         for (int i = a; i < 6; ++i) Cm[ltx(i, a)] *= s;
 #pragma unroll
@@ -1310,11 +1314,28 @@ __device__ __forceinline__ void meas_solve_update(T* P, const PixAcc& acc, const
 // The NIS kernels (NIS = true, ns != null): the normalised innovation squared of the stacked rows at the prior, in double --
 //     NIS = r' S^-1 r = w sum res^2 - b' P_JJ m     (S^-1 r = R^-1 (r - H dx),  dx_J = P_JJ m,  m = G' b)
 // -- and the gate: NIS > ns->thr leaves the record alone (nothing below the 6 x 6 stage runs: no covariance store, no injection).
+// The likelihood kernels (LIK = true, lc != null): the product of the 6 x 6 stage's reciprocal pivots as well (info_solve's DET), and the
+// filter's sums updated behind the gate decision.  fp32 records: at once, where the 6 x 6 stage's values are dead and the update's not
+// yet live; fp64 records (at the 512-register limit): behind the last store, the product waiting in LDS behind G (gpark[36 * 64]).
+// Nothing of the likelihood is held in registers across the update.
 struct NisState { double thr, nis; bool reject; };
-template <typename T, int N, bool NIS = false>
+// r: the table field that is this update's R (read at the use); log det S = rows ln r - 2 ln prod iC
+struct LikCtx {
+    LikOut out; NoiseIn ni; int col, b, rows;
+    __device__ __forceinline__ void applied(double nis, double icp) const
+    {
+        // (the filter index through an empty asm that waits for nis: the loads of the table field and of the sums are formed from it
+        // and so cannot be requested in front of the 6 x 6 stage, where their targets would be live across its peak)
+        int o = b;
+        asm volatile("" : "+v"(o), "+v"(nis) :: "memory");
+        if (rows > 0) lik_add(out, o, true, nis, (double)rows * log(noise_ld(ni, col, o)), 1.0 / (icp * icp), rows);
+    }
+    __device__ __forceinline__ void rejected() const { if (rows > 0) lik_add(out, b, false, 0.0, 0.0, 1.0, rows); }
+};
+template <typename T, int N, bool NIS = false, bool LIK = false>
 __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs, unsigned lane, const PixAcc& acc, const double* Rd, double w,
                                                  int new_prev, T* gpark /* fp64 records: this lane's column of 36 x 64 values in LDS */,
-                                                 NisState* ns = nullptr)
+                                                 NisState* ns = nullptr, const LikCtx* lc = nullptr)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
@@ -1355,8 +1376,10 @@ __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs
                     for (int j = 0; j < 6; ++j) PJJ[6 * i + j] = (double)P[pidx<N>(jcol(i), jcol(j))];
                 if constexpr (NIS) {
                     double md[6];
-                    info_solve<T, true>(Lam, bv, PJJ, G, cs.s, cs.m_, md);
+                    double icp = 1.0;
+                    info_solve<T, true, LIK>(Lam, bv, PJJ, G, cs.s, cs.m_, md, &icp);
                     if (nis_gate(bv, PJJ, md)) return;          // in front of the first store
+                    if constexpr (LIK) gpark[36 * 64] = icp;    // (fp64 records: waits in LDS behind G; the sums behind the last store)
                 } else {
                     info_solve<T>(Lam, bv, PJJ, G, cs.s, cs.m_);
                 }
@@ -1392,6 +1415,7 @@ __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs
         inject<T, N>(nom, dx);
         store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, lane, nom);
         store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, lane, nom + L::NPQR);
+        if constexpr (LIK) { order_fence(); lc->applied(ns->nis, (double)gpark[36 * 64]); }
         return;
     }
     // the covariance is requested here: it arrives under the 6 x 6 stage
@@ -1410,8 +1434,10 @@ __device__ __forceinline__ void meas_update_tail(const __amdgpu_buffer_rsrc_t rs
                 for (int j = 0; j < 6; ++j) PJJ[6 * i + j] = (double)P[pidx<N>(jcol(i), jcol(j))];
             if constexpr (NIS) {
                 double md[6];
-                info_solve<T, true>(Lam, bv, PJJ, G, Sinv, m, md);
+                double icp = 1.0;
+                info_solve<T, true, LIK>(Lam, bv, PJJ, G, Sinv, m, md, &icp);
                 if (nis_gate(bv, PJJ, md)) return;              // in front of the update and every store
+                if constexpr (LIK) lc->applied(ns->nis, icp);
             } else {
                 info_solve<T>(Lam, bv, PJJ, G, Sinv, m);
             }
@@ -1464,6 +1490,21 @@ __device__ __forceinline__ bool nis_tail(const NisOut<T>& o, int b, const __amdg
     if (o.dof) o.dof[b] = dof;
     return !ns.reject;
 }
+// NO = (NisOut<T>, NoiseIn, LikOut) (fbus_ekf_loglik_enable; kernels_tu.hip family 17): nis_tail, then the filter's likelihood sums.
+// col: the table field that is this update's R (NOISE_RPIX / NOISE_RPOS)
+template <typename T, int N>
+__device__ __forceinline__ bool lik_tail(const NisOut<T>& o, const NoiseIn& ni, const LikOut& lk, int col, int b, const __amdgpu_buffer_rsrc_t rs,
+                                         unsigned lane, const PixAcc& acc, const double* Rd, double w, int new_prev, T* gpark)
+{
+    const int dof = (int)acc.nrow;
+    NisState ns{ o.thr ? o.thr[dof] : __builtin_inf(), 0.0, false };
+    const LikCtx lc{ lk, ni, col, b, dof };
+    meas_update_tail<T, N, true, true>(rs, lane, acc, Rd, w, new_prev, gpark, &ns, &lc);
+    if (o.nis) o.nis[b] = (T)ns.nis;
+    if (o.dof) o.dof[b] = dof;
+    if (ns.reject) lc.rejected();
+    return !ns.reject;
+}
 template <typename T, int N, int NR, bool NZ, int CAM = 0, typename... NO>
 __global__ void __launch_bounds__(64 * NR)
 correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ left,
@@ -1487,7 +1528,7 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, tile);
     __shared__ MeasLDS tbl;
     // the roles' partial sums; fp64 records: behind them (role 0 has added them up by then) G waits here while the block outside J is updated
-    constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? 36 * 64 : 1;
+    constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? (has_lik<NO...>() ? 37 : 36) * 64 : 1;
     __shared__ double part_mem[PART_N > GPARK_N ? PART_N : GPARK_N];
     T* gpark_mem = reinterpret_cast<T*>(part_mem);
     // CAM: 0 = left camera or stereo by the right pointer (one kernel for both), 1 = left camera only, 2 = stereo only: compiled
@@ -1610,9 +1651,17 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
         acc.to_imu_frame(mc.adjL);
         double RM[9];
         PixAcc::camera_rotation(Rd, mc.McL, RM);
+        if constexpr (has_lik<NO...>()) {
+            applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPIX, b, rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0;
+            return;
+        }
         if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
         meas_update_tail<T, N>(rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane);
         applied[b] = 1;
+        return;
+    }
+    if constexpr (has_lik<NO...>()) {
+        applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPIX, b, rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0;
         return;
     }
     if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
@@ -1649,7 +1698,7 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, tile);
     __shared__ MeasLDS tbl;
     // the roles' partial sums; fp64 records: behind them (role 0 has added them up by then) G waits here while the block outside J is updated
-    constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? 36 * 64 : 1;
+    constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? (has_lik<NO...>() ? 37 : 36) * 64 : 1;
     __shared__ double part_mem[PART_N > GPARK_N ? PART_N : GPARK_N];
     T* gpark_mem = reinterpret_cast<T*>(part_mem);
     struct Meas { int id; T l[12], r[8]; };
@@ -1800,6 +1849,10 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
         return;
     }
     acc.expand_const(mc.NI);
+    if constexpr (has_lik<NO...>()) {
+        applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPOS, b, rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane) ? 1 : 0;
+        return;
+    }
     if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane) ? 1 : 0; return; }
     meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane);
     applied[b] = 1;

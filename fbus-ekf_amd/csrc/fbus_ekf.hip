@@ -158,6 +158,11 @@ struct fbus_ekf {
     // set_noise and never moved, so a captured call reads the values current at its replay.  noise_on: the tabled routes are taken
     double* d_noise = nullptr;
     bool noise_on = false;
+    // innovation log-likelihood sums (fbus_ekf_loglik_*): [4][B] doubles (ll, rows, applied, rejected), allocated at the first enable and
+    // never moved.  lik_on: every measurement update takes the tabled one-wave route with the likelihood kernels (families 17 / 18);
+    // without a noise table d_noise then holds fbus_params' own row (lik_fill), and noise_on stays false: predict keeps its untabled kernels
+    double* d_lik = nullptr;
+    bool lik_on = false;
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
@@ -287,12 +292,14 @@ void timing_end(fbus_ekf_t h, int i)
 // was measured is "how much of the chip a one-wave launch leaves idle"), and the batch they are compared with is the POLICY batch:
 // the handle's own unless fbus_ekf_set_policy_batch names the whole job -- team and one-wave kernels agree to fp32 rounding only,
 // so a job cut into shards (fbus::ShardedFilter) keys the choice on the total and gets the same kernels whatever the shard layout.
+// the measurement updates read the noise table: one set by the caller, or the handle's own row while the likelihood sums are on
+bool tabled(const fbus_ekf* h) { return h->noise_on || h->lik_on; }
 int policy_tiles(const fbus_ekf* h) { return ((h->policy_batch > 0 ? h->policy_batch : h->B) + 63) / 64; }
 int quarter_chip(const fbus_ekf* h) { return h->lp.simds / 4; }
 int half_chip(const fbus_ekf* h) { return h->lp.simds / 2; }
 int team_roles_predict(const fbus_ekf* h, int K)
 {
-    if (h->dtype != 32 || h->team_predict == 1 || h->noise_on) return 1;      // (a noise table: the one-wave forms only)
+    if (h->dtype != 32 || h->team_predict == 1 || tabled(h)) return 1;      // (a noise table, likelihood sums: the one-wave forms only)
     if (h->team_predict >= 2) return K > 1 ? 4 : (h->team_predict > 4 ? 4 : h->team_predict);
     const int tiles = policy_tiles(h);
     if (K > 1) return tiles <= half_chip(h) ? 4 : 1;
@@ -303,7 +310,7 @@ int team_roles_predict(const fbus_ekf* h, int K)
 // 0 = four up to a quarter of the chip, two up to half.  Both record types.
 int team_roles_pixels(const fbus_ekf* h, int M)
 {
-    if (M < 2 || h->team_correct == 1 || h->noise_on) return 1;
+    if (M < 2 || h->team_correct == 1 || tabled(h)) return 1;
     if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
     const int tiles = policy_tiles(h);
     return tiles <= quarter_chip(h) ? 4 : (tiles <= half_chip(h) ? 2 : 1);
@@ -315,7 +322,7 @@ int team_roles_pixels(const fbus_ekf* h, int M)
 int meas_split_roles(const fbus_ekf* h, int M)
 {
     const double* n = h->prm.port_normal;
-    if (h->dtype != 32 || M < 2 || h->team_correct == 1 || h->meas_split == 0 || h->noise_on) return 0;
+    if (h->dtype != 32 || M < 2 || h->team_correct == 1 || h->meas_split == 0 || tabled(h)) return 0;
     if (!(n[0] == 0.0 && n[1] == 0.0 && n[2] == 1.0)) return 0;
     if (h->meas_split > 0) return h->meas_split;
     if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
@@ -328,7 +335,7 @@ int meas_split_roles(const fbus_ekf* h, int M)
 // 32 768 filters, 0.8x at 40 960).
 bool team_frames(const fbus_ekf* h, int mode)
 {
-    if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH || h->noise_on) return false;
+    if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH || tabled(h)) return false;
     if (mode != MODE_NEAREST && mode != MODE_STACKED) return false;
     if (h->team_frame == 1 || (h->team_frame == 0 && h->team_predict == 1)) return false;
     if (h->team_frame == 2 || h->team_predict >= 2) return true;
@@ -383,16 +390,28 @@ int launch_predict_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, c
     return FBUS_OK;
 }
 
+// the tabled updates: the noise kernels (families 15 / 16), or the likelihood kernels (17 / 18) while the sums are on
+template <typename T, int N, int D>
+void tabled_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, void* nis,
+                    int32_t* dof, const double* thr)
+{
+    if (h->lik_on)
+        launch_correct_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                      h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
+                                      (T*)nis, (int*)dof, thr, h->d_noise, h->d_lik);
+    else
+        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
+                                        (T*)nis, (int*)dof, thr, h->d_noise);
+}
 template <typename T, int N, int D>
 int launch_correct_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
                      const uint8_t* skip)
 {
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;   // false: written through (sc1), the next predict streams them like any other
-    if (h->noise_on)                            // the NIS kernel with no outputs and the +inf table: this filter's r_pos / r_quat
-        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
-                                        nullptr, nullptr, h->d_noise + (size_t)FBUS_NOISE_COLS * h->B, h->d_noise);
+    if (tabled(h))                              // the NIS kernel with no outputs and the +inf table: this filter's r_pos / r_quat
+        tabled_correct<T, N, D>(h, M, ids, pos, quat, mode, skip, nullptr, nullptr, h->d_noise + (size_t)FBUS_NOISE_COLS * h->B);
     else
     launch_correct_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                   h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp);
@@ -433,7 +452,7 @@ int launch_frame_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, con
 {
     const bool f64_fused = sizeof(T) == 8 && mode == MODE_STACKED && h->prm.cov_form != FBUS_COV_JOSEPH && K > 0 && K <= 255;
     // (a noise table: no fused kernel reads it -- predict_n + the per-call update, which do)
-    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || h->noise_on) {
+    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || tabled(h)) {
         // no fused kernel for fp64 outside (stacked, simple) and none for the Joseph form with the reference mode's 7 row-by-row
         // updates (it spilled): those frames are one predict_n launch and one correct launch -- the same arithmetic
         int rc = FBUS_OK;
@@ -750,6 +769,32 @@ int do_pose_init(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const
 }
 
 template <typename T, int N, int D>
+void tabled_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
+                    void* nis, int32_t* dof, const double* thr)
+{
+    if (h->lik_on)
+        launch_corners2_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                       h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
+                                       make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, thr, h->d_noise, h->d_lik);
+    else
+        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
+                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, thr, h->d_noise);
+}
+template <typename T, int N, int D>
+void tabled_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip, void* nis, int32_t* dof,
+                   const double* thr)
+{
+    if (h->lik_on)
+        launch_pixels2_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
+                                      h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
+                                      (int*)dof, thr, h->d_noise, h->d_lik);
+    else
+        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
+                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
+                                        (int*)dof, thr, h->d_noise);
+}
+template <typename T, int N, int D>
 int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                              int mode, const uint8_t* skip)
 {
@@ -761,10 +806,8 @@ int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void
     // triangulation and fold in double, non-cancelling update (ekf_meas.hpp); records written through (sc1) as correct_kernel's
     h->records_warm = h->warm_after_correct;
     const int roles = mode == MODE_STACKED ? team_roles_pixels(h, M) : 1;
-    if (h->noise_on)                    // the NIS kernel with no outputs and no gate: this filter's r_pos (kernels_tu.hip family 15)
-        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
-                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), nullptr, nullptr, nullptr, h->d_noise);
+    if (tabled(h))                      // the NIS kernel with no outputs and no gate: this filter's r_pos (kernels_tu.hip family 15)
+        tabled_corners<T, N, D>(h, M, ids, left, right, geometry, mode, skip, nullptr, nullptr, nullptr);
     else
     launch_corners2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
                                roles, h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
@@ -789,10 +832,8 @@ int launch_correct_pixels_t(fbus_ekf_t h, int M, const int32_t* ids, const void*
             launch_pixels_split_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, split,
                                            h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
     }
-    if (h->noise_on) {                  // (split == 0) the NIS kernel with no outputs and no gate: this filter's r_pix (family 15)
-        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
-                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), nullptr,
-                                        nullptr, nullptr, h->d_noise);
+    if (tabled(h)) {                    // (split == 0) the NIS kernel with no outputs and no gate: this filter's r_pix (family 15)
+        tabled_pixels<T, N, D>(h, M, ids, left, right, skip, nullptr, nullptr, nullptr);
     } else if (split == 0 || sizeof(T) != 4) {
         const int roles = team_roles_pixels(h, M);
         launch_pixels2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, roles,
@@ -818,7 +859,7 @@ template <typename T>
 bool frame_meas_resident(const fbus_ekf* h, int kind, int M, int mode)
 {
     const int roles = (kind == MEAS_CORNERS && mode != MODE_STACKED) ? 1 : team_roles_pixels(h, M);
-    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas && !h->noise_on;
+    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas && !tabled(h);
 }
 template <typename T, int N, int D>
 int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
@@ -899,10 +940,8 @@ int launch_correct_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* po
 {
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;
-    if (h->noise_on)
-        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
-                                        (T*)nis, (int*)dof, h->d_gate, h->d_noise);
+    if (tabled(h))
+        tabled_correct<T, N, D>(h, M, ids, pos, quat, mode, skip, nis, dof, h->d_gate);
     else
     launch_correct_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                   h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
@@ -926,10 +965,8 @@ int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const v
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
-    if (h->noise_on)
-        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
-                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
-                                        (int*)dof, h->d_gate, h->d_noise);
+    if (tabled(h))
+        tabled_pixels<T, N, D>(h, M, ids, left, right, skip, nis, dof, h->d_gate);
     else
     launch_pixels2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, h->prm.marker_size,
                                   h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis, (int*)dof,
@@ -951,10 +988,8 @@ int launch_correct_corners_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const 
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_corners_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
-    if (h->noise_on)
-        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
-                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, h->d_gate, h->d_noise);
+    if (tabled(h))
+        tabled_corners<T, N, D>(h, M, ids, left, right, geometry, mode, skip, nis, dof, h->d_gate);
     else
     launch_corners2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
                                    h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied,
@@ -1310,6 +1345,7 @@ int fbus_ekf_destroy(fbus_ekf_t h)
     if (h->d_id2slot) (void)hipFree(h->d_id2slot);
     if (h->d_gate) (void)hipFree(h->d_gate);
     if (h->d_noise) (void)hipFree(h->d_noise);
+    if (h->d_lik) (void)hipFree(h->d_lik);
     if (h->order_ev) (void)hipEventDestroy(h->order_ev);
     (void)fbus_ekf_comm_destroy(h);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -1917,14 +1953,111 @@ int ensure_noise(fbus_ekf_t h)
     h->d_noise = d;
     return FBUS_OK;
 }
+// fbus_params' own row into every filter's table fields: what the likelihood kernels (always the tabled kind) read while the caller has
+// set no table.  Stream-ordered; noise_on is not touched.
+__global__ void noise_own_row_kernel(double* __restrict__ fields, int B, double q0, double q1, double q2, double q3, double r_pos,
+                                     double r_quat, double r_pix)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (size_t)B * FBUS_NOISE_COLS) return;
+    const int c = (int)(i / (size_t)B);
+    fields[i] = c == 0 ? q0 : c == 1 ? q1 : c == 2 ? q2 : c == 3 ? q3 : c == 4 ? r_pos : c == 5 ? r_quat : r_pix;
+}
+int lik_fill(fbus_ekf_t h)
+{
+    int rc = ensure_noise(h);
+    if (rc != FBUS_OK) return rc;
+    const size_t n = (size_t)FBUS_NOISE_COLS * h->B;
+    const fbus_params& p = h->prm;
+    // (r_pix may be unset -- 0 -- on a handle that never runs the pixel rows: those entry points refuse it themselves)
+    hipLaunchKernelGGL(noise_own_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_noise, h->B, p.q_diag[0],
+                       p.q_diag[1], p.q_diag[2], p.q_diag[3], p.r_pos, p.r_quat, p.r_pix);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+// the sums [4][B] as doubles -> the caller's typed arrays (fbus_ekf_loglik_get*; each may be null)
+__global__ void lik_export_kernel(const double* __restrict__ acc, int B, double* __restrict__ ll, int64_t* __restrict__ rows,
+                                  int32_t* __restrict__ applied, int32_t* __restrict__ rejected)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    if (ll) ll[b] = acc[b];
+    if (rows) rows[b] = (int64_t)acc[(size_t)B + b];
+    if (applied) applied[b] = (int32_t)acc[2 * (size_t)B + b];
+    if (rejected) rejected[b] = (int32_t)acc[3 * (size_t)B + b];
+}
 }  // namespace
+
+int fbus_ekf_loglik_enable(fbus_ekf_t h, int on)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_enable: not between graph_begin and graph_end");
+    if (!on) { h->lik_on = false; return FBUS_OK; }
+    if (!h->d_lik) {
+        double* d = nullptr;
+        if (hipMalloc((void**)&d, 4 * (size_t)h->B * sizeof(double)) != hipSuccess)
+            return fail(h, FBUS_ERR_NOMEM, "fbus_ekf_loglik_enable: device allocation");
+        if (hipMemsetAsync(d, 0, 4 * (size_t)h->B * sizeof(double), h->stream) != hipSuccess) {
+            (void)hipFree(d);
+            return fail(h, FBUS_ERR_HIP, "fbus_ekf_loglik_enable: zeroing the sums");
+        }
+        h->d_lik = d;
+    }
+    if (!h->noise_on) {
+        const int rc = lik_fill(h);
+        if (rc != FBUS_OK) return rc;
+    }
+    h->lik_on = true;
+    return FBUS_OK;
+}
+
+int fbus_ekf_loglik_reset(fbus_ekf_t h)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (!h->d_lik) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_reset: fbus_ekf_loglik_enable(h, 1) has not been called");
+    HIP_TRY(h, hipMemsetAsync(h->d_lik, 0, 4 * (size_t)h->B * sizeof(double), h->stream));
+    return FBUS_OK;
+}
+
+int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (!h->d_lik) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_get_dev: fbus_ekf_loglik_enable(h, 1) has not been called");
+    if (!ll && !rows && !applied && !rejected) return FBUS_OK;
+    hipLaunchKernelGGL(lik_export_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->d_lik, h->B, ll, rows, applied,
+                       rejected);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+
+int fbus_ekf_loglik_get(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    if (!h->d_lik) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_get: fbus_ekf_loglik_enable(h, 1) has not been called");
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_get: not between graph_begin and graph_end");
+    const size_t B = (size_t)h->B;
+    std::vector<double> acc(4 * B);
+    HIP_TRY(h, hipMemcpyAsync(acc.data(), h->d_lik, acc.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    for (size_t b = 0; b < B; ++b) {
+        if (ll) ll[b] = acc[b];
+        if (rows) rows[b] = (int64_t)acc[B + b];
+        if (applied) applied[b] = (int32_t)acc[2 * B + b];
+        if (rejected) rejected[b] = (int32_t)acc[3 * B + b];
+    }
+    return FBUS_OK;
+}
 
 int fbus_ekf_set_noise(fbus_ekf_t h, const double* table)
 {
     DeviceGuard guard_(h);
     if (!h) return FBUS_ERR_INVALID;
     if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_noise: not between graph_begin and graph_end");
-    if (!table) { h->noise_on = false; return FBUS_OK; }
+    if (!table) { h->noise_on = false; return h->lik_on ? lik_fill(h) : FBUS_OK; }
     const size_t B = (size_t)h->B;
     std::vector<double> fields((size_t)FBUS_NOISE_COLS * B);
     for (size_t b = 0; b < B; ++b)
@@ -1952,7 +2085,7 @@ int fbus_ekf_set_noise_dev(fbus_ekf_t h, const double* table)
     DeviceGuard guard_(h);
     if (!h) return FBUS_ERR_INVALID;
     if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_noise_dev: not between graph_begin and graph_end");
-    if (!table) { h->noise_on = false; return FBUS_OK; }
+    if (!table) { h->noise_on = false; return h->lik_on ? lik_fill(h) : FBUS_OK; }
     int rc = ensure_noise(h);
     if (rc != FBUS_OK) return rc;
     const size_t n = (size_t)FBUS_NOISE_COLS * h->B;
@@ -2232,7 +2365,7 @@ static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const v
         if (rc != FBUS_OK) return rc;
     }
     // (a noise table: frame by frame, through the per-call kernels that read it)
-    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) && !h->noise_on;
+    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) && !tabled(h);
     if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
     // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
     // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel

@@ -16,6 +16,9 @@
 //  14 1's kernels with per-filter process noise (predict_kernel with NoiseIn; every form of 1's choice, no team form)
 //  15 12's updates with per-filter r_pix / r_pos (NisOut and NoiseIn; the plain updates of a tabled handle run here with null outputs)
 //  16 13's update with per-filter r_pos / r_quat (NisOut and NoiseIn; likewise)
+//  17 15's updates with the innovation log-likelihood sums (NisOut, NoiseIn and LikOut; fbus_ekf_loglik_enable: every pixel / corner update
+//     of the handle runs here while accumulation is on, with the handle's own noise in the table when the caller set none)
+//  18 16's update with the log-likelihood sums (likewise, every pose update)
 // gfx950 only.
 #include <cstdlib>
 #include "ekf_kernels.hpp"
@@ -592,8 +595,84 @@ void launch_correct_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids
                                                                   const unsigned char*, unsigned char*,                \
                                                                   const DevConst<FBUS_TU_T>&, const LaunchPolicy&,     \
                                                                   FBUS_TU_T*, int*, const double*, const double*);
+#elif FBUS_TU_FAMILY == 17
+// family 15's kernel choice with LikOut behind NoiseIn (the filter's log-likelihood sums, lik = [4][B])
+template <typename T, int N, int D>
+void launch_pixels2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
+                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
+                          const double* thr, const double* noise, double* lik)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = mc.n[0] == 0.0 && mc.n[1] == 0.0 && mc.n[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+    const LikOut lo{ lik, B };
+#define FBUS_LAUNCH_PXL(NZF, CAM)                                                                                        \
+    hipLaunchKernelGGL((correct_pixels2_kernel<T, N, 1, NZF, CAM, NisOut<T>, NoiseIn, LikOut>), dim3(tiles), dim3(64), 0, s, recs, B, M, \
+                       ids, left, right, size, 1.0, skip, applied, id2slot, mc, no, ni, lo)
+    if (nz) { if (right) FBUS_LAUNCH_PXL(true, 2); else FBUS_LAUNCH_PXL(true, 1); }
+    else    { if (right) FBUS_LAUNCH_PXL(false, 2); else FBUS_LAUNCH_PXL(false, 1); }
+#undef FBUS_LAUNCH_PXL
+}
+template <typename T, int N, int D>
+void launch_corners2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
+                           double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
+                           const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
+                           const double* noise, double* lik)
+{
+    const int tiles = (B + 63) / 64;
+    const bool nz = vc.nrm[0] == 0.0 && vc.nrm[1] == 0.0 && vc.nrm[2] == 1.0;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+    const LikOut lo{ lik, B };
+#define FBUS_LAUNCH_CRL(NZF)                                                                                             \
+    hipLaunchKernelGGL((correct_corners2_kernel<T, N, 1, NZF, NisOut<T>, NoiseIn, LikOut>), dim3(tiles), dim3(64), 0, s, recs, B, M, ids, \
+                       left, right, geometry, mode, D, size, 1.0, switch_thres, skip, applied, id2slot, mc, vc, vct, no, ni, lo)
+    if (nz) FBUS_LAUNCH_CRL(true); else FBUS_LAUNCH_CRL(false);
+#undef FBUS_LAUNCH_CRL
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_pixels2_lik_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                const FBUS_TU_T*, double, const unsigned char*,        \
+                                                                unsigned char*, const short*, const MeasConst&, FBUS_TU_T*, \
+                                                                int*, const double*, const double*, double*);          \
+    template void launch_corners2_lik_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*, const FBUS_TU_T*, \
+                                                                 const FBUS_TU_T*, int, int, double, double,           \
+                                                                 const unsigned char*, unsigned char*, const short*,   \
+                                                                 const MeasConst&, const VisConst<double>&,            \
+                                                                 const VisConst<FBUS_TU_T>&, FBUS_TU_T*, int*, const double*, \
+                                                                 const double*, double*);
+#elif FBUS_TU_FAMILY == 18
+// family 16's kernel choice with LikOut behind NoiseIn
+template <typename T, int N, int D>
+void launch_correct_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
+                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
+                          const double* thr, const double* noise, double* lik)
+{
+    const int grid = (B + BLOCK - 1) / BLOCK;
+    const bool joint = mode == MODE_STACKED;
+    if (M % 4 == 0 && ((reinterpret_cast<uintptr_t>(ids) | reinterpret_cast<uintptr_t>(pos) | reinterpret_cast<uintptr_t>(quat)) & 15) == 0 &&
+        lp.meas_vec)
+        mode |= MODE_MEAS_VEC;
+    const NisOut<T> no{ nis, dof, thr };
+    const NoiseIn ni{ noise, B };
+    const LikOut lo{ lik, B };
+    constexpr bool SPLIT = sizeof(T) == 8;
+#define FBUS_LAUNCH_CORRECTL(COV, JOINT)                                                                             \
+    hipLaunchKernelGGL((correct_kernel<T, N, D, COV, JOINT, SPLIT, NisOut<T>, NoiseIn, LikOut>), dim3(grid), dim3(BLOCK), 0, s, recs, B, M, \
+                       ids, pos, quat, mode, skip, applied, dc, no, ni, lo)
+    if (joseph) { if (joint) FBUS_LAUNCH_CORRECTL(COV_JOSEPH, true); else FBUS_LAUNCH_CORRECTL(COV_JOSEPH, false); }
+    else        { if (joint) FBUS_LAUNCH_CORRECTL(COV_SIMPLE, true); else FBUS_LAUNCH_CORRECTL(COV_SIMPLE, false); }
+#undef FBUS_LAUNCH_CORRECTL
+}
+#define FBUS_INST(D)                                                                                                   \
+    template void launch_correct_lik_k<FBUS_TU_T, FBUS_TU_N, D>(hipStream_t, FBUS_TU_T*, int, int, const int*,         \
+                                                                const FBUS_TU_T*, const FBUS_TU_T*, int, bool,         \
+                                                                const unsigned char*, unsigned char*,                  \
+                                                                const DevConst<FBUS_TU_T>&, const LaunchPolicy&,       \
+                                                                FBUS_TU_T*, int*, const double*, const double*, double*);
 #else
-#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15 or 16"
+#error "FBUS_TU_FAMILY must be 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17 or 18"
 #endif
 
 FBUS_INST(DIALECT_MATLAB)

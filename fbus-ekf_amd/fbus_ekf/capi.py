@@ -154,6 +154,10 @@ def load_library():
         "fbus_ekf_set_noise": ([H, C.POINTER(C.c_double)], C.c_int),
         "fbus_ekf_set_noise_dev": ([H, vp], C.c_int),
         "fbus_ekf_get_noise": ([H, C.POINTER(C.c_double)], C.c_int),
+        "fbus_ekf_loglik_enable": ([H, C.c_int], C.c_int),
+        "fbus_ekf_loglik_reset": ([H], C.c_int),
+        "fbus_ekf_loglik_get": ([H, vp, vp, vp, vp], C.c_int),
+        "fbus_ekf_loglik_get_dev": ([H, vp, vp, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

@@ -426,6 +426,34 @@ class BatchedFilter:
         self._check(self._lib.fbus_ekf_get_noise(self._h, t.ctypes.data_as(C.POINTER(C.c_double))), "get_noise")
         return t
 
+    # ---- per-filter innovation log-likelihood sums (include/fbus_ekf.h) --------------------------------------------
+    def loglik_enable(self, on=True):
+        """Switch the accumulation of ll = -1/2 (nis + log det S + rows ln 2 pi) over every applied measurement update on or off
+        (the sums are kept when it goes off).  While on the updates take the one-wave routes, as with a noise table."""
+        self._check(self._lib.fbus_ekf_loglik_enable(self._h, 1 if on else 0), "loglik_enable")
+
+    def loglik_reset(self):
+        """Zero the sums (stream-ordered)."""
+        self._check(self._lib.fbus_ekf_loglik_reset(self._h), "loglik_reset")
+
+    def loglik(self, device=False):
+        """(ll float64, rows int64, applied int32, rejected int32), B entries each: numpy arrays (waits for the handle's stream), or
+        with device=True torch tensors on the handle's device, stream-ordered."""
+        B = self.B
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            out = (torch.empty(B, dtype=torch.float64, device=dev), torch.empty(B, dtype=torch.int64, device=dev),
+                   torch.empty(B, dtype=torch.int32, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+            self._keep += list(out)
+            cur = self._order_in(*out)
+            self._check(self._lib.fbus_ekf_loglik_get_dev(self._h, *(self._p(o) for o in out)), "loglik_get_dev")
+            self._order_out(cur)
+            return out
+        out = (np.empty(B, np.float64), np.empty(B, np.int64), np.empty(B, np.int32), np.empty(B, np.int32))
+        self._check(self._lib.fbus_ekf_loglik_get(self._h, *(self._p(o) for o in out)), "loglik_get")
+        return out
+
     def _nis_outputs(self, dev_like):
         if dev_like is not None:
             import torch

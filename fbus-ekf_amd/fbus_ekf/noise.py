@@ -2,7 +2,8 @@
 
 A noise sweep evaluates G hypotheses on one recording in one batch: noise.grid builds the Cartesian product of per-column
 scale factors around a parameter set and assigns it to the filters round-robin (filter b gets hypothesis b mod G), so every
-hypothesis is run by B / G filters.  numpy only.
+hypothesis is run by B / G filters.  noise.best is the other half: the per-hypothesis sum of the filters' innovation log-likelihood
+(BatchedFilter.loglik) and its arg max -- NIS cannot rank hypotheses (it falls as the noise grows), the evidence can.  numpy only.
 """
 import itertools
 
@@ -43,3 +44,21 @@ def grid(params, B, **scales):
     rows = np.array(rows, np.float64).reshape(-1, len(COLUMNS))
     hyp = np.arange(int(B)) % len(rows)
     return rows[hyp], hyp, rows
+
+
+def best(ll, hyp, G):
+    """The evidence of each hypothesis and the winner: total[g] = sum of ll over the filters with hyp == g (a hypothesis no filter
+    runs has total -inf and cannot win), g_best = the first arg max.  Returns (g_best, total (G,) float64)."""
+    ll = np.asarray(ll, np.float64).ravel()
+    hyp = np.asarray(hyp).ravel()
+    G = int(G)
+    if ll.shape != hyp.shape:
+        raise ValueError(f"best: ll has {ll.size} entries, hyp {hyp.size}")
+    if G < 1 or (hyp.size and (hyp.min() < 0 or hyp.max() >= G)):
+        raise ValueError(f"best: hyp must lie in [0, {G})")
+    total = np.full(G, -np.inf, np.float64)
+    for g in range(G):
+        sel = hyp == g
+        if sel.any():
+            total[g] = ll[sel].sum()
+    return int(np.argmax(total)), total

@@ -47,13 +47,17 @@ def pose_from_marker(meas_row, params):
     return p, q, R
 
 
-def replay(engine, imu, image, params, max_frames=None, matlab_reset=True, corners=None, stereo=True):
+def replay(engine, imu, image, params, max_frames=None, matlab_reset=True, corners=None, stereo=True, loglik=False):
     """Runs the recording through `engine` (B = 1).  Returns (states, npredict):
     states[k] = [t, nominal(19), rot(9), P(N*N)] after frame k.
     corners (optional; round 5): the rows of corners.txt that belong to the rows of image.txt (`t id` + 8 left + 8 right undistorted
     normalised corner coordinates, vision.cpp:111-119).  The frame loop, the initialisation and the resets stay as they are (they use
     the marker poses of image.txt, as the reference does), but every MeasureUpdate becomes the north star's: correct() from the corner
-    PIXELS through the flat-port model (engine.correct_pixels; stereo=False: the left camera's rows only)."""
+    PIXELS through the flat-port model (engine.correct_pixels; stereo=False: the left camera's rows only).
+    loglik=True (an engine with loglik_enable / loglik_reset / loglik, i.e. BatchedFilter): the innovation log-likelihood sums of the
+    run as a third element, (ll, rows, applied, rejected) -- zeroed once, behind the initialisation; see replay_windowed."""
+    if loglik and not all(hasattr(engine, m) for m in ("loglik_enable", "loglik_reset", "loglik")):
+        raise ValueError("replay(loglik=True): the engine has no loglik_enable / loglik_reset / loglik")
     imu = np.asarray(imu, float)
     image = np.asarray(image, float)
     if corners is not None:
@@ -68,6 +72,9 @@ def replay(engine, imu, image, params, max_frames=None, matlab_reset=True, corne
     engine.init_gravity_bias(imu[:500, None, 1:4], imu[:500, None, 4:7])
     meas0 = image[0:1, 1:9]
     engine.pose_init(meas0[:, 0].astype(np.int32)[None], meas0[None, :, 1:4], meas0[None, :, 4:8], 0)
+    if loglik:
+        engine.loglik_enable(True)
+        engine.loglik_reset()
     idx = int(np.argmax(imu[:, 0] > image[0, 0]))
     pre_img, n_img = 0.0, 0
     out, npred = [], []
@@ -107,6 +114,10 @@ def replay(engine, imu, image, params, max_frames=None, matlab_reset=True, corne
         nominal, rot, P, _ = engine.get_state()
         out.append(np.concatenate([[cur], nominal.ravel(), rot.ravel(), P.ravel()]).astype(np.float64))
         npred.append(cnt)
+    if loglik:
+        sums = engine.loglik()
+        engine.loglik_enable(False)
+        return np.array(out), np.array(npred), sums
     return np.array(out), np.array(npred)
 
 
@@ -177,7 +188,7 @@ def plan_windows(imu, image, max_frames=None, matlab_reset=True, max_window=64):
     return plan
 
 
-def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, trajectory=False, corners=None, stereo=True):
+def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, trajectory=False, corners=None, stereo=True, loglik=False):
     """The recording through the Matlab loop on `flt` (a BatchedFilter of B filters, every one of them fed the same recording:
     config 1 at batch scale) with each stretch of consecutive frames as ONE launch of the frame-window kernel
     (fbus_ekf_frames_fused_dev) instead of one launch per EKF step.  Returns the number of EKF steps per filter; the state is
@@ -186,7 +197,13 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, tra
     reference's per-frame output (FBUS_EKF.m:201-204, filter.cpp:238-248; fusion_rows() reads it as it reads replay()'s rows),
     from the windows' own trajectory outputs (fbus_ekf_frames_*_traj_dev) and, for a reset frame, flt.snapshot() after the reset.
     corners (optional): the rows of corners.txt for the rows of image, as in replay(corners=...): every MeasureUpdate becomes the
-    north star's, the windows run through fbus_ekf_frames_meas_fused_dev with the corner pixels (stereo=False: left camera only)."""
+    north star's, the windows run through fbus_ekf_frames_meas_fused_dev with the corner pixels (stereo=False: left camera only).
+    loglik=True: the innovation log-likelihood sums are switched on for the run (and off again at its end) and returned as one more,
+    last element of the result: (ll, rows, applied, rejected), numpy arrays of B entries (BatchedFilter.loglik).  The sums are zeroed
+    ONCE, behind the initialisation and in front of the first frame; a filter reset the recording's vision gaps cause (FBUS_EKF.m:168-171)
+    does NOT zero them: the reset frame applies no update and so adds nothing, and the evidence of a noise hypothesis is the sum over
+    every update of the run, whichever side of a gap it lies on.  While the sums are on the windows run frame by frame (the per-call
+    rate, as with a noise table)."""
     import torch
     imu = np.asarray(imu, float)
     image = np.asarray(image, float)
@@ -204,6 +221,9 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, tra
                           np.ascontiguousarray(np.broadcast_to(imu[:500, None, 4:7], (500, B, 3))))
     meas0 = image[0:1, 1:9]
     flt.pose_init(rep(meas0[:, 0].astype(np.int32)[None]), rep(meas0[None, :, 1:4]), rep(meas0[None, :, 4:8]), 0)
+    if loglik:
+        flt.loglik_enable(True)
+        flt.loglik_reset()
     steps = 0
     rows_out = []           # (t, nominal (19,) or (F, 19) device tensor, pdiag ...) of filter 0, read once at the end
     row0 = 0                # the first image row of the next frame (plan_windows consumes the frames in order)
@@ -261,11 +281,16 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, tra
         row0 += sum(len(m) for m in frames)
         steps += int(kcount.sum()) + F
     flt.sync()
+    sums = None
+    if loglik:
+        sums = flt.loglik()
+        flt.loglik_enable(False)
     if not trajectory:
-        return steps
+        return (steps, sums) if loglik else steps
     torch.cuda.synchronize(dev)
     rows = [np.concatenate([t[:, None], nom.double().cpu().numpy(), pd.double().cpu().numpy()], axis=1) for t, nom, pd in rows_out]
-    return steps, (np.concatenate(rows) if rows else np.zeros((0, 20 + N)))
+    rows = np.concatenate(rows) if rows else np.zeros((0, 20 + N))
+    return (steps, rows, sums) if loglik else (steps, rows)
 
 
 def replay_cpp_loop(engine, imu, image, params, max_frames=None, n_init=500):

@@ -166,6 +166,22 @@ public:
         return t;
     }
 
+    // per-filter innovation log-likelihood sums (include/fbus_ekf.h): every measurement update adds ll = -1/2 (nis + log det S + rows ln 2 pi)
+    // while accumulation is on (the one-wave routes, as with a noise table); the sums of a run rank noise hypotheses
+    struct LogLik { std::vector<double> ll; std::vector<int64_t> rows; std::vector<int32_t> applied, rejected; };
+    void loglik_enable(bool on = true) { check(fbus_ekf_loglik_enable(h_, on ? 1 : 0), "loglik_enable"); }
+    void loglik_reset() { check(fbus_ekf_loglik_reset(h_), "loglik_reset"); }
+    LogLik loglik() const
+    {
+        LogLik s;
+        s.ll.resize(batch_); s.rows.resize(batch_); s.applied.resize(batch_); s.rejected.resize(batch_);
+        check(fbus_ekf_loglik_get(h_, s.ll.data(), s.rows.data(), s.applied.data(), s.rejected.data()), "loglik_get");
+        return s;
+    }
+    // ... into device arrays of batch() entries, stream-ordered; each may be null
+    void loglik_dev(double* ll, int64_t* rows, int32_t* applied, int32_t* rejected) const
+    { check(fbus_ekf_loglik_get_dev(h_, ll, rows, applied, rejected), "loglik_get_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

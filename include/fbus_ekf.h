@@ -107,7 +107,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  * fbus_ekf_abi_version() / fbus_params_size() once after loading and compare; the Python mirror does.)
  *   8  fbus_ekf_set_gate, fbus_ekf_correct_nis[_dev], fbus_ekf_correct_pixels_nis[_dev], fbus_ekf_correct_corners_nis[_dev]
  *      (struct unchanged); added under 8 without a bump: fbus_ekf_set_noise[_dev], fbus_ekf_get_noise (per-filter noise; no
- *      existing meaning changed -- callers detect the feature by the symbol)
+ *      existing meaning changed -- callers detect the feature by the symbol); likewise fbus_ekf_loglik_enable / _reset / _get /
+ *      _get_dev (per-filter innovation log-likelihood sums; off by default, nothing routed differently until switched on)
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -546,6 +547,40 @@ int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, co
 int fbus_ekf_set_noise(fbus_ekf_t h, const double* table);      /* host, B x 7 row-major; NULL = no table (back to fbus_params) */
 int fbus_ekf_set_noise_dev(fbus_ekf_t h, const double* table);  /* device, B x 7 row-major, stream-ordered; NULL = no table      */
 int fbus_ekf_get_noise(fbus_ekf_t h, double* table);            /* host, B x 7; FBUS_ERR_INVALID when no table is set          */
+
+/* ---- per-filter innovation log-likelihood (the evidence of a noise hypothesis) -------------------------------------------
+ * NIS cannot rank noise hypotheses: it falls as R or the prior grow.  The quantity that can is the Gaussian log-likelihood of each
+ * applied update's innovation,
+ *     ll = -1/2 ( r' S^-1 r + log det S + rows ln 2 pi ),      S = H P H' + R,
+ * summed over a run.  The handle owns a per-filter accumulator, fed by EVERY measurement update it launches while accumulation is on
+ * (correct*, correct*_nis*, host-pointer, _dev and _async forms, frame*, frames*, captured graphs):
+ *   * an update that is applied:        ll += -1/2 (nis + log det S + rows ln 2 pi),  rows += rows of S,  applied += 1
+ *   * an update the gate rejects:       rejected += 1, nothing else
+ *   * a skipped filter, or one with no usable marker (dof = 0): nothing
+ * all in double for both record types (nis is the double the NIS kernels hold before its cast to the record type; log det S =
+ * log det R + log det(I + P_JJ Lam) from the Cholesky pivots the update has anyway, R from the filter's own table row when a noise
+ * table is set).  `rows` is the row count of S.  It equals the reported dof everywhere EXCEPT the Matlab dialect's pose rows: there the
+ * quaternion residual is zeroed but its four rows stay in S (MeasureUpdate.m:84-88), so rows = 7 and dof = 3 per used marker, and
+ * log det R counts all seven.
+ * STORAGE: one device buffer, allocated at the first enable(h, 1) and neither moved nor freed before fbus_ekf_destroy, so a captured
+ * graph accumulates at every replay.  A graph captured while accumulation was on keeps its kernels: it goes on accumulating after
+ * enable(h, 0).  enable and get are refused between graph_begin and graph_end; reset and get_dev are stream-ordered and may be captured.
+ * ROUTES while on: as with a noise table (above) -- the one-wave-per-tile kernels only, fbus_ekf_set_team ignored, fbus_ekf_launch_info
+ * reports ROLES_* = 1, TEAM_FRAMES = 0, MEAS_SPLIT = 0, the fused frame and window entry points run frame by frame (predict_n + the
+ * per-call update).  The updates run the tabled kernels; without a noise table the handle writes fbus_params' own values into its table
+ * buffer (fbus_ekf_get_noise still answers "no table", predict keeps its untabled kernels), so records, applied, nis and dof equal the
+ * same call with accumulation off on its one-wave route bit for bit, except fp64 C++-dialect stacked pose updates (nominal state within
+ * ~2e-15, as with a table).  Off (the default) nothing is routed differently.
+ * fbus_ekf_loglik_enable   on != 0: accumulate from the next launch on (first time: allocate and zero); on == 0: stop, keep the sums
+ * fbus_ekf_loglik_reset    zero the sums, stream-ordered on the handle's stream
+ * fbus_ekf_loglik_get      the sums into host arrays of B entries each (any may be NULL); waits for the stream
+ * fbus_ekf_loglik_get_dev  the same into device arrays, stream-ordered
+ * All four return FBUS_ERR_INVALID (1) for a NULL handle; get / get_dev / reset before the first enable(h, 1) are FBUS_ERR_INVALID with
+ * a fbus_ekf_last_error text. */
+int fbus_ekf_loglik_enable(fbus_ekf_t h, int on);
+int fbus_ekf_loglik_reset(fbus_ekf_t h);
+int fbus_ekf_loglik_get(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
+int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
