@@ -1,16 +1,10 @@
 #!/usr/bin/env python3
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
-The library is 57 translation units compiled in parallel and linked into one shared object:
+The library is len(units()) translation units compiled in parallel and linked into one shared object:
   fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose)
-  kernels_tu.hip x 56                   one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
-                                        float: predict / correct / frame / frames / team / meas / fmeas / msplit / framest / fmeast
-                                        / measnis / correctnis / prednz / measnz / correctnz / measlik / correctlik (17 x 2 = 34; framest / fmeast: the windows
-                                        with per-frame trajectory rows, measnis / correctnis: the pixel / corner and the pose updates with
-                                        the NIS output and the gate, prednz / measnz / correctnz: predict and the NIS updates with
-                                        per-filter noise, measlik / correctlik: the tabled NIS updates with the log-likelihood sums),
-                                        double: predict / correct / frame / meas / measnis / correctnis / prednz / measnz / correctnz /
-                                        measlik / correctlik (11 x 2 = 22; len(units()) == 57 with fbus_ekf.hip)
+  kernels_tu.hip, once per unit         one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
+                                        every row of FAMILIES for float, the rows marked fp64 for double, each for N = 18 and N = 15
 Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.
   python build.py [--force] [--only f32_18_correct,...] [--jobs N]
 FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds (A/B of differently built kernels via FBUS_EKF_LIB).
@@ -27,33 +21,41 @@ HEADERS = [os.path.join(CSRC, h) for h in ("ekf_kernels.hpp", "ekf_device.hpp", 
 OUT = os.environ.get("FBUS_OUT") or os.path.join(HERE, "lib", "libfbus_ekf.so")   # FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds
 OBJDIR = os.environ.get("FBUS_OBJDIR") or os.path.join(os.path.dirname(OUT), "obj" if not os.environ.get("FBUS_OUT") else
                                                        "obj_" + os.path.splitext(os.path.basename(OUT))[0])
-FAMILIES = {"predict": 1, "correct": 2, "frame": 3, "frames": 5, "team": 6, "meas": 7, "fmeas": 8, "msplit": 9, "framest": 10, "fmeast": 11, "measnis": 12, "correctnis": 13,
-            "prednz": 14, "measnz": 15, "correctnz": 16, "measlik": 17, "correctlik": 18}
-# Per-family scheduler choice (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
+MAX_ILP = "-mllvm -amdgpu-sched-strategy=max-ilp"
+# One row per kernel family (kernels_tu.hip lists what each number holds):
+#   name: (FBUS_TU_FAMILY, the family whose flags it is built with, built for fp64 records too)
+# An extension family (a kernel of another family with a trailing pack) is built with the flags of the family it extends, both record
+# types.  fp64 has one fused frame kernel (family "frame": frame2_kernel) and runs the windows frame by frame.
+FAMILIES = {
+    "predict":    (1,  "predict", True),
+    "correct":    (2,  "correct", True),
+    "frame":      (3,  "frame",   True),
+    "frames":     (5,  "frames",  False),
+    "team":       (6,  "team",    False),
+    "meas":       (7,  "meas",    True),
+    "fmeas":      (8,  "fmeas",   False),
+    "msplit":     (9,  "msplit",  False),
+    "framest":    (10, "frames",  False),   # the windows with per-frame trajectory rows
+    "fmeast":     (11, "fmeas",   False),
+    "measnis":    (12, "meas",    True),    # the pixel / corner and the pose updates with the NIS output and the gate
+    "correctnis": (13, "correct", True),
+    "prednz":     (14, "predict", True),    # predict and the NIS updates with per-filter noise
+    "measnz":     (15, "meas",    True),
+    "correctnz":  (16, "correct", True),
+    "measlik":    (17, "meas",    True),    # the tabled NIS updates with the log-likelihood sums
+    "correctlik": (18, "correct", True),
+}
+# Per-family scheduler choice, fp32 units (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
 # max-ILP strategy of the AMDGPU machine scheduler shortens the per-call kernels, where one wave per SIMD has nothing
 # but its own independent instructions to cover dependent-issue stalls (predict 13.4 -> 13.05 us, stacked correct
 # 23.0 -> 21.6 us, headline +3.5 %), and lengthens the fused frame kernel (-2.8 %: more live registers, more
-# v_accvgpr traffic), which therefore keeps the default strategy.
-FAMILY_FLAGS = {"predict": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
-                "correct": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
-                "frame": os.environ.get("FBUS_FRAME_FLAGS", "").split(), "frames": os.environ.get("FBUS_FRAMES_FLAGS", "").split(),
-                "team": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"], "meas": os.environ.get("FBUS_MEAS_FLAGS", "").split(),
-                "fmeas": os.environ.get("FBUS_FMEAS_FLAGS", "").split(), "msplit": os.environ.get("FBUS_MSPLIT_FLAGS", "").split(),
-                # the trajectory windows (families 10 / 11) are built with the flags of the windows they extend
-                "framest": os.environ.get("FBUS_FRAMES_FLAGS", "").split(), "fmeast": os.environ.get("FBUS_FMEAS_FLAGS", "").split(),
-                # the NIS updates (families 12 / 13) with the flags of the updates they extend, both record types
-                "measnis": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnis": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
-                # the per-filter noise kernels (families 14-16) with the flags of the kernels they extend, both record types
-                "prednz": os.environ.get("FBUS_PREDICT_FLAGS", "-mllvm -amdgpu-sched-strategy=max-ilp").split(),
-                "measnz": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctnz": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"],
-                # the log-likelihood kernels (families 17 / 18) with the flags of the tabled kernels they extend, both record types
-                "measlik": os.environ.get("FBUS_MEAS_FLAGS", "").split(), "correctlik": ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]}
+# v_accvgpr traffic), which therefore keeps the default strategy.  FBUS_<FAMILY>_FLAGS overrides where listed.
+F32_FLAGS = {"predict": os.environ.get("FBUS_PREDICT_FLAGS", MAX_ILP), "correct": MAX_ILP, "team": MAX_ILP,
+             **{fam: os.environ.get("FBUS_" + fam.upper() + "_FLAGS", "") for fam in ("frame", "frames", "meas", "fmeas", "msplit")}}
 # fp64 units.  meas (correct_pixels2 / correct_corners2 <double>, 512 registers + scratch): the max-memory-clause strategy leaves them
-# 28-136 bytes of scratch instead of 136-340 and is 4-11 % faster (profiles/r05_f64_sched.txt); FBUS_F64_FLAGS_<FAMILY> overrides
-F64_FAMILY_FLAGS = {fam: os.environ.get("FBUS_F64_FLAGS_" + fam.upper(),
-                                        "-mllvm -amdgpu-sched-strategy=max-memory-clause" if fam in ("meas", "measnis", "measnz", "measlik") else "").split()
-                    for fam in ("predict", "correct", "frame", "meas", "measnis", "correctnis", "prednz", "measnz", "correctnz", "measlik",
-                                "correctlik")}
+# 28-136 bytes of scratch instead of 136-340 and is 4-11 % faster (profiles/r05_f64_sched.txt); FBUS_F64_FLAGS_<FAMILY> overrides, by
+# the unit's own family name
+F64_FLAGS = {"meas": "-mllvm -amdgpu-sched-strategy=max-memory-clause"}
 TYPES = {"f32": "float", "f64": "double"}
 
 
@@ -69,15 +71,15 @@ def units():
     out = [("main", os.path.join(CSRC, "fbus_ekf.hip"), [])]
     for tn, t in TYPES.items():
         for n in (18, 15):
-            for fam, code in FAMILIES.items():
-                if fam in ("frames", "team", "fmeas", "msplit", "framest", "fmeast") and tn == "f64":
-                    continue                    # fp64: one fused frame kernel (family "frame": frame2_kernel), windows frame by frame
+            for fam, (code, like, f64) in FAMILIES.items():
+                if tn == "f64" and not f64:
+                    continue
+                # fp32: the family's flags -- the fp64 kernels sit at the 512-register limit and spill more under max-ILP
+                flags = F32_FLAGS[like] if tn == "f32" else os.environ.get("FBUS_F64_FLAGS_" + fam.upper(), F64_FLAGS.get(like, ""))
+                if os.environ.get("FBUS_NO_FAMILY_FLAGS"):      # the flag-free A/B baseline -- for BOTH record types (advisor, round 5)
+                    flags = ""
                 out.append((f"{tn}_{n}_{fam}", os.path.join(CSRC, "kernels_tu.hip"),
-                            [f"-DFBUS_TU_T={t}", f"-DFBUS_TU_N={n}", f"-DFBUS_TU_FAMILY={code}"] +
-                            # fp32 only: the fp64 kernels sit at the 512-register limit and spill more under max-ILP
-                            # FBUS_NO_FAMILY_FLAGS: the flag-free A/B baseline -- for BOTH record types (advisor, round 5)
-                            ([] if (os.environ.get("FBUS_NO_FAMILY_FLAGS") or tn != "f32") else FAMILY_FLAGS[fam]) +
-                            (F64_FAMILY_FLAGS.get(fam, []) if (tn == "f64" and not os.environ.get("FBUS_NO_FAMILY_FLAGS")) else [])))
+                            [f"-DFBUS_TU_T={t}", f"-DFBUS_TU_N={n}", f"-DFBUS_TU_FAMILY={code}"] + flags.split()))
     return out
 
 

@@ -1265,6 +1265,13 @@ __device__ __forceinline__ void noise_pose(DevConst<T>& dc, int b, const NO&... 
     dc.r_quat = (T)noise_ld(n, NOISE_RQUAT, b);
 }
 
+// Per-frame trajectory rows of a window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): what FBUS_EKF.m:201-204 appends
+// to EKFResults and filter.cpp:238-248 writes to fusion.txt after every frame, written by the window kernels straight from the resident
+// registers.  Row r = f * B + b: nom[r][19] (API order p v q ba bg g, the index map of unpack_kernel), pdiag[r][N] = diag(P), applied[r]
+// (what fbus_ekf_get_applied reports after frame f alone).  Each pointer may be null.
+template <typename T>
+struct TrajOut { T* nom; T* pdiag; unsigned char* applied; };
+
 // ---- innovation log-likelihood (fbus_ekf_loglik_*): a trailing kernel parameter LikOut behind (NisOut, NoiseIn) -- the likelihood kernels
 // are always the tabled kind (kernels_tu.hip families 17 / 18).  acc: the handle's sums as fp64 fields [4][B] (ll, rows of S, applied,
 // rejected; the counts are exact in a double far beyond any run); lane b owns filter b and updates its four entries with ordinary loads

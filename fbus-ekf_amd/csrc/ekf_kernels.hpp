@@ -1035,12 +1035,7 @@ frame_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, co
 // window.  Same device functions, same order of operations per filter as F fused frames (bit-identical results).
 struct FrameCounts { unsigned char k[FBUS_MAX_WINDOW_FRAMES]; };      // IMU samples in front of each frame
 
-// Per-frame trajectory rows of a window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): what FBUS_EKF.m:201-204 appends
-// to EKFResults and filter.cpp:238-248 writes to fusion.txt after every frame, written by the window kernels straight from the resident
-// registers.  Row r = f * B + b: nom[r][19] (API order p v q ba bg g, the index map of unpack_kernel), pdiag[r][N] = diag(P), applied[r]
-// (what fbus_ekf_get_applied reports after frame f alone).  Each pointer may be null.
-template <typename T>
-struct TrajOut { T* nom; T* pdiag; unsigned char* applied; };
+// (TrajOut, the per-frame trajectory rows of a window: ekf_device.hpp, beside the other pack types the launchers pass)
 // record element of API nominal element i (TileIO::nom_elem, as a constant expression: the rows index registers)
 template <int N>
 __host__ __device__ constexpr int api_nom_elem(int i)

@@ -1,9 +1,21 @@
-// ekf_launch.hpp -- host-callable launchers of the four large kernel families.
+// ekf_launch.hpp -- host-callable launchers of the large kernel families.
 //
 // The library is built from several translation units so that the kernels compile in parallel (and a kernel under
 // work rebuilds in seconds): kernels_tu.hip is compiled once per (scalar type, state size, family) with
 // -DFBUS_TU_T / -DFBUS_TU_N / -DFBUS_TU_FAMILY and holds the explicit instantiations of the function templates
 // declared here (both dialects); fbus_ekf.hip (handle, C ABI, the small kernels) only sees these declarations.
+//
+// A launcher whose kernel takes a trailing parameter pack takes the same pack (`X... x`) and hands it on: one launcher and one
+// kernel choice per kernel, whatever the pack.  The packs that are instantiated (each in a unit of its own, listed at the top of
+// kernels_tu.hip; any other pack links as an undefined symbol):
+//   launch_predict_k                                          ()  (NoiseIn)
+//   launch_correct_k, launch_pixels2_k, launch_corners2_k     ()  (NisOut<T>)  (NisOut<T>, NoiseIn)  (NisOut<T>, NoiseIn, LikOut)
+//   launch_frames_k, launch_frame_meas_k                      ()  (TrajOut<T>)
+// NisOut<T>{nis, dof, thr}: nis [B] in T and dof [B] on the device (each may be null), thr: the handle's gate table on the device (null
+// for the pixel / corner updates, a table of +inf for the pose update: no gate; its length was checked against the largest dof).
+// NoiseIn{noise, B}: the handle's table [FBUS_NOISE_COLS][B] (fbus_ekf_set_noise).  LikOut{lik, B}: the handle's sums [4][B] (ll, rows,
+// applied, rejected as doubles; fbus_ekf_loglik_enable).  TrajOut<T>{nominal, pdiag, applied}: frame f's trajectory row [f][B][.] goes
+// to each non-null output.  With a pack the updates run one wave per tile.
 #pragma once
 #include "ekf_device.hpp"
 #include "vision_device.hpp"
@@ -26,36 +38,24 @@ struct LaunchPolicy {
 
 // K == 1: the streamed per-call kernel (`policy`: 0 = nt loads and stores, 1 = default-policy loads, 2 = default loads
 // and stores); K > 1: predict_n, K samples per launch with the record resident in registers
-template <typename T, int N, int D>
+template <typename T, int N, int D, typename... X>
 void launch_predict_k(hipStream_t s, T* recs, int B, int K, int policy, const T* accel, const T* gyro, const T* dt,
-                      int dt_stride, const DevConst<T>& dc, const LaunchPolicy& lp);
+                      int dt_stride, const DevConst<T>& dc, const LaunchPolicy& lp, X... x);
 
-template <typename T, int N, int D>
+// (with a pack fp32 never runs the row-split form)
+template <typename T, int N, int D, typename... X>
 void launch_correct_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode,
-                      bool joseph, const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp);
-// the same update with the NIS output and the gate (kernels_tu.hip family 13: correct_kernel with NisOut; fp32 never row-split):
-// nis [B] in T, dof [B] (device, each may be null), thr: the handle's gate table on the device
-template <typename T, int N, int D>
-void launch_correct_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
-                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
-                          const double* thr);
+                      bool joseph, const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, X... x);
 
 template <typename T, int N, int D>
 void launch_frame_k(hipStream_t s, T* recs, int B, int K, const T* accel, const T* gyro, const T* dt, int dt_stride,
                     int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
                     const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp);
-
 // a window of F frames in one launch (fp32; not (Joseph, nearest)); kcount: F host bytes
-template <typename T, int N, int D>
+template <typename T, int N, int D, typename... X>
 void launch_frames_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
                      const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
-                     const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc);
-// the same window writing frame f's trajectory row [f][B][.] to each non-null output (kernels_tu.hip family 10: frames_kernel with TrajOut)
-template <typename T, int N, int D>
-void launch_frames_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
-                          const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
-                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, T* out_nominal, T* out_pdiag,
-                          unsigned char* out_applied);
+                     const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, X... x);
 
 // ---- team kernels (ekf_team.hpp): several waves per 64-filter tile, fp32 only -------------------------------------------
 // roles: waves per tile (predict 2..4, predict_n always 4); policy as in launch_predict_k
@@ -87,88 +87,33 @@ struct MeasConst {
                                     // a1, a1^2, 1 - a1^2, 1 - a0^2, d_air, d_glass a0, (d_air + d_glass a0) / a1, 0
     const double* mkc;              // [FBUS_MAX_MARKERS][MKC_STRIDE]
 };
-
-// roles: waves per 64-filter tile (1, 2 or 4: the markers of a filter divided among them); right == nullptr: left camera only.
+// roles: waves per 64-filter tile (1, 2 or 4: the markers of a filter divided among them; with a pack always 1); right == nullptr: left
+// camera only; r_pix: ignored with a NoiseIn.
 // The kernel does not depend on the dialect (the pixel rows have no quaternion part); D only keeps the instantiation macro uniform.
-template <typename T, int N, int D>
+template <typename T, int N, int D, typename... X>
 void launch_pixels2_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int roles, double size,
-                      double r_pix, const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc);
+                      double r_pix, const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, X... x);
 // (round 5) the same update with the TAIL divided between the waves of a tile (ekf_meas_split.hpp): roles = 2 or 4 waves per tile
 // (launches below half / a quarter of the chip's SIMDs in tiles).  fp32 records, square port only -- the caller checks.
 template <typename T, int N, int D>
 void launch_pixels_split_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int roles, double size,
                            double r_pix, const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc);
-// correct() from stereo corners, round-4 kernel: nearest marker (roles forced to 1) or stacked; dialect: hysteresis of the nearest mode
-template <typename T, int N, int D>
+// correct() from stereo corners, round-4 kernel: nearest marker (roles forced to 1) or stacked; dialect: hysteresis of the nearest mode;
+// roles and r_pos as launch_pixels2_k's roles and r_pix
+template <typename T, int N, int D, typename... X>
 void launch_corners2_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
                        int roles, double size, double r_pos, double switch_thres, const unsigned char* skip, unsigned char* applied,
-                       const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct);
-// the two updates above with the NIS output and the gate (kernels_tu.hip family 12: NisOut, one wave per tile): nis [B] in T and dof [B]
-// (device, each may be null); thr: the handle's gate table on the device (null: no gate; its length was checked against the largest dof)
-template <typename T, int N, int D>
-void launch_pixels2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size, double r_pix,
-                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
-                          const double* thr);
-template <typename T, int N, int D>
-void launch_corners2_nis_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
-                           double size, double r_pos, double switch_thres, const unsigned char* skip, unsigned char* applied,
-                           const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof,
-                           const double* thr);
-
-// ---- per-filter noise (fbus_ekf_set_noise): the one-wave forms with a trailing NoiseIn, noise = the handle's table [FBUS_NOISE_COLS][B] ----
-// the kernel choice of launch_predict_k (kernels_tu.hip family 14: predict_kernel with NoiseIn)
-template <typename T, int N, int D>
-void launch_predict_noise_k(hipStream_t s, T* recs, int B, int K, int policy, const T* accel, const T* gyro, const T* dt,
-                            int dt_stride, const DevConst<T>& dc, const LaunchPolicy& lp, const double* noise);
-// the kernel choice of launch_correct_nis_k (family 16: correct_kernel with NisOut and NoiseIn); the plain update passes null nis / dof and a
-// table of +inf for thr
-template <typename T, int N, int D>
-void launch_correct_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
-                            const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
-                            const double* thr, const double* noise);
-// the kernel choice of launch_pixels2_nis_k / launch_corners2_nis_k (family 15: NisOut and NoiseIn); the plain updates pass null nis / dof / thr
-template <typename T, int N, int D>
-void launch_pixels2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
-                            const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
-                            const double* thr, const double* noise);
-template <typename T, int N, int D>
-void launch_corners2_noise_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
-                             double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
-                             const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
-                             const double* noise);
-
-// ---- innovation log-likelihood (fbus_ekf_loglik_enable): the tabled one-wave forms with a trailing LikOut, lik = the handle's sums [4][B]
-// (ll, rows, applied, rejected as doubles).  The kernel choice of the launchers above (kernels_tu.hip families 17 / 18); the plain
-// updates pass null nis / dof and the tabled routes' "no gate" thr.
-template <typename T, int N, int D>
-void launch_correct_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
-                          const unsigned char* skip, unsigned char* applied, const DevConst<T>& dc, const LaunchPolicy& lp, T* nis, int* dof,
-                          const double* thr, const double* noise, double* lik);
-template <typename T, int N, int D>
-void launch_pixels2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, double size,
-                          const unsigned char* skip, unsigned char* applied, const short* id2slot, const MeasConst& mc, T* nis, int* dof,
-                          const double* thr, const double* noise, double* lik);
-template <typename T, int N, int D>
-void launch_corners2_lik_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* left, const T* right, int geometry, int mode,
-                           double size, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
-                           const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, T* nis, int* dof, const double* thr,
-                           const double* noise, double* lik);
+                       const short* id2slot, const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, X... x);
 
 // ---- one camera frame with the north star's MeasureUpdate in one launch (ekf_meas.hpp::frame_meas_kernel; fp32) -----------------
 // kind: corner pixels (geometry / mode ignored; right == nullptr: left camera) or stereo corners (geometry, mode as correct_corners)
 enum { MEAS_PIXELS = 0, MEAS_CORNERS = 1 };
-// F = 1: one frame of kcount[0] predicts; F > 1: a window of F frames in one launch (kcount: F host bytes; measurements [F][B][M]...)
-template <typename T, int N, int D>
+// F = 1: one frame of kcount[0] predicts; F > 1: a window of F frames in one launch (kcount: F host bytes; measurements [F][B][M]...);
+// with TrajOut a window only
+template <typename T, int N, int D, typename... X>
 void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt, int dt_stride, int kind,
                          int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size, double r_meas,
                          double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
-                         const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd);
-// a window (F > 1) of such frames writing frame f's trajectory row to each non-null output (kernels_tu.hip family 11: frame_meas_kernel with TrajOut)
-template <typename T, int N, int D>
-void launch_frame_meas_traj_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt,
-                              int dt_stride, int kind, int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size,
-                              double r_meas, double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
-                              const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd, T* out_nominal,
-                              T* out_pdiag, unsigned char* out_applied);
+                         const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd, X... x);
 
 }  // namespace fbus

@@ -374,47 +374,49 @@ int launch_predict_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, c
     if (h->predict_policy_force >= 0) policy = h->predict_policy_force;
     h->records_warm = false;
     const int roles = team_roles_predict(h, K);
+    const auto one_wave = [&](auto... x) {
+        launch_predict_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                  dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp, x...);
+    };
     if constexpr (sizeof(T) == 4) {
         if (roles > 1)
             launch_predict_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, roles, policy, (const T*)accel, (const T*)gyro,
                                            (const T*)dt, dt_per_filter ? 1 : 0, make_dc<T>(h));
     }
-    if (h->noise_on)                // (roles == 1) the same kernel choice with this filter's q (kernels_tu.hip family 14)
-        launch_predict_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                        dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp, h->d_noise);
-    else if (roles <= 1 || sizeof(T) != 4)
-        launch_predict_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                  dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp);
+    if (h->noise_on) one_wave(NoiseIn{ h->d_noise, h->B });     // (roles == 1) the same kernel choice with this filter's q
+    else if (roles <= 1 || sizeof(T) != 4) one_wave();
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
 
-// the tabled updates: the noise kernels (families 15 / 16), or the likelihood kernels (17 / 18) while the sums are on
-template <typename T, int N, int D>
-void tabled_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, void* nis,
-                    int32_t* dof, const double* thr)
+// Outputs of an _nis call: nis [B] in the record type and dof [B] on the device, each may be null
+struct NisDst { void* nis; int32_t* dof; };
+// One measurement update with the pack that the handle and the call ask for; `go(x...)` launches it.  While the likelihood sums are on:
+// NisOut, NoiseIn, LikOut; on a tabled handle: NisOut, NoiseIn; an _nis call (nis != nullptr) otherwise: NisOut; the plain update: none.
+// An _nis call gates with the handle's table; the plain update of a tabled handle runs the NIS kernel with no outputs and `no_gate`.
+template <typename T, typename GO>
+void with_update_pack(fbus_ekf_t h, const NisDst* nis, const double* no_gate, GO go)
 {
-    if (h->lik_on)
-        launch_correct_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                      h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
-                                      (T*)nis, (int*)dof, thr, h->d_noise, h->d_lik);
-    else
-        launch_correct_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                        h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
-                                        (T*)nis, (int*)dof, thr, h->d_noise);
+    const NisOut<T> no = nis ? NisOut<T>{ (T*)nis->nis, (int*)nis->dof, h->d_gate } : NisOut<T>{ nullptr, nullptr, no_gate };
+    const NoiseIn ni{ h->d_noise, h->B };
+    if (h->lik_on) go(no, ni, LikOut{ h->d_lik, h->B });
+    else if (tabled(h)) go(no, ni);
+    else if (nis) go(no);
+    else go();
 }
 template <typename T, int N, int D>
 int launch_correct_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
-                     const uint8_t* skip)
+                     const uint8_t* skip, const NisDst* nis = nullptr)
 {
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;   // false: written through (sc1), the next predict streams them like any other
-    if (tabled(h))                              // the NIS kernel with no outputs and the +inf table: this filter's r_pos / r_quat
-        tabled_correct<T, N, D>(h, M, ids, pos, quat, mode, skip, nullptr, nullptr, h->d_noise + (size_t)FBUS_NOISE_COLS * h->B);
-    else
-    launch_correct_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                  h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp);
+    // (the pose kernel always reads a gate table: "no gate" is the row of +inf behind the noise table)
+    const double* no_gate = tabled(h) ? h->d_noise + (size_t)FBUS_NOISE_COLS * h->B : nullptr;
+    with_update_pack<T>(h, nis, no_gate, [&](auto... x) {
+        launch_correct_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                  h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp, x...);
+    });
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -496,61 +498,42 @@ int launch_frame(fbus_ekf_t h, int K, const void* accel, const void* gyro, const
     DISPATCH(h, launch_frame_t, h, K, accel, gyro, dt, per, M, ids, pos, quat, mode, skip);
 }
 
-template <typename T, int N, int D>
-int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
-                    int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
-{
-    if constexpr (sizeof(T) == 4) {
-        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
-        h->records_warm = true;
-        if (team_frames(h, mode))
-            launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                          dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                          (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
-        else
-        launch_frames_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                 dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                 h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
-        timing_end(h, ev);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return FBUS_OK;
-}
-
-int launch_frames(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
-                  const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
-{
-    DISPATCH(h, launch_frames_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip);
-}
-
 // Output slices of a trajectory window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): [nframes][B][19], [nframes][B][N],
 // [nframes][B]; any may be null
 struct TrajDst { void* nom; void* pdiag; uint8_t* applied; };
 
-// the window of frames_kernel with frame f's rows written from its registers (frames_kernel with TrajOut; the caller has checked that the
-// one-wave resident kernel applies: fp32, not (Joseph, nearest), not the team form)
+// tj: the window with frame f's rows written from its registers (frames_kernel with TrajOut; the caller has checked that the one-wave
+// resident kernel applies: fp32, not (Joseph, nearest), not the team form)
 template <typename T, int N, int D>
-int launch_frames_traj_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
-                         int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
-                         const TrajDst& tj)
+int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+                    int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                    const TrajDst* tj)
 {
     if constexpr (sizeof(T) == 4) {
         const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
         h->records_warm = true;
-        launch_frames_traj_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                      dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                      h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h),
-                                      (T*)tj.nom, (T*)tj.pdiag, tj.applied);
+        const auto one_wave = [&](auto... x) {
+            launch_frames_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                     dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                     h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), x...);
+        };
+        if (tj) one_wave(TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied });
+        else if (team_frames(h, mode))
+            launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                          dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                          (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
+        else one_wave();
         timing_end(h, ev);
         HIP_TRY(h, hipGetLastError());
         return FBUS_OK;
     }
-    return fail(h, FBUS_ERR_UNSUPPORTED, "frames_fused_traj: no resident fp64 window");
+    return tj ? fail(h, FBUS_ERR_UNSUPPORTED, "frames_fused_traj: no resident fp64 window") : FBUS_OK;
 }
-int launch_frames_traj(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
-                       const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, const TrajDst& tj)
+
+int launch_frames(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
+                  const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, const TrajDst* tj = nullptr)
 {
-    DISPATCH(h, launch_frames_traj_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip, tj);
+    DISPATCH(h, launch_frames_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip, tj);
 }
 
 
@@ -768,50 +751,35 @@ int do_pose_init(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const
     DISPATCH(h, pose_init_t, h, M, ids, pos, quat, what, mask, out7);
 }
 
+// the pixel update with the handle's and the call's pack; roles: waves per tile of the plain update
 template <typename T, int N, int D>
-void tabled_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
-                    void* nis, int32_t* dof, const double* thr)
+void update_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int roles, const uint8_t* skip,
+                   const NisDst* nis)
 {
-    if (h->lik_on)
-        launch_corners2_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                       h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
-                                       make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, thr, h->d_noise, h->d_lik);
-    else
-        launch_corners2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                         h->prm.marker_size, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied, h->d_id2slot,
-                                         make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, thr, h->d_noise);
-}
-template <typename T, int N, int D>
-void tabled_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip, void* nis, int32_t* dof,
-                   const double* thr)
-{
-    if (h->lik_on)
-        launch_pixels2_lik_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
-                                      h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
-                                      (int*)dof, thr, h->d_noise, h->d_lik);
-    else
-        launch_pixels2_noise_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right,
-                                        h->prm.marker_size, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis,
-                                        (int*)dof, thr, h->d_noise);
+    with_update_pack<T>(h, nis, nullptr, [&](auto... x) {
+        launch_pixels2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, roles,
+                                  h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), x...);
+    });
 }
 template <typename T, int N, int D>
 int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
-                             int mode, const uint8_t* skip)
+                             int mode, const uint8_t* skip, const NisDst* nis = nullptr)
 {
     // the kernel fetches a slot's image points with 16-byte loads (a slot is 32 / 48 contiguous bytes): the arrays must start on a
     // 16-byte boundary -- any allocation does; a view offset by one to three elements does not and is refused, not read unaligned
     if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_corners: left / right must be 16-byte aligned device pointers");
+        return fail(h, FBUS_ERR_INVALID, std::string(nis ? "fbus_ekf_correct_corners_nis" : "fbus_ekf_correct_corners") +
+                                         ": left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     // triangulation and fold in double, non-cancelling update (ekf_meas.hpp); records written through (sc1) as correct_kernel's
     h->records_warm = h->warm_after_correct;
-    const int roles = mode == MODE_STACKED ? team_roles_pixels(h, M) : 1;
-    if (tabled(h))                      // the NIS kernel with no outputs and no gate: this filter's r_pos (kernels_tu.hip family 15)
-        tabled_corners<T, N, D>(h, M, ids, left, right, geometry, mode, skip, nullptr, nullptr, nullptr);
-    else
-    launch_corners2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                               roles, h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
-                               h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h));
+    // (the markers of a filter divided among the waves of a tile: the plain stacked update alone)
+    const int roles = mode == MODE_STACKED && !nis ? team_roles_pixels(h, M) : 1;
+    with_update_pack<T>(h, nis, nullptr, [&](auto... x) {
+        launch_corners2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
+                                   roles, h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
+                                   h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), x...);
+    });
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -826,19 +794,13 @@ int launch_correct_pixels_t(fbus_ekf_t h, int M, const int32_t* ids, const void*
     // double-precision fold + non-cancelling update (ekf_meas.hpp), both record types, either covariance form (the form is
     // symmetric by construction and subtracts nothing on the rows the measurement shrinks: what Joseph's form is chosen for)
     h->records_warm = h->warm_after_correct;          // written through (sc1), as correct_kernel's records
-    const int split = meas_split_roles(h, M);
+    const int split = meas_split_roles(h, M);         // (0 on a tabled handle, as team_roles_pixels is 1)
     if constexpr (sizeof(T) == 4) {
         if (split > 0)
             launch_pixels_split_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, split,
                                            h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
     }
-    if (tabled(h)) {                    // (split == 0) the NIS kernel with no outputs and no gate: this filter's r_pix (family 15)
-        tabled_pixels<T, N, D>(h, M, ids, left, right, skip, nullptr, nullptr, nullptr);
-    } else if (split == 0 || sizeof(T) != 4) {
-        const int roles = team_roles_pixels(h, M);
-        launch_pixels2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, roles,
-                                  h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
-    }
+    if (split == 0 || sizeof(T) != 4) update_pixels<T, N, D>(h, M, ids, left, right, team_roles_pixels(h, M), skip, nullptr);
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -861,9 +823,11 @@ bool frame_meas_resident(const fbus_ekf* h, int kind, int M, int mode)
     const int roles = (kind == MEAS_CORNERS && mode != MODE_STACKED) ? 1 : team_roles_pixels(h, M);
     return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas && !tabled(h);
 }
+// tj: the resident window (F > 1) with frame f's rows written from the registers (frame_meas_kernel with TrajOut)
 template <typename T, int N, int D>
 int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
-                        int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip)
+                        int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
+                        const TrajDst* tj)
 {
     // F = 1: one frame; F > 1: a window (the caller has checked that the resident kernel applies)
     const int K = kc[0];
@@ -881,46 +845,24 @@ int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void
         const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
         h->records_warm = h->warm_after_correct;      // written through (sc1), as the per-call updates: the next predict streams them
         const DevConst<T> dc = make_dc<T>(h);
-        launch_frame_meas_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt, dt_per_filter ? 1 : 0,
-                                     kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode, h->prm.marker_size,
-                                     kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
-                                     h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), dc.qd);
-        timing_end(h, ev);
-        HIP_TRY(h, hipGetLastError());
-    }
-    return FBUS_OK;
-}
-int launch_frame_meas(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per, int kind,
-                      int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip)
-{
-    DISPATCH(h, launch_frame_meas_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip);
-}
-// the resident window (F > 1) of launch_frame_meas_t with frame f's rows written from the registers (frame_meas_kernel with TrajOut)
-template <typename T, int N, int D>
-int launch_frame_meas_traj_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
-                             int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
-                             int mode, const uint8_t* skip, const TrajDst& tj)
-{
-    if constexpr (sizeof(T) == 4) {
-        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
-        h->records_warm = h->warm_after_correct;
-        const DevConst<T> dc = make_dc<T>(h);
-        launch_frame_meas_traj_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                          dt_per_filter ? 1 : 0, kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                          h->prm.marker_size, kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres,
-                                          (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h),
-                                          make_vc<T>(h), dc.qd, (T*)tj.nom, (T*)tj.pdiag, tj.applied);
+        const auto go = [&](auto... x) {
+            launch_frame_meas_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt, dt_per_filter ? 1 : 0,
+                                         kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode, h->prm.marker_size,
+                                         kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
+                                         h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), dc.qd, x...);
+        };
+        if (tj) go(TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied }); else go();
         timing_end(h, ev);
         HIP_TRY(h, hipGetLastError());
         return FBUS_OK;
     }
-    return fail(h, FBUS_ERR_UNSUPPORTED, "frames_meas_fused_traj: no resident fp64 window");
+    return tj ? fail(h, FBUS_ERR_UNSUPPORTED, "frames_meas_fused_traj: no resident fp64 window") : FBUS_OK;
 }
-int launch_frame_meas_traj(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per,
-                           int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
-                           const uint8_t* skip, const TrajDst& tj)
+int launch_frame_meas(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per, int kind,
+                      int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
+                      const TrajDst* tj = nullptr)
 {
-    DISPATCH(h, launch_frame_meas_traj_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip, tj);
+    DISPATCH(h, launch_frame_meas_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip, tj);
 }
 bool frame_meas_is_resident(const fbus_ekf* h, int kind, int M, int mode)
 {
@@ -933,44 +875,22 @@ int launch_correct_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* 
     DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip);
 }
 
-// the pose update with the NIS output and the gate (kernels_tu.hip family 13)
-template <typename T, int N, int D>
-int launch_correct_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
-                         void* nis, int32_t* dof)
-{
-    const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
-    h->records_warm = h->warm_after_correct;
-    if (tabled(h))
-        tabled_correct<T, N, D>(h, M, ids, pos, quat, mode, skip, nis, dof, h->d_gate);
-    else
-    launch_correct_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                  h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp,
-                                  (T*)nis, (int*)dof, h->d_gate);
-    timing_end(h, ev);
-    HIP_TRY(h, hipGetLastError());
-    return FBUS_OK;
-}
+// the updates with the NIS output and the gate (the pixel / corner updates: always the one-wave-per-tile kernels)
 int launch_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                        void* nis, int32_t* dof)
 {
-    DISPATCH(h, launch_correct_nis_t, h, M, ids, pos, quat, mode, skip, nis, dof);
+    const NisDst nd{ nis, dof };
+    DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip, &nd);
 }
-
-// the pixel / corner updates with the NIS output and the gate (kernels_tu.hip family 12): always the one-wave-per-tile kernels
 template <typename T, int N, int D>
 int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
-                                void* nis, int32_t* dof)
+                                const NisDst& nd)
 {
     if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
         return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
-    if (tabled(h))
-        tabled_pixels<T, N, D>(h, M, ids, left, right, skip, nis, dof, h->d_gate);
-    else
-    launch_pixels2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, h->prm.marker_size,
-                                  h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h), (T*)nis, (int*)dof,
-                                  h->d_gate);
+    update_pixels<T, N, D>(h, M, ids, left, right, 1, skip, &nd);
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -978,30 +898,14 @@ int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const v
 int launch_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
                               void* nis, int32_t* dof)
 {
-    DISPATCH(h, launch_correct_pixels_nis_t, h, M, ids, left, right, skip, nis, dof);
-}
-template <typename T, int N, int D>
-int launch_correct_corners_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
-                                 const uint8_t* skip, void* nis, int32_t* dof)
-{
-    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_corners_nis: left / right must be 16-byte aligned device pointers");
-    const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
-    h->records_warm = h->warm_after_correct;
-    if (tabled(h))
-        tabled_corners<T, N, D>(h, M, ids, left, right, geometry, mode, skip, nis, dof, h->d_gate);
-    else
-    launch_corners2_nis_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
-                                   h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip, h->d_applied,
-                                   h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), (T*)nis, (int*)dof, h->d_gate);
-    timing_end(h, ev);
-    HIP_TRY(h, hipGetLastError());
-    return FBUS_OK;
+    const NisDst nd{ nis, dof };
+    DISPATCH(h, launch_correct_pixels_nis_t, h, M, ids, left, right, skip, nd);
 }
 int launch_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
                                const uint8_t* skip, void* nis, int32_t* dof)
 {
-    DISPATCH(h, launch_correct_corners_nis_t, h, M, ids, left, right, geometry, mode, skip, nis, dof);
+    const NisDst nd{ nis, dof };
+    DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip, &nd);
 }
 // a call whose largest possible dof has no entry in the gate table is refused (before anything is launched)
 int check_gate_dof(fbus_ekf_t h, int max_dof, const char* where)
@@ -2301,8 +2205,7 @@ static int frames_meas_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, co
     // the resident window kernel where the frame form takes the resident kernel (fp32 records, one wave per tile); elsewhere frame by
     // frame through the frame entry point's routes -- the same arithmetic (with a trajectory: each frame's rows by the snapshot kernel)
     if (nframes > 1 && frame_meas_is_resident(h, kind, M, mode))
-        return tj ? launch_frame_meas_traj(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, *tj)
-                  : launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip);
+        return launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, tj);
     const size_t es = esize(h), B = (size_t)h->B;
     const size_t lw = (kind == FBUS_MEAS_CORNERS && geometry == FBUS_VIS_CORNERS3D) ? 12 : 8;
     size_t k0 = 0;
@@ -2370,7 +2273,7 @@ static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const v
     // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
     // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel
     const bool team = resident && team_frames(h, mode);
-    if (resident && !team) return launch_frames_traj(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, *tj);
+    if (resident && !team) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, tj);
     const size_t es = esize(h), B = (size_t)h->B;
     size_t k0 = 0;
     for (int f = 0; f < nframes; ++f) {

@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""Are the kernels of two builds the same instruction streams?  For every object present in both directories the gfx950 code object is
+"""Are the kernels of two builds the same instruction streams?  For every object of either directory the gfx950 code object is
 unbundled and disassembled (llvm-objdump -d); per kernel symbol the instruction text (addresses and encodings stripped) is compared.
   python tools/isa_diff.py OBJDIR_A OBJDIR_B [name-filter ...]
 Used to show that a change that adds kernel families leaves the existing instantiations as they were (a parent-commit build against
-the branch's).  Exit status 1 when a common kernel differs or a kernel of A is missing in B."""
+the branch's), or that a refactor of the launch layer leaves the device code as it was.  Symmetric: exit status 1 when a common kernel
+differs, or when an object or a kernel of one build is missing in the other."""
 import glob, hashlib, os, re, subprocess, sys, tempfile
 LLVM = "/opt/rocm/lib/llvm/bin"
 
@@ -44,23 +45,28 @@ def main():
     a, b, filt = sys.argv[1], sys.argv[2], sys.argv[3:]
     bad = 0
     nk = ni = 0
-    for pa in sorted(glob.glob(os.path.join(a, "*.o"))):
-        base = os.path.basename(pa)
+    nkb = nib = 0
+    names = {os.path.basename(p) for d in (a, b) for p in glob.glob(os.path.join(d, "*.o"))}
+    for base in sorted(names):
         if filt and not any(f in base for f in filt):
             continue
-        pb = os.path.join(b, base)
-        if not os.path.exists(pb):
-            print(f"{base}: missing in {b}"); bad += 1
+        pa, pb = os.path.join(a, base), os.path.join(b, base)
+        if not os.path.exists(pa) or not os.path.exists(pb):
+            print(f"{base}: missing in {b if os.path.exists(pa) else a}"); bad += 1
             continue
         ka, kb = kernels_of(pa), kernels_of(pb)
         diff = [k for k in ka if k not in kb or ka[k][0] != kb[k][0]]
+        extra = [k for k in kb if k not in ka]
         nk += len(ka); ni += sum(v[1] for v in ka.values())
+        nkb += len(kb); nib += sum(v[1] for v in kb.values())
         print(f"{base}: {len(ka)} kernels, {sum(v[1] for v in ka.values())} instructions, {len(diff)} differ" +
-              (f", {len(kb) - len(ka)} more in B" if len(kb) != len(ka) else ""))
+              (f", {len(extra)} only in B" if extra else ""))
         for k in diff:
-            print("   differs:", k)
-        bad += len(diff)
-    print(f"total: {nk} kernels, {ni} instructions compared, {bad} differ")
+            print("   differs:" if k in kb else "   only in A:", k)
+        for k in extra:
+            print("   only in B:", k)
+        bad += len(diff) + len(extra)
+    print(f"total: A {nk} kernels, {ni} instructions; B {nkb} kernels, {nib} instructions; {bad} differ")
     sys.exit(1 if bad else 0)
 
 
