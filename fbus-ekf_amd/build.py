@@ -44,6 +44,8 @@ FAMILIES = {
     "correctnz":  (16, "correct", True),
     "measlik":    (17, "meas",    True),    # the tabled NIS updates with the log-likelihood sums
     "correctlik": (18, "correct", True),
+    "framesnz":   (19, "frames",  False),   # the trajectory windows with per-filter noise (the resident windows of a tabled handle)
+    "fmeasnz":    (20, "fmeas",   False),
 }
 # Per-family scheduler choice, fp32 units (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
 # max-ILP strategy of the AMDGPU machine scheduler shortens the per-call kernels, where one wave per SIMD has nothing

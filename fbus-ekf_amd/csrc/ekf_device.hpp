@@ -1271,6 +1271,9 @@ __device__ __forceinline__ void noise_pose(DevConst<T>& dc, int b, const NO&... 
 // (what fbus_ekf_get_applied reports after frame f alone).  Each pointer may be null.
 template <typename T>
 struct TrajOut { T* nom; T* pdiag; unsigned char* applied; };
+// the resident windows of a tabled handle (kernels_tu.hip families 19 / 20) take (TrajOut, NoiseIn): a window without trajectory
+// outputs passes three null pointers; a trailing LikOut has room behind them
+template <typename T> __device__ __forceinline__ NoiseIn noise_in(const TrajOut<T>&, const NoiseIn& n) { return n; }
 
 // ---- innovation log-likelihood (fbus_ekf_loglik_*): a trailing kernel parameter LikOut behind (NisOut, NoiseIn) -- the likelihood kernels
 // are always the tabled kind (kernels_tu.hip families 17 / 18).  acc: the handle's sums as fp64 fields [4][B] (ll, rows of S, applied,

@@ -1060,9 +1060,18 @@ __device__ __forceinline__ void traj_row(const TrajOut<T>& o, size_t row, const 
     }
     if (o.applied) o.applied[row] = app;
 }
+// (the pack of a tabled window: TrajOut, NoiseIn)
+template <typename T, int N>
+__device__ __forceinline__ void traj_row(const TrajOut<T>& o, const NoiseIn&, size_t row, const T* nom, const T* P, unsigned char app)
+{
+    traj_row<T, N>(o, row, nom, P, app);
+}
 
 // TJ = TrajOut<T> (fbus_ekf_frames_fused_traj_dev, instantiated in a family of its own: kernels_tu.hip "framest"): frame f's trajectory
 // row goes out after its update, from the resident registers.  The empty pack is the window without rows.
+// TJ = TrajOut<T>, NoiseIn (the window of a tabled handle, family "framesnz"; the rows may be three null pointers): this lane's q_v q_theta
+// q_ba q_bg, r_pos and r_quat written into the by-value constants once, in front of the frame loop (noise_q, noise_pose: what predict_kernel
+// and correct_kernel do per call) -- the arithmetic of the untabled window on the lane's own values.
 template <typename T, int N, int DIALECT, int COV, bool JOINT, typename... TJ>
 __global__ void __launch_bounds__(BLOCK)
 frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __restrict__ accel, const T* __restrict__ gyro,
@@ -1088,6 +1097,7 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
         order_fence();
     }
     if (b >= B) return;
+    if constexpr (has_noise<TJ...>()) { noise_q<T>(dc, b, traj...); noise_pose<T>(dc, b, traj...); }
     int k0 = 0, last_used = 0;
     // (TRAJ) M = 0: no frame writes d_applied, get_applied keeps reporting what it did before the window
     const unsigned char app_in = (TRAJ && M == 0) ? applied[b] : 0;

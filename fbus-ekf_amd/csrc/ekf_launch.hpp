@@ -10,12 +10,13 @@
 // kernels_tu.hip; any other pack links as an undefined symbol):
 //   launch_predict_k                                          ()  (NoiseIn)
 //   launch_correct_k, launch_pixels2_k, launch_corners2_k     ()  (NisOut<T>)  (NisOut<T>, NoiseIn)  (NisOut<T>, NoiseIn, LikOut)
-//   launch_frames_k, launch_frame_meas_k                      ()  (TrajOut<T>)
+//   launch_frames_k, launch_frame_meas_k                      ()  (TrajOut<T>)  (TrajOut<T>, NoiseIn)
 // NisOut<T>{nis, dof, thr}: nis [B] in T and dof [B] on the device (each may be null), thr: the handle's gate table on the device (null
 // for the pixel / corner updates, a table of +inf for the pose update: no gate; its length was checked against the largest dof).
 // NoiseIn{noise, B}: the handle's table [FBUS_NOISE_COLS][B] (fbus_ekf_set_noise).  LikOut{lik, B}: the handle's sums [4][B] (ll, rows,
 // applied, rejected as doubles; fbus_ekf_loglik_enable).  TrajOut<T>{nominal, pdiag, applied}: frame f's trajectory row [f][B][.] goes
-// to each non-null output.  With a pack the updates run one wave per tile.
+// to each non-null output.  With a pack the updates run one wave per tile.  (TrajOut<T>, NoiseIn): the resident windows of a tabled handle
+// (fp32); its windows without trajectory outputs pass three null pointers, its fused single frames F = 1.
 #pragma once
 #include "ekf_device.hpp"
 #include "vision_device.hpp"
@@ -109,7 +110,7 @@ void launch_corners2_k(hipStream_t s, T* recs, int B, int M, const int* ids, con
 // kind: corner pixels (geometry / mode ignored; right == nullptr: left camera) or stereo corners (geometry, mode as correct_corners)
 enum { MEAS_PIXELS = 0, MEAS_CORNERS = 1 };
 // F = 1: one frame of kcount[0] predicts; F > 1: a window of F frames in one launch (kcount: F host bytes; measurements [F][B][M]...);
-// with TrajOut a window only
+// with a pack the window form only (F = 1 included); with a NoiseIn qd and r_meas are ignored
 template <typename T, int N, int D, typename... X>
 void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt, int dt_stride, int kind,
                          int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size, double r_meas,

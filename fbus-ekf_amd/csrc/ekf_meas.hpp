@@ -1883,6 +1883,8 @@ template <typename T> struct QDiag { T qd[4]; };      // (MEAS_PIXELS / MEAS_COR
 // TJ = TrajOut<T> (fbus_ekf_frames_meas_fused_traj_dev; WINDOW only, instantiated in a family of its own: kernels_tu.hip "fmeast"): frame
 // f's trajectory row goes out from the resident registers once its update has been applied, or the predicted record where it was not.
 // The empty pack is the kernel without rows.
+// TJ = TrajOut<T>, NoiseIn (the window of a tabled handle, family "fmeasnz"; the rows may be three null pointers): this lane's q in place of
+// qd and its r_pix (pixel rows) / r_pos (corner rows) in place of r_meas, loaded once in front of the frame loop.
 template <typename T, int N, int DIALECT, int KIND, bool NZ, bool WINDOW = false, int CAM = 0, typename... TJ>
 __global__ void __launch_bounds__(64)
 frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __restrict__ accel, const T* __restrict__ gyro,
@@ -1996,6 +1998,12 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
         }
     }
     if (b >= B) return;
+    if constexpr (has_noise<TJ...>()) {
+        const NoiseIn ni = noise_in(traj...);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) qd.qd[i] = (T)noise_ld(ni, NOISE_QV + i, b);
+        r_meas = noise_ld(ni, KIND == MEAS_PIXELS ? NOISE_RPIX : NOISE_RPOS, b);
+    }
     // WINDOW: F times { K_f ImuUpdates, the update } with the record resident from the first load to the last store (offline replay of a
     // recorded stretch of corners.txt, FBUS_EKF.m:151-210); otherwise one pass (F = 1).  Same device functions in the same order per filter
     // as F launches of the frame form: bit-identical results.

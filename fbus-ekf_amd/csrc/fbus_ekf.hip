@@ -297,6 +297,13 @@ bool tabled(const fbus_ekf* h) { return h->noise_on || h->lik_on; }
 int policy_tiles(const fbus_ekf* h) { return ((h->policy_batch > 0 ? h->policy_batch : h->B) + 63) / 64; }
 int quarter_chip(const fbus_ekf* h) { return h->lp.simds / 4; }
 int half_chip(const fbus_ekf* h) { return h->lp.simds / 2; }
+// A noise table and the resident windows (frames_kernel / frame_meas_kernel with (TrajOut, NoiseIn): kernels_tu.hip families 19 / 20).
+// The fused frames and the frame windows of a tabled handle take them exactly where an untabled handle of the same policy batch runs
+// the ONE-WAVE resident kernels: fp32 records, more than half a chip of tiles.  A pure size rule on the policy batch (fbus_ekf_set_team
+// stays ignored while a table is set; the shards of a job agree with the unsharded run).  At or below half a chip, where untabled
+// handles take the team forms, and while the likelihood sums are on (no resident kernel feeds them): frame by frame through the per-call
+// kernels.  What a single call can still exclude -- (Joseph, nearest) pose rows, M = 0, FBUS_NO_FRAME_MEAS -- is excluded as without a table.
+bool noise_resident(const fbus_ekf* h) { return h->noise_on && !h->lik_on && h->dtype == 32 && policy_tiles(h) > half_chip(h); }
 int team_roles_predict(const fbus_ekf* h, int K)
 {
     if (h->dtype != 32 || h->team_predict == 1 || tabled(h)) return 1;      // (a noise table, likelihood sums: the one-wave forms only)
@@ -448,13 +455,20 @@ int launch_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, con
     DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip);
 }
 
+struct TrajDst;
+template <typename T, int N, int D>
+int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+                    int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+                    const TrajDst* tj);
 template <typename T, int N, int D>
 int launch_frame_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter, int M,
                    const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
     const bool f64_fused = sizeof(T) == 8 && mode == MODE_STACKED && h->prm.cov_form != FBUS_COV_JOSEPH && K > 0 && K <= 255;
-    // (a noise table: no fused kernel reads it -- predict_n + the per-call update, which do)
-    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || tabled(h)) {
+    // (a noise table: the window kernel with F = 1 where noise_resident() says so -- a window is then bit-equal to its fused frames by
+    // construction; otherwise predict_n + the per-call update, which read the table too)
+    const bool nz_resident = noise_resident(h) && K <= 255;
+    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || (tabled(h) && !nz_resident)) {
         // no fused kernel for fp64 outside (stacked, simple) and none for the Joseph form with the reference mode's 7 row-by-row
         // updates (it spilled): those frames are one predict_n launch and one correct launch -- the same arithmetic
         int rc = FBUS_OK;
@@ -475,6 +489,10 @@ int launch_frame_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, con
         return FBUS_OK;
     }
     if constexpr (sizeof(T) == 4) {
+    if (nz_resident) {
+        const unsigned char kc1 = (unsigned char)K;
+        return launch_frames_t<T, N, D>(h, 1, &kc1, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, nullptr);
+    }
     const int ev = timing_begin(h, FBUS_KERNEL_FRAME);
     h->records_warm = true;
     if (team_frames(h, mode) && K <= 255) {
@@ -503,7 +521,8 @@ int launch_frame(fbus_ekf_t h, int K, const void* accel, const void* gyro, const
 struct TrajDst { void* nom; void* pdiag; uint8_t* applied; };
 
 // tj: the window with frame f's rows written from its registers (frames_kernel with TrajOut; the caller has checked that the one-wave
-// resident kernel applies: fp32, not (Joseph, nearest), not the team form)
+// resident kernel applies: fp32, not (Joseph, nearest), not the team form).  A tabled handle (noise_resident(): the caller has checked) runs
+// the same kernel with (TrajOut, NoiseIn), the window without rows with three null pointers.
 template <typename T, int N, int D>
 int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
                     int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
@@ -517,7 +536,9 @@ int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* ac
                                      dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                      h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), x...);
         };
-        if (tj) one_wave(TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied });
+        const TrajOut<T> to = tj ? TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied } : TrajOut<T>{ nullptr, nullptr, nullptr };
+        if (noise_resident(h)) one_wave(to, NoiseIn{ h->d_noise, h->B });
+        else if (tj) one_wave(to);
         else if (team_frames(h, mode))
             launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
                                           dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
@@ -820,10 +841,13 @@ int launch_correct_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* l
 template <typename T>
 bool frame_meas_resident(const fbus_ekf* h, int kind, int M, int mode)
 {
+    // (a noise table: the size rule alone, see noise_resident)
+    if (tabled(h)) return sizeof(T) == 4 && M > 0 && !h->no_frame_meas && noise_resident(h);
     const int roles = (kind == MEAS_CORNERS && mode != MODE_STACKED) ? 1 : team_roles_pixels(h, M);
-    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas && !tabled(h);
+    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas;
 }
-// tj: the resident window (F > 1) with frame f's rows written from the registers (frame_meas_kernel with TrajOut)
+// tj: the resident window (F > 1) with frame f's rows written from the registers (frame_meas_kernel with TrajOut).  A tabled handle runs
+// the window kernel with (TrajOut, NoiseIn) for F = 1 as well, and without rows with three null pointers.
 template <typename T, int N, int D>
 int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                         int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
@@ -851,7 +875,10 @@ int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void
                                          kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
                                          h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), dc.qd, x...);
         };
-        if (tj) go(TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied }); else go();
+        const TrajOut<T> to = tj ? TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied } : TrajOut<T>{ nullptr, nullptr, nullptr };
+        if (noise_resident(h)) go(to, NoiseIn{ h->d_noise, h->B });
+        else if (tj) go(to);
+        else go();
         timing_end(h, ev);
         HIP_TRY(h, hipGetLastError());
         return FBUS_OK;
@@ -1288,6 +1315,7 @@ int fbus_ekf_launch_info(fbus_ekf_t h, int what, int arg, int* value)
         case FBUS_INFO_ROLES_MEAS: *value = team_roles_pixels(h, arg > 0 ? arg : 4); break;
         case FBUS_INFO_TEAM_FRAMES: *value = team_frames(h, MODE_STACKED) ? 1 : 0; break;
         case FBUS_INFO_MEAS_SPLIT: *value = meas_split_roles(h, arg > 0 ? arg : 4); break;
+        case FBUS_INFO_NOISE_RESIDENT: *value = noise_resident(h) ? 1 : 0; break;
         default: return FBUS_ERR_INVALID;
     }
     return FBUS_OK;
@@ -2267,8 +2295,9 @@ static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const v
         const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_fused_traj_dev");
         if (rc != FBUS_OK) return rc;
     }
-    // (a noise table: frame by frame, through the per-call kernels that read it)
-    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) && !tabled(h);
+    // (a noise table: the resident window that reads it where noise_resident() says so, else frame by frame through the per-call kernels)
+    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) &&
+                          (!tabled(h) || noise_resident(h));
     if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
     // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
     // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel

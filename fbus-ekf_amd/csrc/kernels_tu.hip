@@ -19,6 +19,9 @@
 //  17 15's updates with the innovation log-likelihood sums (NisOut, NoiseIn and LikOut; fbus_ekf_loglik_enable: every pixel / corner update
 //     of the handle runs here while accumulation is on, with the handle's own noise in the table when the caller set none)
 //  18 16's update with the log-likelihood sums (likewise, every pose update)
+//  19 10's window with per-filter q, r_pos, r_quat (frames_kernel with TrajOut and NoiseIn; fp32 only; the window without trajectory
+//     outputs and the fused frame of a tabled handle run here too, with null outputs and F = 1)
+//  20 11's window with per-filter q and r_pix / r_pos (frame_meas_kernel with TrajOut and NoiseIn; fp32 only; likewise)
 // A launcher is written once for its kernel and takes the kernel's trailing pack; the families that extend another (10-18) instantiate the
 // launcher of the family they extend with their pack (FBUS_TU_PACK), and what they choose differently is an `if constexpr` on the pack.
 // gfx950 only.
@@ -47,6 +50,8 @@
 #define FBUS_TU_PACK , NisOut<FBUS_TU_T>, NoiseIn
 #elif FBUS_TU_FAMILY == 17 || FBUS_TU_FAMILY == 18
 #define FBUS_TU_PACK , NisOut<FBUS_TU_T>, NoiseIn, LikOut
+#elif FBUS_TU_FAMILY == 19 || FBUS_TU_FAMILY == 20
+#define FBUS_TU_PACK , TrajOut<FBUS_TU_T>, NoiseIn
 #else
 #define FBUS_TU_PACK
 #endif
@@ -175,7 +180,7 @@ void launch_frame_k(hipStream_t s, T* recs, int B, int K, const T* accel, const 
                                                           const unsigned char*, unsigned char*,                       \
                                                           const DevConst<FBUS_TU_T>&, const LaunchPolicy&);
 
-#elif FBUS_TU_FAMILY == 5 || FBUS_TU_FAMILY == 10
+#elif FBUS_TU_FAMILY == 5 || FBUS_TU_FAMILY == 10 || FBUS_TU_FAMILY == 19
 template <typename T, int N, int D, typename... X>
 void launch_frames_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro,
                      const T* dt, int dt_stride, int M, const int* ids, const T* pos, const T* quat, int mode, bool joseph,
@@ -319,7 +324,7 @@ void launch_corners2_k(hipStream_t s, T* recs, int B, int M, const int* ids, con
                                                                           const unsigned char*, unsigned char*, const short*, \
                                                                           const MeasConst&, const VisConst<double>&,  \
                                                                           const VisConst<FBUS_TU_T>& FBUS_TU_PACK);
-#elif FBUS_TU_FAMILY == 8 || FBUS_TU_FAMILY == 11
+#elif FBUS_TU_FAMILY == 8 || FBUS_TU_FAMILY == 11 || FBUS_TU_FAMILY == 20
 template <typename T, int N, int D, typename... X>
 void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned char* kcount, const T* accel, const T* gyro, const T* dt,
                          int dt_stride, int kind, int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size,
@@ -332,7 +337,8 @@ void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned ch
     for (int i = 0; i < 4; ++i) q.qd[i] = qd[i];
     // the shorter fold / triangulation of the square port, as the per-call launchers choose
     const bool nz = square_port(kind == MEAS_PIXELS ? mc.n : vc.nrm);
-    // with TrajOut only the window form is built (the trajectory entry points are windows, F > 1)
+    // with a pack only the window form is built (the trajectory entry points are windows, F > 1; a tabled handle runs its single
+    // frames as windows of F = 1; with a NoiseIn the kernel reads the lane's own q and r from the table, not qd / r_meas)
     constexpr bool window_only = sizeof...(X) > 0;
 #define FBUS_LAUNCH_FM1(KIND, NZF, CAM, WINDOW)                                                                          \
     hipLaunchKernelGGL((frame_meas_kernel<T, N, D, KIND, NZF, WINDOW, CAM, X...>), dim3(tiles), dim3(64), 0, s, recs, B, F, kc, accel, gyro, dt, \

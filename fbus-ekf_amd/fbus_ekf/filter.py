@@ -395,7 +395,10 @@ class BatchedFilter:
         """Per-filter process and measurement noise (fbus_ekf_set_noise): a (B, 7) table, columns noise.COLUMNS (q_v q_theta q_ba q_bg
         r_pos r_quat r_pix, the fbus_params fields of the same names); row b replaces those fields for filter b.  A numpy array (or
         anything np.asarray takes) goes through the host form, which validates every entry; a contiguous float64 device tensor through
-        the device form, validated here with torch first.  None: no table (back to the handle's parameters)."""
+        the device form, validated here with torch first.  None: no table (back to the handle's parameters).
+        With a table the updates and predicts take the one-wave kernels; frames() / frames_meas() and the fused single frames run the
+        resident window kernels that read the table while launch_info(capi.INFO_NOISE_RESIDENT) is 1 (fp32 records, likelihood sums off,
+        policy batch above half a chip), and frame by frame through the per-call kernels otherwise."""
         if table is None:
             return self._check(self._lib.fbus_ekf_set_noise(self._h, None), "set_noise")
         B, NC = self.B, capi.NOISE_COLS

@@ -203,7 +203,7 @@ def replay_windowed(flt, imu, image, params, max_frames=None, max_window=64, tra
     ONCE, behind the initialisation and in front of the first frame; a filter reset the recording's vision gaps cause (FBUS_EKF.m:168-171)
     does NOT zero them: the reset frame applies no update and so adds nothing, and the evidence of a noise hypothesis is the sum over
     every update of the run, whichever side of a gap it lies on.  While the sums are on the windows run frame by frame (the per-call
-    rate, as with a noise table)."""
+    rate, as with a noise table at or below half a chip of filters; above it a tabled handle's windows stay resident)."""
     import torch
     imu = np.asarray(imu, float)
     image = np.asarray(image, float)

@@ -170,8 +170,12 @@ enum { FBUS_INFO_SIMDS = 0,            /* SIMDs of the device = CUs x 4 (FBUS_FA
        FBUS_INFO_ROLES_PREDICT = 7,    /* waves per tile the next predict (arg = 1) / predict_n (arg = K) would use       */
        FBUS_INFO_ROLES_MEAS = 8,       /* ... correct_corners (stacked) / correct_pixels with arg = M marker slots          */
        FBUS_INFO_TEAM_FRAMES = 9,      /* 1: the fused frame / frame window entry points use the team kernel              */
-       FBUS_INFO_MEAS_SPLIT = 10 };    /* (round 5) correct_pixels with arg = M: 0 = one wave applies the update, 2 / 4 = the update divided
+       FBUS_INFO_MEAS_SPLIT = 10,      /* (round 5) correct_pixels with arg = M: 0 = one wave applies the update, 2 / 4 = the update divided
                                           between a solver and an updater wave, that many waves per tile (fp32, square port) */
+       FBUS_INFO_NOISE_RESIDENT = 11 };/* 1: with the noise table and the likelihood sums as they are now, the fused frame / frame window
+                                          entry points take the resident kernels that read the table (table set, sums off, fp32 records,
+                                          policy batch above half a chip); 0 otherwise, no table included.  What a single call can still
+                                          exclude ((Joseph, nearest) pose rows, M = 0, FBUS_NO_FRAME_MEAS) is not part of the answer */
 int fbus_ekf_launch_info(fbus_ekf_t h, int what, int arg, int* value);
 /* Cross-stream ordering without a host sync (hipEventRecord + hipStreamWaitEvent):
  * wait_stream   -- work submitted to the handle's stream after this call starts
@@ -530,9 +534,14 @@ int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, co
  * table therefore sees the values current at its replay.  A graph captured without a table keeps the kernels it captured (it reads
  * fbus_params as they were at capture).  set_noise / set_noise_dev / get_noise are refused between graph_begin and graph_end.
  * ROUTES with a table: the one-wave-per-tile kernels only.  The team forms (fbus_ekf_set_team is ignored while a table is set, and
- * fbus_ekf_launch_info reports ROLES_* = 1, TEAM_FRAMES = 0, MEAS_SPLIT = 0), the divided pixel update and the resident window
- * kernels are bypassed; fbus_ekf_frame*_fused_dev and the windows run frame by frame (predict_n + the per-call update; trajectory rows
- * from the snapshot kernel).  The plain updates run the NIS kernels with no outputs and no gate: records equal a handle with the row's
+ * fbus_ekf_launch_info reports ROLES_* = 1, TEAM_FRAMES = 0, MEAS_SPLIT = 0) and the divided pixel update are bypassed.
+ * fbus_ekf_frame*_fused_dev and the windows take resident kernels that read the table where an untabled handle of the same policy
+ * batch runs the one-wave resident kernels: fp32 records, likelihood sums off, policy batch above half a chip
+ * (FBUS_INFO_NOISE_RESIDENT; not (Joseph, nearest) pose rows, M = 0, FBUS_NO_FRAME_MEAS, as without a table).  Filter b of such a window
+ * equals, bit for bit, the untabled resident window of a handle with row b's values in fbus_params, and the window equals its fused frames
+ * bit for bit (the single-frame entry points launch the same kernels with one frame); it equals the per-call sequence to fp32 rounding,
+ * as every untabled window does.  Elsewhere (at or below half a chip, the sums on, fp64 records) they run frame by frame, bit-equal to
+ * predict_n + the per-call update (trajectory rows from the snapshot kernel).  The plain updates run the NIS kernels with no outputs and no gate: records equal a handle with the row's
  * values in fbus_params on its one-wave route bit for bit, except fp64 C++-dialect stacked pose updates (nominal state within ~2e-15,
  * see the NIS section above).
  * fbus_ekf_set_noise     host table; every entry must be finite, q >= 0 and r > 0 (as fbus_params_validate).  A bad entry returns
