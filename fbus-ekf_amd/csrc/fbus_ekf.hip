@@ -222,6 +222,15 @@ int fail(fbus_ekf_t h, int code, const std::string& msg)
     } while (0)
 
 size_t esize(const fbus_ekf* h) { return h->dtype == 32 ? 4 : 8; }
+// what the entry points accept: an update mode, a corner geometry, and image-point arrays on a 16-byte boundary -- the kernels fetch a
+// slot's points with 16-byte loads (a slot is 32 / 48 contiguous bytes): any allocation is aligned, a view offset by one to three
+// elements is not and is refused, not read unaligned
+bool mode_ok(int mode) { return mode == FBUS_MODE_NEAREST || mode == FBUS_MODE_STACKED; }
+bool geometry_ok(int g) { return g == FBUS_VIS_REFRACTIVE || g == FBUS_VIS_PINHOLE || g == FBUS_VIS_CORNERS3D; }
+bool points_aligned(const void* left, const void* right)
+{
+    return ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) == 0;
+}
 
 template <typename T>
 DevConst<T> make_dc(const fbus_ekf* h)
@@ -343,7 +352,7 @@ int meas_split_roles(const fbus_ekf* h, int M)
 bool team_frames(const fbus_ekf* h, int mode)
 {
     if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH || tabled(h)) return false;
-    if (mode != MODE_NEAREST && mode != MODE_STACKED) return false;
+    if (!mode_ok(mode)) return false;
     if (h->team_frame == 1 || (h->team_frame == 0 && h->team_predict == 1)) return false;
     if (h->team_frame == 2 || h->team_predict >= 2) return true;
     return policy_tiles(h) <= half_chip(h);
@@ -450,9 +459,9 @@ int launch_predict(fbus_ekf_t h, int K, const void* a, const void* g, const void
 }
 
 int launch_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
-                   const uint8_t* skip)
+                   const uint8_t* skip, const NisDst* nis = nullptr)
 {
-    DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip);
+    DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip, nis);
 }
 
 struct TrajDst;
@@ -786,11 +795,6 @@ template <typename T, int N, int D>
 int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                              int mode, const uint8_t* skip, const NisDst* nis = nullptr)
 {
-    // the kernel fetches a slot's image points with 16-byte loads (a slot is 32 / 48 contiguous bytes): the arrays must start on a
-    // 16-byte boundary -- any allocation does; a view offset by one to three elements does not and is refused, not read unaligned
-    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, std::string(nis ? "fbus_ekf_correct_corners_nis" : "fbus_ekf_correct_corners") +
-                                         ": left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     // triangulation and fold in double, non-cancelling update (ekf_meas.hpp); records written through (sc1) as correct_kernel's
     h->records_warm = h->warm_after_correct;
@@ -809,8 +813,6 @@ int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void
 template <typename T, int N, int D>
 int launch_correct_pixels_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip)
 {
-    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)      // 16-byte loads, see correct_corners
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     // double-precision fold + non-cancelling update (ekf_meas.hpp), both record types, either covariance form (the form is
     // symmetric by construction and subtracts nothing on the rows the measurement shrinks: what Joseph's form is chosen for)
@@ -864,8 +866,6 @@ int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void
         return rc;
     }
     if constexpr (sizeof(T) == 4) {
-        if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-            return fail(h, FBUS_ERR_INVALID, "fbus_ekf_frame(s)_meas_fused_dev: left / right must be 16-byte aligned device pointers");
         const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
         h->records_warm = h->warm_after_correct;      // written through (sc1), as the per-call updates: the next predict streams them
         const DevConst<T> dc = make_dc<T>(h);
@@ -897,24 +897,16 @@ bool frame_meas_is_resident(const fbus_ekf* h, int kind, int M, int mode)
 }
 
 int launch_correct_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
-                           int mode, const uint8_t* skip)
+                           int mode, const uint8_t* skip, const NisDst* nis = nullptr)
 {
-    DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip);
+    DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip, nis);
 }
 
-// the updates with the NIS output and the gate (the pixel / corner updates: always the one-wave-per-tile kernels)
-int launch_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
-                       void* nis, int32_t* dof)
-{
-    const NisDst nd{ nis, dof };
-    DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip, &nd);
-}
+// the pixel update with the NIS output and the gate: always the one-wave-per-tile kernel
 template <typename T, int N, int D>
 int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
                                 const NisDst& nd)
 {
-    if (((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_correct_pixels_nis: left / right must be 16-byte aligned device pointers");
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT_CORNERS);
     h->records_warm = h->warm_after_correct;
     update_pixels<T, N, D>(h, M, ids, left, right, 1, skip, &nd);
@@ -923,16 +915,9 @@ int launch_correct_pixels_nis_t(fbus_ekf_t h, int M, const int32_t* ids, const v
     return FBUS_OK;
 }
 int launch_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
-                              void* nis, int32_t* dof)
+                              const NisDst& nd)
 {
-    const NisDst nd{ nis, dof };
     DISPATCH(h, launch_correct_pixels_nis_t, h, M, ids, left, right, skip, nd);
-}
-int launch_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
-                               const uint8_t* skip, void* nis, int32_t* dof)
-{
-    const NisDst nd{ nis, dof };
-    DISPATCH(h, launch_correct_corners_t, h, M, ids, left, right, geometry, mode, skip, &nd);
 }
 // a call whose largest possible dof has no entry in the gate table is refused (before anything is launched)
 int check_gate_dof(fbus_ekf_t h, int max_dof, const char* where)
@@ -941,6 +926,98 @@ int check_gate_dof(fbus_ekf_t h, int max_dof, const char* where)
         return fail(h, FBUS_ERR_INVALID, std::string(where) + ": the gate table has " + std::to_string(h->gate_n) +
                                          " entries, the call can reach dof " + std::to_string(max_dof));
     return FBUS_OK;
+}
+
+// ---- argument checks: one per update -------------------------------------------------------------------------------------------
+// Every form of an update (device pointers, host pointers, asynchronous, _nis) calls its check first: a refused call stages, copies,
+// queues and launches nothing.  where: the entry point the messages name; nis: an _nis form (the gate table must reach the call's
+// largest dof); dev: left / right are device pointers, which the kernels load 16 bytes at a time (staging memory is aligned as allocated).
+int check_predict(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt)
+{
+    return (!h || !accel || !gyro || !dt || K < 1) ? FBUS_ERR_INVALID : FBUS_OK;
+}
+int check_points(fbus_ekf_t h, const void* left, const void* right, const char* where)
+{
+    if (points_aligned(left, right)) return FBUS_OK;
+    return fail(h, FBUS_ERR_INVALID, std::string(where) + ": left / right must be 16-byte aligned device pointers");
+}
+int check_pose(fbus_ekf_t h, const char* where, bool nis, int M, const void* ids, const void* pos, const void* quat, int mode)
+{
+    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (!mode_ok(mode)) return FBUS_ERR_UNSUPPORTED;
+    const int rows = h->prm.dialect == FBUS_DIALECT_CPP ? 7 : 3;
+    return nis ? check_gate_dof(h, rows * (mode == FBUS_MODE_NEAREST ? 1 : M), where) : FBUS_OK;
+}
+int check_r_pix(fbus_ekf_t h) { return h->prm.r_pix > 0 ? FBUS_OK : fail(h, FBUS_ERR_INVALID, "r_pix must be positive"); }
+int check_pixels(fbus_ekf_t h, const char* where, bool nis, bool dev, int M, const void* ids, const void* left, const void* right)
+{
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    int rc = check_r_pix(h);
+    if (rc == FBUS_OK && nis) rc = check_gate_dof(h, M * 8 * (right ? 2 : 1), where);
+    if (rc == FBUS_OK && dev) rc = check_points(h, left, right, where);
+    return rc;
+}
+// geometry and mode of corner rows; rows: the call has marker slots (a frame may have none)
+int check_corner_kind(bool rows, const void* right, int geometry, int mode)
+{
+    if (!geometry_ok(geometry)) return FBUS_ERR_UNSUPPORTED;
+    if (rows && geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
+    return mode_ok(mode) ? FBUS_OK : FBUS_ERR_UNSUPPORTED;
+}
+int check_corners(fbus_ekf_t h, const char* where, bool nis, bool dev, int M, const void* ids, const void* left, const void* right,
+                  int geometry, int mode)
+{
+    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    int rc = check_corner_kind(true, right, geometry, mode);
+    if (rc == FBUS_OK && nis) rc = check_gate_dof(h, 12 * (mode == FBUS_MODE_NEAREST ? 1 : M), where);
+    if (rc == FBUS_OK && dev) rc = check_points(h, left, right, where);
+    return rc;
+}
+
+// kcount -> the window kernels' byte counts (kc, may be null) and the sample total; false when an entry lies outside 0..kmax
+bool frame_counts(int nframes, const int32_t* kcount, int kmax, unsigned char* kc, size_t* total)
+{
+    *total = 0;
+    for (int f = 0; f < nframes; ++f) {
+        if (kcount[f] < 0 || kcount[f] > kmax) return false;
+        if (kc) kc[f] = (unsigned char)kcount[f];
+        *total += (size_t)kcount[f];
+    }
+    return true;
+}
+// The frame / window family.  A single frame is a window of one whose count K may exceed a byte (kcount = &K, kmax = INT_MAX, kc = null).
+// kind: KIND_POSE (a, b = pos, quat) or FBUS_MEAS_PIXELS / FBUS_MEAS_CORNERS (a, b = left, right: device pointers); geometry and mode
+// of a pixel frame are set to the values the launchers expect.  An empty window (nframes = 0) passes: the caller returns FBUS_OK.
+constexpr int KIND_POSE = -1;
+int check_frames(fbus_ekf_t h, const char* where, int nframes, const int32_t* kcount, int kmax, unsigned char* kc, const void* accel,
+                 const void* gyro, const void* dt, int kind, int M, const void* ids, const void* a, const void* b, int& geometry,
+                 int& mode, const TrajDst* tj)
+{
+    const bool window = kc != nullptr;
+    if (!h || nframes < 0 || nframes > FBUS_MAX_WINDOW_FRAMES || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (!window && kcount[0] < 0) return FBUS_ERR_INVALID;
+    if (kind != KIND_POSE && kind != FBUS_MEAS_PIXELS && kind != FBUS_MEAS_CORNERS) return FBUS_ERR_UNSUPPORTED;
+    if (nframes > 0 && !kcount) return FBUS_ERR_INVALID;
+    // (a pose window tests its mode before kcount's entries, a single pose frame behind its arrays: as they always have)
+    const bool pose_mode_bad = kind == KIND_POSE && !mode_ok(mode);
+    if (pose_mode_bad && window) return FBUS_ERR_UNSUPPORTED;
+    size_t total = 0;
+    if (!frame_counts(nframes, kcount, kmax, kc, &total)) return FBUS_ERR_INVALID;
+    if (total > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
+    const bool rows = M > 0 && nframes > 0;
+    if (rows && (!ids || !a || (kind == KIND_POSE && !b))) return FBUS_ERR_INVALID;
+    if (pose_mode_bad) return FBUS_ERR_UNSUPPORTED;
+    int rc = FBUS_OK;
+    if (kind == FBUS_MEAS_PIXELS) {
+        rc = check_r_pix(h);
+        geometry = FBUS_VIS_REFRACTIVE; mode = FBUS_MODE_STACKED;          // (not used by the pixel rows)
+    } else if (kind == FBUS_MEAS_CORNERS)
+        rc = check_corner_kind(rows, b, geometry, mode);
+    if (rc != FBUS_OK || nframes == 0) return rc;
+    // on every route, not only the resident one: the per-call updates behind the fall-back routes would meet unaligned image points AFTER
+    // the predicts have run.  Every frame's arrays start a multiple of 16 bytes behind the first (B M x 32 / 48 bytes x element size)
+    if (kind != KIND_POSE && M > 0 && (rc = check_points(h, a, b, where)) != FBUS_OK) return rc;
+    return tj ? check_traj(h, *tj, nframes, where) : FBUS_OK;
 }
 
 int ensure_stage(fbus_ekf_t h, int slot, size_t bytes)
@@ -957,17 +1034,14 @@ int ensure_stage(fbus_ekf_t h, int slot, size_t bytes)
     return FBUS_OK;
 }
 
-// copies a host array into staging slot `slot`; returns the device pointer through out
-int stage_in(fbus_ekf_t h, int slot, const void* host, size_t bytes, const void** out)
-{
-    *out = nullptr;
-    if (!host || bytes == 0) return FBUS_OK;
-    int rc = ensure_stage(h, slot, bytes);
-    if (rc != FBUS_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(h->stage[slot], host, bytes, hipMemcpyHostToDevice, h->stream));
-    *out = h->stage[slot];
-    return FBUS_OK;
-}
+// ---- the arrays of a call, and the three ways they reach the kernels -----------------------------------------------------------------
+// One array: the caller's pointer as an input (in), as an output (out) or both, its size (0: absent), and where the pointer the launch
+// uses goes.  An update describes its arrays once (`*_pieces` below) and hands the description to run_pieces with the transport.
+struct Piece { const void* in; void* out; size_t bytes; const void** dev; bool zero; };
+Piece in_piece(const void* p, size_t bytes, const void** dev) { return { p, nullptr, p ? bytes : 0, dev, false }; }
+// zero: the staged copy starts as zeros (a kernel that writes only some entries)
+Piece out_piece(void* p, size_t bytes, void** dev, bool zero = false) { return { nullptr, p, p ? bytes : 0, const_cast<const void**>(dev), zero }; }
+Piece inout_piece(void* p, size_t bytes, void** dev) { return { p, p, p ? bytes : 0, const_cast<const void**>(dev), false }; }
 
 // ---- asynchronous host-pointer calls ---------------------------------------------------------------------------------
 // The reference's caller hands one IMU sample at a time to a filter thread and returns at once (FILTER::SetImuData under a mutex,
@@ -980,8 +1054,6 @@ int stage_in(fbus_ekf_t h, int slot, const void* host, size_t bytes, const void*
 //     overlaps the kernel of call i;
 //   * a slot is reused after ASYNC_SLOTS calls; the call then waits for THAT slot's kernel only (back-pressure, counted).
 // Completion and device-side errors: fbus_ekf_sync, or any host-pointer result (fbus_ekf_get_state, fbus_ekf_get_applied).
-struct AsyncPiece { const void* src; size_t bytes; const void** dev_out; };
-
 bool host_ptr_is_pinned(const void* p)
 {
     hipPointerAttribute_t at;
@@ -989,7 +1061,8 @@ bool host_ptr_is_pinned(const void* p)
     return at.type == hipMemoryTypeHost;
 }
 
-int async_begin(fbus_ekf_t h, AsyncPiece* pieces, int n, fbus_ekf::AsyncSlot** out)
+// (input pieces only: no asynchronous form has outputs)
+int async_begin(fbus_ekf_t h, Piece* pieces, int n, fbus_ekf::AsyncSlot** out)
 {
     if (h->capturing) return fail(h, FBUS_ERR_INVALID, "the asynchronous host-pointer calls cannot be captured into a graph (use the _dev entry points)");
     if (!h->copy_stream) HIP_TRY(h, hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
@@ -1018,20 +1091,20 @@ int async_begin(fbus_ekf_t h, AsyncPiece* pieces, int n, fbus_ekf::AsyncSlot** o
     size_t off = 0, staged_end = 0;
     bool direct[8] = { false, false, false, false, false, false, false, false };
     for (int i = 0; i < n; ++i) {
-        *pieces[i].dev_out = nullptr;
-        if (!pieces[i].src || pieces[i].bytes == 0) continue;
-        direct[i] = pieces[i].bytes >= 4096 && host_ptr_is_pinned(pieces[i].src);
+        *pieces[i].dev = nullptr;
+        if (!pieces[i].in || pieces[i].bytes == 0) continue;
+        direct[i] = pieces[i].bytes >= 4096 && host_ptr_is_pinned(pieces[i].in);
         if (direct[i]) continue;
-        std::memcpy((char*)a.host + off, pieces[i].src, pieces[i].bytes);
-        *pieces[i].dev_out = (char*)a.dev + off;
+        std::memcpy((char*)a.host + off, pieces[i].in, pieces[i].bytes);
+        *pieces[i].dev = (char*)a.dev + off;
         off += (pieces[i].bytes + 255) & ~(size_t)255;
         staged_end = off;
     }
     if (staged_end) HIP_TRY(h, hipMemcpyAsync(a.dev, a.host, staged_end, hipMemcpyHostToDevice, h->copy_stream));
     for (int i = 0; i < n; ++i) {
         if (!direct[i]) continue;
-        HIP_TRY(h, hipMemcpyAsync((char*)a.dev + off, pieces[i].src, pieces[i].bytes, hipMemcpyHostToDevice, h->copy_stream));
-        *pieces[i].dev_out = (char*)a.dev + off;
+        HIP_TRY(h, hipMemcpyAsync((char*)a.dev + off, pieces[i].in, pieces[i].bytes, hipMemcpyHostToDevice, h->copy_stream));
+        *pieces[i].dev = (char*)a.dev + off;
         off += (pieces[i].bytes + 255) & ~(size_t)255;
         ++h->async_direct;
     }
@@ -1049,10 +1122,308 @@ int async_end(fbus_ekf_t h, fbus_ekf::AsyncSlot* a, int rc)
     return rc;
 }
 
+// DEV: the caller's pointers are device pointers and the launch takes them as they are.  STAGED: piece i goes through staging slot i
+// (inputs copied in, outputs copied back) and the call returns when the stream has drained -- the staging buffers and the caller's
+// arrays are free again.  ASYNC: the inputs go through the pinned ring and nothing waits.  `go` launches with the pieces' device pointers.
+enum Transport { DEV, STAGED, ASYNC };
+template <typename GO>
+int run_pieces(fbus_ekf_t h, Transport t, Piece* pc, int n, GO go)
+{
+    if (t == DEV) {
+        for (int i = 0; i < n; ++i) *pc[i].dev = pc[i].in ? pc[i].in : pc[i].out;
+        return go();
+    }
+    int rc;
+    if (t == ASYNC) {
+        fbus_ekf::AsyncSlot* a;
+        if ((rc = async_begin(h, pc, n, &a)) != FBUS_OK) return rc;
+        return async_end(h, a, go());
+    }
+    for (int i = 0; i < n; ++i) {
+        *pc[i].dev = nullptr;
+        if (pc[i].bytes == 0) continue;
+        if ((rc = ensure_stage(h, i, pc[i].bytes)) != FBUS_OK) return rc;
+        if (pc[i].in) HIP_TRY(h, hipMemcpyAsync(h->stage[i], pc[i].in, pc[i].bytes, hipMemcpyHostToDevice, h->stream));
+        else if (pc[i].zero) HIP_TRY(h, hipMemsetAsync(h->stage[i], 0, pc[i].bytes, h->stream));
+        *pc[i].dev = h->stage[i];
+    }
+    if ((rc = go()) != FBUS_OK) return rc;
+    for (int i = 0; i < n; ++i)
+        if (pc[i].out && pc[i].bytes) HIP_TRY(h, hipMemcpyAsync(pc[i].out, h->stage[i], pc[i].bytes, hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));      // the staging buffers are reused by the next host call, the host arrays by the caller
+    return FBUS_OK;
+}
+
 size_t record_elems(int dtype, int N)
 {
     if (dtype == 32) return N == 18 ? Rec<float, 18>::NRECP : Rec<float, 15>::NRECP;
     return N == 18 ? Rec<double, 18>::NRECP : Rec<double, 15>::NRECP;
+}
+
+// ---- the updates: check, describe the arrays, run through the transport ---------------------------------------------------------------
+int predict_any(fbus_ekf_t h, Transport t, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
+{
+    DeviceGuard guard_(h);
+    const int rc = check_predict(h, K, accel, gyro, dt);
+    if (rc != FBUS_OK) return rc;
+    const size_t es = esize(h), B = (size_t)h->B;
+    const void *da, *dg, *dd;
+    Piece pc[3] = { in_piece(accel, (size_t)K * B * 3 * es, &da), in_piece(gyro, (size_t)K * B * 3 * es, &dg),
+                    in_piece(dt, (size_t)K * (dt_per_filter ? B : 1) * es, &dd) };
+    return run_pieces(h, t, pc, 3, [&] { return launch_predict(h, K, da, dg, dd, dt_per_filter); });
+}
+
+// The arrays of a measurement update on the device: ids [B][M], a / b [B][M][wa / wb] in the record type (pos, quat: 3, 4; left, right:
+// 8 or 12, 8), skip [B], and an _nis form's outputs nis [B] in the record type, dof [B].  Absent arrays (b, skip, nis, dof; b_unused:
+// `right` beside corner positions, which the device forms hand on as it is) take no bytes.
+struct RowsDev { const void *ids, *a, *b, *skip; void *nis, *dof; };
+void rows_pieces(const fbus_ekf* h, Piece* pc, RowsDev& d, int M, const void* ids, const void* a, size_t wa, const void* b, size_t wb,
+                 bool b_unused, const void* skip, void* nis, int32_t* dof)
+{
+    const size_t es = esize(h), BM = (size_t)h->B * M;
+    pc[0] = in_piece(ids, BM * sizeof(int32_t), &d.ids);
+    pc[1] = in_piece(a, BM * wa * es, &d.a);
+    pc[2] = in_piece(b, b_unused ? 0 : BM * wb * es, &d.b);
+    pc[3] = in_piece(skip, (size_t)h->B, &d.skip);
+    pc[4] = out_piece(nis, (size_t)h->B * es, &d.nis);
+    pc[5] = out_piece(dof, (size_t)h->B * sizeof(int32_t), &d.dof);
+}
+// nis: an _nis form (its outputs may still be null)
+int correct_any(fbus_ekf_t h, Transport t, bool nis, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
+                const uint8_t* skip, void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const int rc = check_pose(h, "fbus_ekf_correct_nis", nis, M, ids, pos, quat, mode);
+    if (rc != FBUS_OK) return rc;
+    Piece pc[6];
+    RowsDev d;
+    rows_pieces(h, pc, d, M, ids, pos, 3, quat, 4, false, skip, out_nis, out_dof);
+    return run_pieces(h, t, pc, 6, [&] {
+        const NisDst nd{ d.nis, (int32_t*)d.dof };
+        return launch_correct(h, M, (const int32_t*)d.ids, d.a, d.b, mode, (const uint8_t*)d.skip, nis ? &nd : nullptr);
+    });
+}
+int correct_pixels_any(fbus_ekf_t h, Transport t, bool nis, int M, const int32_t* ids, const void* left, const void* right,
+                       const uint8_t* skip, void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const int rc = check_pixels(h, nis ? "fbus_ekf_correct_pixels_nis" : "fbus_ekf_correct_pixels", nis, t == DEV, M, ids, left, right);
+    if (rc != FBUS_OK) return rc;
+    Piece pc[6];
+    RowsDev d;
+    rows_pieces(h, pc, d, M, ids, left, 8, right, 8, false, skip, out_nis, out_dof);
+    return run_pieces(h, t, pc, 6, [&] {
+        const NisDst nd{ d.nis, (int32_t*)d.dof };
+        return nis ? launch_correct_pixels_nis(h, M, (const int32_t*)d.ids, d.a, d.b, (const uint8_t*)d.skip, nd)
+                   : launch_correct_pixels(h, M, (const int32_t*)d.ids, d.a, d.b, (const uint8_t*)d.skip);
+    });
+}
+int correct_corners_any(fbus_ekf_t h, Transport t, bool nis, int M, const int32_t* ids, const void* left, const void* right,
+                        int geometry, int mode, const uint8_t* skip, void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const int rc = check_corners(h, nis ? "fbus_ekf_correct_corners_nis" : "fbus_ekf_correct_corners", nis, t == DEV, M, ids, left, right,
+                                 geometry, mode);
+    if (rc != FBUS_OK) return rc;
+    const bool c3d = geometry == FBUS_VIS_CORNERS3D;
+    Piece pc[6];
+    RowsDev d;
+    rows_pieces(h, pc, d, M, ids, left, c3d ? 12 : 8, right, 8, c3d, skip, out_nis, out_dof);
+    return run_pieces(h, t, pc, 6, [&] {
+        const NisDst nd{ d.nis, (int32_t*)d.dof };
+        return launch_correct_corners(h, M, (const int32_t*)d.ids, d.a, d.b, geometry, mode, (const uint8_t*)d.skip, nis ? &nd : nullptr);
+    });
+}
+
+// ---- frames and windows ------------------------------------------------------------------------------------------------------------------
+// The device arrays of a frame or of a window: IMU samples [samples][B][3], dt [samples] or [samples][B]; per frame ids [B][M],
+// a / b [B][M][wa / wb] (pos, quat: 3, 4; left, right: 8 or 12, 8), skip [B]
+struct FrameArrays { const void *accel, *gyro, *dt; int per, M; const int32_t* ids; const void *a, *b; size_t wa, wb; const uint8_t* skip; };
+// frame f of a window whose frames 0 .. f - 1 hold k0 samples (f = 0: the arrays from sample k0 on)
+FrameArrays frame_slice(const fbus_ekf* h, const FrameArrays& w, size_t k0, int f)
+{
+    const size_t es = esize(h), B = (size_t)h->B, fBM = (size_t)f * B * w.M;
+    const auto at = [](const void* p, size_t bytes) { return p ? (const void*)((const char*)p + bytes) : nullptr; };
+    FrameArrays s = w;
+    s.accel = at(w.accel, k0 * B * 3 * es);
+    s.gyro = at(w.gyro, k0 * B * 3 * es);
+    s.dt = at(w.dt, k0 * (w.per ? B : 1) * es);
+    s.ids = (const int32_t*)at(w.ids, fBM * sizeof(int32_t));
+    s.a = at(w.a, fBM * w.wa * es);
+    s.b = at(w.b, fBM * w.wb * es);
+    s.skip = (const uint8_t*)at(w.skip, (size_t)f * B);
+    return s;
+}
+
+// fbus_ekf_frame_dev (fused = false: K predict launches + one correct launch) and fbus_ekf_frame_fused_dev
+int frame_any(fbus_ekf_t h, bool fused, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter, int M,
+              const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
+{
+    DeviceGuard guard_(h);
+    // everything is validated before the first launch: a rejected call must not leave the state advanced by the K predicts
+    int geometry = 0;
+    int rc = check_frames(h, fused ? "fbus_ekf_frame_fused_dev" : "fbus_ekf_frame_dev", 1, &K, std::numeric_limits<int>::max(), nullptr, accel, gyro, dt, KIND_POSE, M, ids, pos, quat,
+                          geometry, mode, nullptr);
+    if (rc != FBUS_OK) return rc;
+    if (fused) return launch_frame(h, K, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    // one event pair around the whole run of K back-to-back predict launches: a pair per launch
+    // would cost ~8 us of stream time each and read ~3 us long; duration / K is the per-launch time
+    const bool sampled = (h->frame_count++ % h->timing_stride) == 0;
+    const int ev = (K > 0 && sampled) ? timing_begin(h, FBUS_KERNEL_PREDICT, K) : -1;
+    h->timing_suspended = true;
+    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
+    for (int k = 0; k < K && rc == FBUS_OK; ++k) {
+        const FrameArrays s = frame_slice(h, w, (size_t)k, 0);
+        rc = launch_predict(h, 1, s.accel, s.gyro, s.dt, dt_per_filter);
+    }
+    timing_end(h, ev);
+    if (rc != FBUS_OK) { h->timing_suspended = false; return rc; }
+    h->timing_suspended = !sampled;
+    if (M > 0) rc = launch_correct(h, M, ids, pos, quat, mode, skip);
+    h->timing_suspended = false;
+    return rc;
+}
+
+// fbus_ekf_frames_fused_dev (tj = null) and fbus_ekf_frames_fused_traj_dev
+int frames_any(fbus_ekf_t h, const char* where, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
+               int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
+               const TrajDst* tj)
+{
+    DeviceGuard guard_(h);
+    unsigned char kc[FBUS_MAX_WINDOW_FRAMES];
+    int geometry = 0;
+    int rc = check_frames(h, where, nframes, kcount, 255, kc, accel, gyro, dt, KIND_POSE, M, ids, pos, quat, geometry, mode, tj);
+    if (rc != FBUS_OK || nframes == 0) return rc;
+    // no resident-record kernel for fp64 and for (Joseph, nearest) -- see launch_frame_t: those windows run frame by frame,
+    // the same arithmetic
+    // (a noise table: the resident window that reads it where noise_resident() says so, else frame by frame through the per-call kernels)
+    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) &&
+                          (!tabled(h) || noise_resident(h));
+    if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
+    // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel
+    const bool team = resident && team_frames(h, mode);
+    if (resident && !team) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, tj);
+    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
+    size_t k0 = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const FrameArrays s = frame_slice(h, w, k0, f);
+        rc = team ? launch_frames(h, 1, kc + f, s.accel, s.gyro, s.dt, dt_per_filter, M, s.ids, s.a, s.b, mode, s.skip)
+                  : launch_frame(h, kc[f], s.accel, s.gyro, s.dt, dt_per_filter, M, s.ids, s.a, s.b, mode, s.skip);
+        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
+        if (rc != FBUS_OK) return rc;
+        k0 += kc[f];
+    }
+    return FBUS_OK;
+}
+
+// fbus_ekf_frame_meas_fused_dev (kcount = &K, nframes = 1, single = true: K may exceed a byte), fbus_ekf_frames_meas_fused_dev (tj = null)
+// and fbus_ekf_frames_meas_fused_traj_dev: one validation, one choice of route
+int frames_meas_any(fbus_ekf_t h, const char* where, bool single, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
+                    const void* dt, int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right,
+                    int geometry, int mode, const uint8_t* skip, const TrajDst* tj)
+{
+    DeviceGuard guard_(h);
+    // everything is validated before the first launch: a rejected call must not leave the state advanced by the predicts
+    unsigned char kc[FBUS_MAX_WINDOW_FRAMES];
+    int rc = check_frames(h, where, nframes, kcount, single ? std::numeric_limits<int>::max() : 255, single ? nullptr : kc, accel, gyro,
+                          dt, kind, M, ids, left, right, geometry, mode, tj);
+    if (rc != FBUS_OK || nframes == 0) return rc;
+    if (single && kcount[0] > 255) {          // (the resident kernel counts a frame's samples in a byte)
+        rc = launch_predict(h, kcount[0], accel, gyro, dt, dt_per_filter);
+        if (rc == FBUS_OK && M > 0)
+            rc = kind == FBUS_MEAS_PIXELS ? launch_correct_pixels(h, M, ids, left, right, skip)
+                                          : launch_correct_corners(h, M, ids, left, right, geometry, mode, skip);
+        return rc;
+    }
+    if (single) kc[0] = (unsigned char)kcount[0];
+    // the resident window kernel where the frame form takes the resident kernel (fp32 records, one wave per tile); elsewhere frame by
+    // frame through the frame form's routes -- the same arithmetic (with a trajectory: each frame's rows by the snapshot kernel)
+    if (single || (nframes > 1 && frame_meas_is_resident(h, kind, M, mode)))
+        return launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, tj);
+    const bool c3d = kind == FBUS_MEAS_CORNERS && geometry == FBUS_VIS_CORNERS3D;
+    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, left, right, c3d ? (size_t)12 : (size_t)8, 8, skip };
+    size_t k0 = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const FrameArrays s = frame_slice(h, w, k0, f);
+        rc = launch_frame_meas(h, 1, kc + f, s.accel, s.gyro, s.dt, dt_per_filter, kind, M, s.ids, s.a, s.b, geometry, mode, s.skip);
+        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
+        if (rc != FBUS_OK) return rc;
+        k0 += kc[f];
+    }
+    return FBUS_OK;
+}
+
+// ---- the element-wise entry points --------------------------------------------------------------------------------------------------------
+int marker_pose_any(fbus_ekf_t h, Transport t, int n, int geometry, const void* left, const void* right, void* pos, void* quat,
+                    void* corners3d)
+{
+    DeviceGuard guard_(h);
+    if (!h || n < 1 || !left || !pos || !quat) return FBUS_ERR_INVALID;
+    if (!geometry_ok(geometry)) return FBUS_ERR_UNSUPPORTED;
+    const bool c3d = geometry == FBUS_VIS_CORNERS3D;
+    if (!c3d && !right) return FBUS_ERR_INVALID;
+    const size_t es = esize(h), nn = (size_t)n;
+    const void *dl, *dr;
+    void *dp, *dq, *dc;
+    Piece pc[5] = { in_piece(left, nn * (c3d ? 12 : 8) * es, &dl), in_piece(right, c3d ? 0 : nn * 8 * es, &dr),
+                    out_piece(pos, nn * 3 * es, &dp), out_piece(quat, nn * 4 * es, &dq), out_piece(corners3d, nn * 12 * es, &dc) };
+    return run_pieces(h, t, pc, 5, [&] {
+        return h->dtype == 32 ? launch_marker_pose_t<float>(h, n, geometry, dl, dr, dp, dq, dc)
+                              : launch_marker_pose_t<double>(h, n, geometry, dl, dr, dp, dq, dc);
+    });
+}
+
+int init_gravity_bias_any(fbus_ekf_t h, Transport t, int T, const void* accel, const void* gyro)
+{
+    DeviceGuard guard_(h);
+    if (!h || T < 1 || !accel || !gyro) return FBUS_ERR_INVALID;
+    const size_t bytes = (size_t)T * h->B * 3 * esize(h);
+    const void *da, *dg;
+    Piece pc[2] = { in_piece(accel, bytes, &da), in_piece(gyro, bytes, &dg) };
+    return run_pieces(h, t, pc, 2, [&] { return do_init_gb(h, T, da, dg); });
+}
+
+// fbus_ekf_pose_init (what = FBUS_POSE_INIT / FBUS_POSE_RESET) and fbus_ekf_vision_only_pose (what = POSE_VISION: out_pose [B][7], the
+// state is not touched; the kernel writes the filters that see a marker, the staged copy starts as zeros)
+constexpr int POSE_VISION = 2;
+int pose_init_any(fbus_ekf_t h, Transport t, int M, const int32_t* ids, const void* pos, const void* quat, int what, const uint8_t* mask,
+                  void* out_pose)
+{
+    DeviceGuard guard_(h);
+    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
+    if (what == POSE_VISION ? !out_pose : (what != FBUS_POSE_INIT && what != FBUS_POSE_RESET)) return FBUS_ERR_INVALID;
+    const size_t es = esize(h), B = (size_t)h->B;
+    RowsDev d;
+    Piece pc[6];
+    rows_pieces(h, pc, d, M, ids, pos, 3, quat, 4, false, mask, nullptr, nullptr);
+    void* dout;
+    pc[4] = out_piece(out_pose, B * 7 * es, &dout, true);         // (in the place of the nis output, which this call does not have)
+    return run_pieces(h, t, pc, 5, [&] { return do_pose_init(h, M, (const int32_t*)d.ids, d.a, d.b, what, (const uint8_t*)d.skip, dout); });
+}
+
+int imu_ema_any(fbus_ekf_t h, Transport t, int T, void* accel, void* gyro, int restart)
+{
+    DeviceGuard guard_(h);
+    if (!h || T < 0 || (T > 0 && (!accel || !gyro))) return FBUS_ERR_INVALID;
+    if (!h->d_ema_carry) HIP_TRY(h, hipMalloc(&h->d_ema_carry, (size_t)h->B * 6 * esize(h)));
+    if (restart) h->ema_has_carry = false;
+    if (T == 0) return FBUS_OK;
+    const size_t bytes = (size_t)T * h->B * 3 * esize(h);
+    void *da, *dg;
+    Piece pc[2] = { inout_piece(accel, bytes, &da), inout_piece(gyro, bytes, &dg) };
+    return run_pieces(h, t, pc, 2, [&] {
+        const int grid = (h->B + 255) / 256;
+        if (h->dtype == 32)
+            hipLaunchKernelGGL((imu_ema_kernel<float>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (float*)da, (float*)dg,
+                               (float*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
+        else
+            hipLaunchKernelGGL((imu_ema_kernel<double>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (double*)da, (double*)dg,
+                               (double*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
+        HIP_TRY(h, hipGetLastError());
+        h->ema_has_carry = true;
+        return (int)FBUS_OK;
+    });
 }
 
 }  // namespace
@@ -1384,14 +1755,9 @@ int fbus_ekf_set_state(fbus_ekf_t h, const void* nominal, const void* rot, const
     if (!h) return FBUS_ERR_INVALID;
     const size_t es = esize(h), B = (size_t)h->B, N = (size_t)h->N;
     const void *dn, *dr, *dP, *dp;
-    int rc;
-    if ((rc = stage_in(h, 0, nominal, B * 19 * es, &dn)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, rot, B * 9 * es, &dr)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, P, B * N * N * es, &dP)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, prev_id, B * 4, &dp)) != FBUS_OK) return rc;
-    if ((rc = do_pack(h, dn, dr, dP, (const int32_t*)dp)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));    // host buffers may be reused by the caller
-    return FBUS_OK;
+    Piece pc[4] = { in_piece(nominal, B * 19 * es, &dn), in_piece(rot, B * 9 * es, &dr), in_piece(P, B * N * N * es, &dP),
+                    in_piece(prev_id, B * sizeof(int32_t), &dp) };
+    return run_pieces(h, STAGED, pc, 4, [&] { return do_pack(h, dn, dr, dP, (const int32_t*)dp); });
 }
 
 int fbus_ekf_get_state(fbus_ekf_t h, void* nominal, void* rot, void* P, int32_t* prev_id)
@@ -1399,19 +1765,10 @@ int fbus_ekf_get_state(fbus_ekf_t h, void* nominal, void* rot, void* P, int32_t*
     DeviceGuard guard_(h);
     if (!h) return FBUS_ERR_INVALID;
     const size_t es = esize(h), B = (size_t)h->B, N = (size_t)h->N;
-    int rc;
-    if (nominal && (rc = ensure_stage(h, 0, B * 19 * es)) != FBUS_OK) return rc;
-    if (rot && (rc = ensure_stage(h, 1, B * 9 * es)) != FBUS_OK) return rc;
-    if (P && (rc = ensure_stage(h, 2, B * N * N * es)) != FBUS_OK) return rc;
-    if (prev_id && (rc = ensure_stage(h, 3, B * 4)) != FBUS_OK) return rc;
-    if ((rc = do_unpack(h, nominal ? h->stage[0] : nullptr, rot ? h->stage[1] : nullptr, P ? h->stage[2] : nullptr,
-                        prev_id ? (int32_t*)h->stage[3] : nullptr)) != FBUS_OK) return rc;
-    if (nominal) HIP_TRY(h, hipMemcpyAsync(nominal, h->stage[0], B * 19 * es, hipMemcpyDeviceToHost, h->stream));
-    if (rot) HIP_TRY(h, hipMemcpyAsync(rot, h->stage[1], B * 9 * es, hipMemcpyDeviceToHost, h->stream));
-    if (P) HIP_TRY(h, hipMemcpyAsync(P, h->stage[2], B * N * N * es, hipMemcpyDeviceToHost, h->stream));
-    if (prev_id) HIP_TRY(h, hipMemcpyAsync(prev_id, h->stage[3], B * 4, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    void *dn, *dr, *dP, *dp;
+    Piece pc[4] = { out_piece(nominal, B * 19 * es, &dn), out_piece(rot, B * 9 * es, &dr), out_piece(P, B * N * N * es, &dP),
+                    out_piece(prev_id, B * sizeof(int32_t), &dp) };
+    return run_pieces(h, STAGED, pc, 4, [&] { return do_unpack(h, dn, dr, dP, (int32_t*)dp); });
 }
 
 int fbus_ekf_reset_cov(fbus_ekf_t h)
@@ -1647,83 +2004,42 @@ int fbus_ekf_attach_records(fbus_ekf_t h, void* dev_ptr, size_t total_bytes)
 
 int fbus_ekf_predict_n_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    DeviceGuard guard_(h);
-    if (!h || !accel || !gyro || !dt || K < 1) return FBUS_ERR_INVALID;
-    return launch_predict(h, K, accel, gyro, dt, dt_per_filter);
+    return predict_any(h, DEV, K, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_predict_dev(fbus_ekf_t h, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    DeviceGuard guard_(h);
-    return fbus_ekf_predict_n_dev(h, 1, accel, gyro, dt, dt_per_filter);
+    return predict_any(h, DEV, 1, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_predict_n(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    DeviceGuard guard_(h);
-    if (!h || !accel || !gyro || !dt || K < 1) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *da, *dg, *dd;
-    int rc;
-    if ((rc = stage_in(h, 0, accel, (size_t)K * B * 3 * es, &da)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, gyro, (size_t)K * B * 3 * es, &dg)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, dt, (size_t)K * (dt_per_filter ? B : 1) * es, &dd)) != FBUS_OK) return rc;
-    if ((rc = launch_predict(h, K, da, dg, dd, dt_per_filter)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));    // staging buffers are reused by the next host call
-    return FBUS_OK;
+    return predict_any(h, STAGED, K, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_predict(fbus_ekf_t h, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    DeviceGuard guard_(h);
-    return fbus_ekf_predict_n(h, 1, accel, gyro, dt, dt_per_filter);
+    return predict_any(h, STAGED, 1, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_predict_n_async(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    DeviceGuard guard_(h);
-    if (!h || !accel || !gyro || !dt || K < 1) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *da, *dg, *dd;
-    AsyncPiece pc[3] = { { accel, (size_t)K * B * 3 * es, &da }, { gyro, (size_t)K * B * 3 * es, &dg },
-                         { dt, (size_t)K * (dt_per_filter ? B : 1) * es, &dd } };
-    fbus_ekf::AsyncSlot* a;
-    int rc = async_begin(h, pc, 3, &a);
-    if (rc != FBUS_OK) return rc;
-    return async_end(h, a, launch_predict(h, K, da, dg, dd, dt_per_filter));
+    return predict_any(h, ASYNC, K, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_predict_async(fbus_ekf_t h, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
 {
-    return fbus_ekf_predict_n_async(h, 1, accel, gyro, dt, dt_per_filter);
+    return predict_any(h, ASYNC, 1, accel, gyro, dt, dt_per_filter);
 }
 
 int fbus_ekf_correct_async(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dp, *dq, *ds;
-    AsyncPiece pc[4] = { { ids, B * M * 4, &di }, { pos, B * M * 3 * es, &dp }, { quat, B * M * 4 * es, &dq }, { skip, skip ? B : 0, &ds } };
-    fbus_ekf::AsyncSlot* a;
-    int rc = async_begin(h, pc, 4, &a);
-    if (rc != FBUS_OK) return rc;
-    return async_end(h, a, launch_correct(h, M, (const int32_t*)di, dp, dq, mode, (const uint8_t*)ds));
+    return correct_any(h, ASYNC, false, M, ids, pos, quat, mode, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct_pixels_async(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dl, *dr, *ds;
-    AsyncPiece pc[4] = { { ids, B * M * 4, &di }, { left, B * M * 8 * es, &dl }, { right, right ? B * M * 8 * es : 0, &dr }, { skip, skip ? B : 0, &ds } };
-    fbus_ekf::AsyncSlot* a;
-    int rc = async_begin(h, pc, 4, &a);
-    if (rc != FBUS_OK) return rc;
-    return async_end(h, a, launch_correct_pixels(h, M, (const int32_t*)di, dl, dr, (const uint8_t*)ds));
+    return correct_pixels_any(h, ASYNC, false, M, ids, left, right, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_async_inputs_consumed(fbus_ekf_t h)
@@ -1758,85 +2074,37 @@ int fbus_ekf_host_unregister(void* ptr)
 int fbus_ekf_correct_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
                          const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    return launch_correct(h, M, ids, pos, quat, mode, skip);
+    return correct_any(h, DEV, false, M, ids, pos, quat, mode, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode,
                      const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dp, *dq, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, pos, B * M * 3 * es, &dp)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, quat, B * M * 4 * es, &dq)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
-    if ((rc = launch_correct(h, M, (const int32_t*)di, dp, dq, mode, (const uint8_t*)ds)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_any(h, STAGED, false, M, ids, pos, quat, mode, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct_corners_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
                                  int geometry, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D)
-        return FBUS_ERR_UNSUPPORTED;
-    if (geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    return launch_correct_corners(h, M, ids, left, right, geometry, mode, skip);
+    return correct_corners_any(h, DEV, false, M, ids, left, right, geometry, mode, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
                              int geometry, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const size_t lw = geometry == FBUS_VIS_CORNERS3D ? 12 : 8;
-    const void *di, *dl, *dr, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, left, B * M * lw * es, &dl)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, geometry == FBUS_VIS_CORNERS3D ? nullptr : right, B * M * 8 * es, &dr)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_correct_corners_dev(h, M, (const int32_t*)di, dl, dr, geometry, mode, (const uint8_t*)ds)) != FBUS_OK)
-        return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_corners_any(h, STAGED, false, M, ids, left, right, geometry, mode, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct_pixels_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
                                 const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
-    return launch_correct_pixels(h, M, ids, left, right, skip);
+    return correct_pixels_any(h, DEV, false, M, ids, left, right, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_correct_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right,
                             const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dl, *dr, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * sizeof(int32_t), &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, left, B * M * 8 * es, &dl)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, right, right ? B * M * 8 * es : 0, &dr)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, skip ? B : 0, &ds)) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_correct_pixels_dev(h, M, (const int32_t*)di, dl, dr, (const uint8_t*)ds)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_pixels_any(h, STAGED, false, M, ids, left, right, skip, nullptr, nullptr);
 }
 
 int fbus_ekf_set_gate(fbus_ekf_t h, int n, const double* thresholds)
@@ -2045,103 +2313,37 @@ int fbus_ekf_get_noise(fbus_ekf_t h, double* table)
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                              void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    const int rows = h->prm.dialect == FBUS_DIALECT_CPP ? 7 : 3;
-    const int rc = check_gate_dof(h, rows * (mode == FBUS_MODE_NEAREST ? 1 : M), "fbus_ekf_correct_nis");
-    return rc != FBUS_OK ? rc : launch_correct_nis(h, M, ids, pos, quat, mode, skip, nis, dof);
+    return correct_any(h, DEV, true, M, ids, pos, quat, mode, skip, nis, dof);
 }
 
 int fbus_ekf_correct_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                          void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dp, *dq, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, pos, B * M * 3 * es, &dp)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, quat, B * M * 4 * es, &dq)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
-    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
-    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_correct_nis_dev(h, M, (const int32_t*)di, dp, dq, mode, (const uint8_t*)ds, nis ? h->stage[4] : nullptr,
-                                       dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK) return rc;
-    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
-    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_any(h, STAGED, true, M, ids, pos, quat, mode, skip, nis, dof);
 }
 
 int fbus_ekf_correct_pixels_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
                                     void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
-    const int rc = check_gate_dof(h, M * 8 * (right ? 2 : 1), "fbus_ekf_correct_pixels_nis");
-    return rc != FBUS_OK ? rc : launch_correct_pixels_nis(h, M, ids, left, right, skip, nis, dof);
+    return correct_pixels_any(h, DEV, true, M, ids, left, right, skip, nis, dof);
 }
 
 int fbus_ekf_correct_pixels_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, const uint8_t* skip,
                                 void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dl, *dr, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * sizeof(int32_t), &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, left, B * M * 8 * es, &dl)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, right, right ? B * M * 8 * es : 0, &dr)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, skip ? B : 0, &ds)) != FBUS_OK) return rc;
-    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
-    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_correct_pixels_nis_dev(h, M, (const int32_t*)di, dl, dr, (const uint8_t*)ds, nis ? h->stage[4] : nullptr,
-                                              dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK) return rc;
-    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
-    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_pixels_any(h, STAGED, true, M, ids, left, right, skip, nis, dof);
 }
 
 int fbus_ekf_correct_corners_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                                      int mode, const uint8_t* skip, void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D)
-        return FBUS_ERR_UNSUPPORTED;
-    if (geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    const int rc = check_gate_dof(h, 12 * (mode == FBUS_MODE_NEAREST ? 1 : M), "fbus_ekf_correct_corners_nis");
-    return rc != FBUS_OK ? rc : launch_correct_corners_nis(h, M, ids, left, right, geometry, mode, skip, nis, dof);
+    return correct_corners_any(h, DEV, true, M, ids, left, right, geometry, mode, skip, nis, dof);
 }
 
 int fbus_ekf_correct_corners_nis(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                                  int mode, const uint8_t* skip, void* nis, int32_t* dof)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !left || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), B = (size_t)h->B;
-    const size_t lw = geometry == FBUS_VIS_CORNERS3D ? 12 : 8;
-    const void *di, *dl, *dr, *ds;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, left, B * M * lw * es, &dl)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, geometry == FBUS_VIS_CORNERS3D ? nullptr : right, B * M * 8 * es, &dr)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, skip, B, &ds)) != FBUS_OK) return rc;
-    if (nis && (rc = ensure_stage(h, 4, B * es)) != FBUS_OK) return rc;
-    if (dof && (rc = ensure_stage(h, 5, B * sizeof(int32_t))) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_correct_corners_nis_dev(h, M, (const int32_t*)di, dl, dr, geometry, mode, (const uint8_t*)ds,
-                                               nis ? h->stage[4] : nullptr, dof ? (int32_t*)h->stage[5] : nullptr)) != FBUS_OK)
-        return rc;
-    if (nis) HIP_TRY(h, hipMemcpyAsync(nis, h->stage[4], B * es, hipMemcpyDeviceToHost, h->stream));
-    if (dof) HIP_TRY(h, hipMemcpyAsync(dof, h->stage[5], B * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return correct_corners_any(h, STAGED, true, M, ids, left, right, geometry, mode, skip, nis, dof);
 }
 
 int fbus_ekf_get_applied(fbus_ekf_t h, uint8_t* applied_host)
@@ -2156,107 +2358,23 @@ int fbus_ekf_get_applied(fbus_ekf_t h, uint8_t* applied_host)
 int fbus_ekf_frame_fused_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                              int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    if (!h || K < 0 || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (K > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
-    if (M > 0 && (!ids || !pos || !quat)) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    return launch_frame(h, K, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    return frame_any(h, true, K, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
 }
 
 int fbus_ekf_frame_meas_fused_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                                   int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,
                                   const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    // everything is validated before the first launch: a rejected call must not leave the state advanced by the K predicts
-    if (!h || K < 0 || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (kind != FBUS_MEAS_PIXELS && kind != FBUS_MEAS_CORNERS) return FBUS_ERR_UNSUPPORTED;
-    if (K > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
-    if (M > 0 && (!ids || !left)) return FBUS_ERR_INVALID;
-    if (kind == FBUS_MEAS_PIXELS) {
-        if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
-        geometry = FBUS_VIS_REFRACTIVE; mode = FBUS_MODE_STACKED;          // (not used by the pixel rows)
-    } else {
-        if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D) return FBUS_ERR_UNSUPPORTED;
-        if (M > 0 && geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
-        if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    }
-    // (advisor, round 5) on every route, not only the resident one: the per-call updates behind the fall-back routes (fp64 records, team /
-    // split forms, K > 255) refuse unaligned image points AFTER the predicts have run
-    if (M > 0 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_frame_meas_fused_dev: left / right must be 16-byte aligned device pointers");
-    if (K > 255) {          // (the resident kernel counts a frame's samples in a byte)
-        int rc = launch_predict(h, K, accel, gyro, dt, dt_per_filter);
-        if (rc == FBUS_OK && M > 0)
-            rc = kind == FBUS_MEAS_PIXELS ? launch_correct_pixels(h, M, ids, left, right, skip)
-                                          : launch_correct_corners(h, M, ids, left, right, geometry, mode, skip);
-        return rc;
-    }
-    const unsigned char kc1 = (unsigned char)K;
-    return launch_frame_meas(h, 1, &kc1, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip);
-}
-
-// fbus_ekf_frames_meas_fused_dev (tj = null) and fbus_ekf_frames_meas_fused_traj_dev: one validation, one choice of route
-static int frames_meas_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
-                            int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
-                            int mode, const uint8_t* skip, const TrajDst* tj)
-{
-    if (!h || nframes < 0 || nframes > FBUS_MAX_WINDOW_FRAMES || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (kind != FBUS_MEAS_PIXELS && kind != FBUS_MEAS_CORNERS) return FBUS_ERR_UNSUPPORTED;
-    if (nframes > 0 && !kcount) return FBUS_ERR_INVALID;
-    unsigned char kc[FBUS_MAX_WINDOW_FRAMES];
-    size_t total = 0;
-    for (int f = 0; f < nframes; ++f) {
-        if (kcount[f] < 0 || kcount[f] > 255) return FBUS_ERR_INVALID;
-        kc[f] = (unsigned char)kcount[f];
-        total += (size_t)kcount[f];
-    }
-    if (total > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
-    if (M > 0 && nframes > 0 && (!ids || !left)) return FBUS_ERR_INVALID;
-    if (kind == FBUS_MEAS_PIXELS) {
-        if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, "r_pix must be positive");
-        geometry = FBUS_VIS_REFRACTIVE; mode = FBUS_MODE_STACKED;
-    } else {
-        if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D) return FBUS_ERR_UNSUPPORTED;
-        if (M > 0 && nframes > 0 && geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
-        if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    }
-    if (nframes == 0) return FBUS_OK;
-    // every frame's arrays start a multiple of 16 bytes behind the first (B M x 32 / 48 bytes x element size): one check covers the window
-    if (M > 0 && ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right)) & 15) != 0)
-        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_frames_meas_fused_dev: left / right must be 16-byte aligned device pointers");
-    if (tj) {
-        const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_meas_fused_traj_dev");
-        if (rc != FBUS_OK) return rc;
-    }
-    // the resident window kernel where the frame form takes the resident kernel (fp32 records, one wave per tile); elsewhere frame by
-    // frame through the frame entry point's routes -- the same arithmetic (with a trajectory: each frame's rows by the snapshot kernel)
-    if (nframes > 1 && frame_meas_is_resident(h, kind, M, mode))
-        return launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, tj);
-    const size_t es = esize(h), B = (size_t)h->B;
-    const size_t lw = (kind == FBUS_MEAS_CORNERS && geometry == FBUS_VIS_CORNERS3D) ? 12 : 8;
-    size_t k0 = 0;
-    int rc2 = FBUS_OK;
-    for (int f = 0; f < nframes; ++f) {
-        const int rc = launch_frame_meas(h, 1, kc + f, (const char*)accel + k0 * B * 3 * es, (const char*)gyro + k0 * B * 3 * es,
-                                         (const char*)dt + k0 * (dt_per_filter ? B : 1) * es, dt_per_filter, kind, M,
-                                         ids ? ids + (size_t)f * B * M : nullptr, left ? (const char*)left + (size_t)f * B * M * lw * es : nullptr,
-                                         right ? (const char*)right + (size_t)f * B * M * 8 * es : nullptr, geometry, mode,
-                                         skip ? skip + (size_t)f * B : nullptr);
-        if (rc != FBUS_OK) return rc;
-        if (tj && (rc2 = snapshot_row(h, *tj, f)) != FBUS_OK) return rc2;
-        k0 += kc[f];
-    }
-    return FBUS_OK;
+    return frames_meas_any(h, "fbus_ekf_frame_meas_fused_dev", true, 1, &K, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right,
+                           geometry, mode, skip, nullptr);
 }
 
 int fbus_ekf_frames_meas_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
                                    int dt_per_filter, int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry,
                                    int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    return frames_meas_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, nullptr);
+    return frames_meas_any(h, "fbus_ekf_frames_meas_fused_dev", false, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids, left,
+                           right, geometry, mode, skip, nullptr);
 }
 
 int fbus_ekf_frames_meas_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
@@ -2264,70 +2382,18 @@ int fbus_ekf_frames_meas_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t
                                         const void* right, int geometry, int mode, const uint8_t* skip, void* out_nominal, void* out_pdiag,
                                         uint8_t* out_applied)
 {
-    DeviceGuard guard_(h);
     const TrajDst tj{ out_nominal, out_pdiag, out_applied };
     const bool any = out_nominal || out_pdiag || out_applied;
-    return frames_meas_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip,
-                            any ? &tj : nullptr);
-}
-
-// fbus_ekf_frames_fused_dev (tj = null) and fbus_ekf_frames_fused_traj_dev
-static int frames_impl(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro, const void* dt,
-                       int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
-                       const TrajDst* tj)
-{
-    if (!h || nframes < 0 || nframes > FBUS_MAX_WINDOW_FRAMES || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (nframes > 0 && !kcount) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    unsigned char kc[FBUS_MAX_WINDOW_FRAMES];
-    size_t total = 0;
-    for (int f = 0; f < nframes; ++f) {
-        if (kcount[f] < 0 || kcount[f] > 255) return FBUS_ERR_INVALID;
-        kc[f] = (unsigned char)kcount[f];
-        total += (size_t)kcount[f];
-    }
-    if (total > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
-    if (M > 0 && nframes > 0 && (!ids || !pos || !quat)) return FBUS_ERR_INVALID;
-    if (nframes == 0) return FBUS_OK;
-    // no resident-record kernel for fp64 and for (Joseph, nearest) -- see launch_frame_t: those windows run frame by frame,
-    // the same arithmetic
-    if (tj) {
-        const int rc = check_traj(h, *tj, nframes, "fbus_ekf_frames_fused_traj_dev");
-        if (rc != FBUS_OK) return rc;
-    }
-    // (a noise table: the resident window that reads it where noise_resident() says so, else frame by frame through the per-call kernels)
-    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) &&
-                          (!tabled(h) || noise_resident(h));
-    if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
-    // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
-    // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel
-    const bool team = resident && team_frames(h, mode);
-    if (resident && !team) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, tj);
-    const size_t es = esize(h), B = (size_t)h->B;
-    size_t k0 = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const char* a = (const char*)accel + k0 * B * 3 * es;
-        const char* g = (const char*)gyro + k0 * B * 3 * es;
-        const char* d = (const char*)dt + k0 * (dt_per_filter ? B : 1) * es;
-        const int32_t* fi = ids ? ids + (size_t)f * B * M : nullptr;
-        const char* fp = pos ? (const char*)pos + (size_t)f * B * M * 3 * es : nullptr;
-        const char* fq = quat ? (const char*)quat + (size_t)f * B * M * 4 * es : nullptr;
-        const uint8_t* fs = skip ? skip + (size_t)f * B : nullptr;
-        int rc = team ? launch_frames(h, 1, kc + f, a, g, d, dt_per_filter, M, fi, fp, fq, mode, fs)
-                      : launch_frame(h, kc[f], a, g, d, dt_per_filter, M, fi, fp, fq, mode, fs);
-        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
-        if (rc != FBUS_OK) return rc;
-        k0 += kc[f];
-    }
-    return FBUS_OK;
+    return frames_meas_any(h, "fbus_ekf_frames_meas_fused_traj_dev", false, nframes, kcount, accel, gyro, dt, dt_per_filter, kind, M, ids,
+                           left, right, geometry, mode, skip, any ? &tj : nullptr);
 }
 
 int fbus_ekf_frames_fused_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
                               const void* dt, int dt_per_filter, int M, const int32_t* ids, const void* pos,
                               const void* quat, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    return frames_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, nullptr);
+    return frames_any(h, "fbus_ekf_frames_fused_dev", nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip,
+                      nullptr);
 }
 
 int fbus_ekf_frames_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kcount, const void* accel, const void* gyro,
@@ -2335,10 +2401,10 @@ int fbus_ekf_frames_fused_traj_dev(fbus_ekf_t h, int nframes, const int32_t* kco
                                    const void* quat, int mode, const uint8_t* skip, void* out_nominal, void* out_pdiag,
                                    uint8_t* out_applied)
 {
-    DeviceGuard guard_(h);
     const TrajDst tj{ out_nominal, out_pdiag, out_applied };
     const bool any = out_nominal || out_pdiag || out_applied;
-    return frames_impl(h, nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, any ? &tj : nullptr);
+    return frames_any(h, "fbus_ekf_frames_fused_traj_dev", nframes, kcount, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip,
+                      any ? &tj : nullptr);
 }
 
 int fbus_ekf_snapshot_dev(fbus_ekf_t h, void* nominal, void* pdiag, uint8_t* applied)
@@ -2354,176 +2420,62 @@ int fbus_ekf_snapshot_dev(fbus_ekf_t h, void* nominal, void* pdiag, uint8_t* app
 int fbus_ekf_frame_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                        int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
-    DeviceGuard guard_(h);
-    // everything is validated before the first launch (the same checks as frame_fused_dev): a rejected call must not
-    // leave the state advanced by the K predicts
-    if (!h || K < 0 || M < 0 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (K > 0 && (!accel || !gyro || !dt)) return FBUS_ERR_INVALID;
-    if (M > 0 && (!ids || !pos || !quat)) return FBUS_ERR_INVALID;
-    if (mode != FBUS_MODE_NEAREST && mode != FBUS_MODE_STACKED) return FBUS_ERR_UNSUPPORTED;
-    const size_t es = esize(h), B = (size_t)h->B;
-    // one event pair around the whole run of K back-to-back predict launches: a pair per launch
-    // would cost ~8 us of stream time each and read ~3 us long; duration / K is the per-launch time
-    const bool sampled = (h->frame_count++ % h->timing_stride) == 0;
-    const int ev = (K > 0 && sampled) ? timing_begin(h, FBUS_KERNEL_PREDICT, K) : -1;
-    h->timing_suspended = true;
-    int rc = FBUS_OK;
-    for (int k = 0; k < K && rc == FBUS_OK; ++k) {
-        const char* a = (const char*)accel + (size_t)k * B * 3 * es;
-        const char* g = (const char*)gyro + (size_t)k * B * 3 * es;
-        const char* d = (const char*)dt + (size_t)k * (dt_per_filter ? B : 1) * es;
-        rc = launch_predict(h, 1, a, g, d, dt_per_filter);
-    }
-    timing_end(h, ev);
-    if (rc != FBUS_OK) { h->timing_suspended = false; return rc; }
-    h->timing_suspended = !sampled;
-    if (M > 0) rc = fbus_ekf_correct_dev(h, M, ids, pos, quat, mode, skip);
-    h->timing_suspended = false;
-    return rc;
+    return frame_any(h, false, K, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
 }
 
 int fbus_ekf_marker_pose_dev(fbus_ekf_t h, int n, int geometry, const void* left, const void* right, void* pos,
                              void* quat, void* corners3d)
 {
-    DeviceGuard guard_(h);
-    if (!h || n < 1 || !left || !pos || !quat) return FBUS_ERR_INVALID;
-    if (geometry != FBUS_VIS_REFRACTIVE && geometry != FBUS_VIS_PINHOLE && geometry != FBUS_VIS_CORNERS3D)
-        return FBUS_ERR_UNSUPPORTED;
-    if (geometry != FBUS_VIS_CORNERS3D && !right) return FBUS_ERR_INVALID;
-    if (h->dtype == 32) return launch_marker_pose_t<float>(h, n, geometry, left, right, pos, quat, corners3d);
-    return launch_marker_pose_t<double>(h, n, geometry, left, right, pos, quat, corners3d);
+    return marker_pose_any(h, DEV, n, geometry, left, right, pos, quat, corners3d);
 }
 
 int fbus_ekf_marker_pose(fbus_ekf_t h, int n, int geometry, const void* left, const void* right, void* pos,
                          void* quat, void* corners3d)
 {
-    DeviceGuard guard_(h);
-    if (!h || n < 1 || !left || !pos || !quat) return FBUS_ERR_INVALID;
-    const size_t es = esize(h), nn = (size_t)n;
-    const size_t in_w = geometry == FBUS_VIS_CORNERS3D ? 12 : 8;
-    const void *dl, *dr;
-    int rc;
-    if ((rc = stage_in(h, 0, left, nn * in_w * es, &dl)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, geometry == FBUS_VIS_CORNERS3D ? nullptr : right, nn * 8 * es, &dr)) != FBUS_OK) return rc;
-    if ((rc = ensure_stage(h, 2, nn * 3 * es)) != FBUS_OK) return rc;
-    if ((rc = ensure_stage(h, 3, nn * 4 * es)) != FBUS_OK) return rc;
-    if (corners3d && (rc = ensure_stage(h, 4, nn * 12 * es)) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_marker_pose_dev(h, n, geometry, dl, dr, h->stage[2], h->stage[3],
-                                       corners3d ? h->stage[4] : nullptr)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(pos, h->stage[2], nn * 3 * es, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(quat, h->stage[3], nn * 4 * es, hipMemcpyDeviceToHost, h->stream));
-    if (corners3d) HIP_TRY(h, hipMemcpyAsync(corners3d, h->stage[4], nn * 12 * es, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return marker_pose_any(h, STAGED, n, geometry, left, right, pos, quat, corners3d);
 }
 
 int fbus_ekf_init_gravity_bias_dev(fbus_ekf_t h, int T, const void* accel, const void* gyro)
 {
-    DeviceGuard guard_(h);
-    if (!h || T < 1 || !accel || !gyro) return FBUS_ERR_INVALID;
-    return do_init_gb(h, T, accel, gyro);
+    return init_gravity_bias_any(h, DEV, T, accel, gyro);
 }
 
 int fbus_ekf_init_gravity_bias(fbus_ekf_t h, int T, const void* accel, const void* gyro)
 {
-    DeviceGuard guard_(h);
-    if (!h || T < 1 || !accel || !gyro) return FBUS_ERR_INVALID;
-    const size_t bytes = (size_t)T * h->B * 3 * esize(h);
-    const void *da, *dg;
-    int rc;
-    if ((rc = stage_in(h, 0, accel, bytes, &da)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, gyro, bytes, &dg)) != FBUS_OK) return rc;
-    if ((rc = do_init_gb(h, T, da, dg)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return init_gravity_bias_any(h, STAGED, T, accel, gyro);
 }
 
 int fbus_ekf_pose_init_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int what,
                            const uint8_t* mask)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (what != FBUS_POSE_INIT && what != FBUS_POSE_RESET) return FBUS_ERR_INVALID;
-    return do_pose_init(h, M, ids, pos, quat, what, mask, nullptr);
+    return pose_init_any(h, DEV, M, ids, pos, quat, what, mask, nullptr);
 }
 
 int fbus_ekf_vision_only_pose_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat,
                                   void* out_pose)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || !out_pose || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    return do_pose_init(h, M, ids, pos, quat, 2, nullptr, out_pose);
-}
-
-static int pose_host(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int what,
-                     const uint8_t* mask, void* out_pose)
-{
-    const size_t es = esize(h), B = (size_t)h->B;
-    const void *di, *dp, *dq, *dm;
-    int rc;
-    if ((rc = stage_in(h, 0, ids, B * M * 4, &di)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, pos, B * M * 3 * es, &dp)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 2, quat, B * M * 4 * es, &dq)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 3, mask, B, &dm)) != FBUS_OK) return rc;
-    if (out_pose && (rc = ensure_stage(h, 4, B * 7 * es)) != FBUS_OK) return rc;
-    if (out_pose) HIP_TRY(h, hipMemsetAsync(h->stage[4], 0, B * 7 * es, h->stream));
-    if ((rc = do_pose_init(h, M, (const int32_t*)di, dp, dq, what, (const uint8_t*)dm, out_pose ? h->stage[4] : nullptr)) != FBUS_OK)
-        return rc;
-    if (out_pose) HIP_TRY(h, hipMemcpyAsync(out_pose, h->stage[4], B * 7 * es, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return pose_init_any(h, DEV, M, ids, pos, quat, POSE_VISION, nullptr, out_pose);
 }
 
 int fbus_ekf_pose_init(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int what,
                        const uint8_t* mask)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    if (what != FBUS_POSE_INIT && what != FBUS_POSE_RESET) return FBUS_ERR_INVALID;
-    return pose_host(h, M, ids, pos, quat, what, mask, nullptr);
+    return pose_init_any(h, STAGED, M, ids, pos, quat, what, mask, nullptr);
 }
 
 int fbus_ekf_vision_only_pose(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, void* out_pose)
 {
-    DeviceGuard guard_(h);
-    if (!h || !ids || !pos || !quat || !out_pose || M < 1 || M > FBUS_MAX_VISIBLE) return FBUS_ERR_INVALID;
-    return pose_host(h, M, ids, pos, quat, 2, nullptr, out_pose);
+    return pose_init_any(h, STAGED, M, ids, pos, quat, POSE_VISION, nullptr, out_pose);
 }
 
 int fbus_ekf_imu_ema_dev(fbus_ekf_t h, int T, void* accel, void* gyro, int restart)
 {
-    DeviceGuard guard_(h);
-    if (!h || T < 0 || (T > 0 && (!accel || !gyro))) return FBUS_ERR_INVALID;
-    if (!h->d_ema_carry) HIP_TRY(h, hipMalloc(&h->d_ema_carry, (size_t)h->B * 6 * esize(h)));
-    if (restart) h->ema_has_carry = false;
-    if (T == 0) return FBUS_OK;
-    const int grid = (h->B + 255) / 256;
-    if (h->dtype == 32)
-        hipLaunchKernelGGL((imu_ema_kernel<float>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (float*)accel,
-                           (float*)gyro, (float*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
-    else
-        hipLaunchKernelGGL((imu_ema_kernel<double>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (double*)accel,
-                           (double*)gyro, (double*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
-    HIP_TRY(h, hipGetLastError());
-    h->ema_has_carry = true;
-    return FBUS_OK;
+    return imu_ema_any(h, DEV, T, accel, gyro, restart);
 }
 
 int fbus_ekf_imu_ema(fbus_ekf_t h, int T, void* accel, void* gyro, int restart)
 {
-    DeviceGuard guard_(h);
-    if (!h || T < 0 || (T > 0 && (!accel || !gyro))) return FBUS_ERR_INVALID;
-    if (T == 0) return fbus_ekf_imu_ema_dev(h, 0, nullptr, nullptr, restart);
-    const size_t bytes = (size_t)T * h->B * 3 * esize(h);
-    const void *da, *dg;
-    int rc;
-    if ((rc = stage_in(h, 0, accel, bytes, &da)) != FBUS_OK) return rc;
-    if ((rc = stage_in(h, 1, gyro, bytes, &dg)) != FBUS_OK) return rc;
-    if ((rc = fbus_ekf_imu_ema_dev(h, T, h->stage[0], h->stage[1], restart)) != FBUS_OK) return rc;
-    HIP_TRY(h, hipMemcpyAsync(accel, h->stage[0], bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipMemcpyAsync(gyro, h->stage[1], bytes, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    return imu_ema_any(h, STAGED, T, accel, gyro, restart);
 }
 
 int fbus_ekf_graph_begin(fbus_ekf_t h)
@@ -2611,22 +2563,21 @@ int fbus_ekf_l0_eval(fbus_ekf_t h, int op, int n, const void* a, const void* b, 
     static const int wa[] = { 4, 4, 4, 4, 3, 3, 1 }, wb[] = { 4, 0, 0, 0, 1, 0, 0 }, wo[] = { 4, 9, 9, 4, 9, 4, 4 };
     if (!h || op < 0 || op > FBUS_L0_SINCOS_HALF || n < 1 || !a || !out || (wb[op] && !b)) return FBUS_ERR_INVALID;
     const size_t es = esize(h);
-    const void *da, *db = nullptr;
-    int rc;
-    if ((rc = stage_in(h, 0, a, (size_t)n * wa[op] * es, &da)) != FBUS_OK) return rc;
-    if (wb[op] && (rc = stage_in(h, 1, b, (size_t)n * wb[op] * es, &db)) != FBUS_OK) return rc;
-    if ((rc = ensure_stage(h, 2, (size_t)n * wo[op] * es)) != FBUS_OK) return rc;
-    const int grid = (n + 255) / 256;
-    if (h->dtype == 32)
-        hipLaunchKernelGGL((l0_eval_kernel<float>), dim3(grid), dim3(256), 0, h->stream, op, n, (const float*)da,
-                           (const float*)db, (float*)h->stage[2]);
-    else
-        hipLaunchKernelGGL((l0_eval_kernel<double>), dim3(grid), dim3(256), 0, h->stream, op, n, (const double*)da,
-                           (const double*)db, (double*)h->stage[2]);
-    HIP_TRY(h, hipGetLastError());
-    HIP_TRY(h, hipMemcpyAsync(out, h->stage[2], (size_t)n * wo[op] * es, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FBUS_OK;
+    const void *da, *db;
+    void* dout;
+    Piece pc[3] = { in_piece(a, (size_t)n * wa[op] * es, &da), in_piece(wb[op] ? b : nullptr, (size_t)n * wb[op] * es, &db),
+                    out_piece(out, (size_t)n * wo[op] * es, &dout) };
+    return run_pieces(h, STAGED, pc, 3, [&] {
+        const int grid = (n + 255) / 256;
+        if (h->dtype == 32)
+            hipLaunchKernelGGL((l0_eval_kernel<float>), dim3(grid), dim3(256), 0, h->stream, op, n, (const float*)da, (const float*)db,
+                               (float*)dout);
+        else
+            hipLaunchKernelGGL((l0_eval_kernel<double>), dim3(grid), dim3(256), 0, h->stream, op, n, (const double*)da, (const double*)db,
+                               (double*)dout);
+        HIP_TRY(h, hipGetLastError());
+        return (int)FBUS_OK;
+    });
 }
 
 }  // extern "C"

@@ -240,27 +240,43 @@ class BatchedFilter:
     def predict(self, accel, gyro, dt):
         return self.predict_n(accel, gyro, dt, K=1)
 
-    def predict_n(self, accel, gyro, dt, K=None):
+    def _imu(self, accel, gyro, dt, K=None, what="K", exact=False):
+        """(K, per) of the IMU samples of a device-array call, accel / gyro / dt checked and kept alive.  K: the sample count (None: what
+        accel holds); per: dt has one entry per sample and filter.  exact: dt may not be longer than K either (predict_n)"""
         B = self.B
-        if _is_dev(accel):
-            K = K if K is not None else accel.numel() // (3 * B)
-            per = 1 if dt.numel() == K * B and not (B == 1 and dt.numel() == K) else 0
-            if not per and dt.numel() != K:
-                raise ValueError("dt must have K or K*B elements")
-            self._dev_checked(accel, K * B * 3, "accel"); self._dev_checked(gyro, K * B * 3, "gyro")
-            self._dev_checked(dt, dt.numel(), "dt")
-            cur = self._order_in(accel, gyro, dt)
-            rc = self._lib.fbus_ekf_predict_n_dev(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per)
-            self._check(rc, "predict_n_dev")
-            return self._order_out(cur)
-        accel = np.ascontiguousarray(accel, self.np_dtype)
-        K = K if K is not None else accel.size // (3 * B)
-        accel = self._host(accel, (K, B, 3))
-        gyro = self._host(gyro, (K, B, 3))
+        if K is None:
+            K = accel.numel() // (3 * B) if accel is not None else 0
+        if K <= 0 and not exact:
+            return K, 0
+        n = dt.numel()
+        per = 1 if (n == K * B and B > 1) else 0
+        if not per and (n != K if exact else n < K):
+            raise ValueError(f"dt must have {what} or {what}*B elements")
+        self._dev_checked(accel, K * B * 3, "accel"); self._dev_checked(gyro, K * B * 3, "gyro")
+        self._dev_checked(dt, n, "dt")
+        return K, per
+
+    def _imu_host(self, accel, gyro, dt, K, conv):
+        """(K, accel, gyro, dt, per) of a host-array predict; conv: _host or _host_any"""
+        B = self.B
+        if K is None:
+            accel = np.ascontiguousarray(accel, self.np_dtype)
+            K = accel.size // (3 * B)
+        accel, gyro = conv(accel, (K, B, 3)), conv(gyro, (K, B, 3))
         dt = np.ascontiguousarray(np.atleast_1d(dt), self.np_dtype)
         per = 1 if (dt.size == K * B and B > 1) else 0
         if not per and dt.size != K:
             raise ValueError("dt must have K or K*B elements")
+        return K, accel, gyro, dt, per
+
+    def predict_n(self, accel, gyro, dt, K=None):
+        if _is_dev(accel):
+            K, per = self._imu(accel, gyro, dt, K, exact=True)
+            cur = self._order_in(accel, gyro, dt)
+            rc = self._lib.fbus_ekf_predict_n_dev(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per)
+            self._check(rc, "predict_n_dev")
+            return self._order_out(cur)
+        K, accel, gyro, dt, per = self._imu_host(accel, gyro, dt, K, self._host)
         rc = self._lib.fbus_ekf_predict_n(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per)
         self._check(rc, "predict_n")
 
@@ -275,31 +291,14 @@ class BatchedFilter:
 
     def predict_async(self, accel, gyro, dt, K=1):
         """fbus_ekf_predict_n_async: host arrays taken by value, nothing waits for the device (results: sync() / get_state())"""
-        B = self.B
-        accel, gyro = self._host_any(accel, (K, B, 3)), self._host_any(gyro, (K, B, 3))
-        dt = np.ascontiguousarray(np.atleast_1d(dt), self.np_dtype)
-        per = 1 if (dt.size == K * B and B > 1) else 0
-        if not per and dt.size != K:
-            raise ValueError("dt must have K or K*B elements")
+        K, accel, gyro, dt, per = self._imu_host(accel, gyro, dt, K, self._host_any)
         self._check(self._lib.fbus_ekf_predict_n_async(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per), "predict_n_async")
 
     def correct_async(self, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
-        B = self.B
-        ids = np.ascontiguousarray(ids.numpy() if _is_dev(ids) else ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        pos, quat = self._host_any(pos, (B, M, 3)), self._host_any(quat, (B, M, 4))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        self._check(self._lib.fbus_ekf_correct_async(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip)), "correct_async")
+        self._update("correct", ids, self._pose_arrays(pos, quat), (mode,), skip, transport="_async")
 
     def correct_pixels_async(self, ids, left, right=None, skip=None):
-        B = self.B
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        left = self._host_any(left, (B, M, 8))
-        right = None if right is None else self._host_any(right, (B, M, 8))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        self._check(self._lib.fbus_ekf_correct_pixels_async(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip)),
-                    "correct_pixels_async")
+        self._update("correct_pixels", ids, self._image_arrays(left, right), (), skip, transport="_async")
 
     def async_inputs_consumed(self):
         """every H2D copy of the _async calls so far is done: pinned input arrays may be rewritten"""
@@ -311,76 +310,70 @@ class BatchedFilter:
         return {"calls": a.value, "waits": b.value, "direct_pieces": c.value}
 
     # ---- correct == MeasureUpdate -----------------------------------------------------
-    def correct(self, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
+    def _rows_checked(self, n, M, ids, arrays, skip):
+        """the device arrays of n filter-frames of M marker slots, checked and kept alive: ids n * M, every (array, width, name, optional)
+        n * M * width elements, skip n"""
+        self._dev_checked(ids, n * M, "ids")
+        for a, w, name, optional in arrays:
+            if a is not None or not optional:
+                self._dev_checked(a, n * M * w, name)
+        if skip is not None:
+            self._dev_checked(skip, n, "skip")
+
+    def _update(self, stem, ids, arrays, tail=(), skip=None, nis=False, transport=None):
+        """One measurement update through fbus_ekf_<stem>[_nis]<transport>.  arrays: (array, elements per marker slot, name, optional)
+        behind ids; tail: the int arguments behind them; nis: the _nis form, returns its (nis, dof).  transport None: "_dev" for device
+        arrays (no copy, ordered with the caller's stream), "" for host arrays (staged, waits); "_async": host arrays, no wait"""
         B = self.B
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(pos, B * M * 3, "pos")
-            self._dev_checked(quat, B * M * 4, "quat")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            cur = self._order_in(ids, pos, quat, skip)
-            rc = self._lib.fbus_ekf_correct_dev(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip))
-            self._check(rc, "correct_dev")
-            return self._order_out(cur)
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        pos = self._host(pos, (B, M, 3))
-        quat = self._host(quat, (B, M, 4))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        rc = self._lib.fbus_ekf_correct(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip))
-        self._check(rc, "correct")
+        cur, out = None, ()
+        if transport is None and _is_dev(ids):
+            transport, M = "_dev", ids.numel() // B
+            self._rows_checked(B, M, ids, arrays, skip)
+            arrs = [a for a, _, _, _ in arrays]
+            if nis:
+                out = self._nis_outputs(ids)
+                self._keep += list(out)
+            cur = self._order_in(ids, *arrs, skip)
+        else:
+            conv = self._host_any if transport else self._host
+            transport = transport or ""
+            ids = np.ascontiguousarray(ids.numpy() if _is_dev(ids) else ids, np.int32).reshape(B, -1)
+            M = ids.shape[1]
+            arrs = [None if (a is None and optional) else conv(a, (B, M, w)) for a, w, _, optional in arrays]
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            if nis:
+                out = self._nis_outputs(None)
+        name = stem + ("_nis" if nis else "") + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, M, self._p(ids), *[self._p(a) for a in arrs], *tail, self._p(skip),
+                                                    *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if nis else None
+
+    def correct(self, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
+        self._update("correct", ids, self._pose_arrays(pos, quat), (mode,), skip)
 
     def correct_corners(self, ids, left, right=None, geometry=capi.VIS_REFRACTIVE, mode=capi.MODE_NEAREST, skip=None):
         """correct() from stereo corners (north-star extension, no reference counterpart): the corners are
         triangulated on the device and each corner position is a 3-row measurement (12 rows per marker).
         left/right: (B, M, 8) normalised corner coordinates, or left = (B, M, 12) with VIS_CORNERS3D."""
-        B = self.B
-        w = 12 if geometry == capi.VIS_CORNERS3D else 8
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * w, "left")
-            if right is not None:
-                self._dev_checked(right, B * M * 8, "right")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            cur = self._order_in(ids, left, right, skip)
-            rc = self._lib.fbus_ekf_correct_corners_dev(self._h, M, self._p(ids), self._p(left), self._p(right),
-                                                        geometry, mode, self._p(skip))
-            self._check(rc, "correct_corners_dev")
-            return self._order_out(cur)
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        left = self._host(left, (B, M, w))
-        right = None if right is None else self._host(right, (B, M, 8))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        rc = self._lib.fbus_ekf_correct_corners(self._h, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
-                                                self._p(skip))
-        self._check(rc, "correct_corners")
+        self._update("correct_corners", ids, self._image_arrays(left, right, capi.MEAS_CORNERS, geometry), (geometry, mode), skip)
 
     def correct_pixels(self, ids, left, right=None, skip=None):
         """correct() from corner PIXELS (north-star extension, no reference counterpart): the flat-port reprojection of
         the four corners of every visible marker, 2 rows per corner (left camera) or 4 (left and right).
         left/right: (B, M, 8) normalised image points x0 y0 .. x3 y3."""
-        B = self.B
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * 8, "left")
-            if right is not None:
-                self._dev_checked(right, B * M * 8, "right")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            cur = self._order_in(ids, left, right, skip)
-            rc = self._lib.fbus_ekf_correct_pixels_dev(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip))
-            self._check(rc, "correct_pixels_dev")
-            return self._order_out(cur)
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        left = self._host(left, (B, M, 8))
-        right = None if right is None else self._host(right, (B, M, 8))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        rc = self._lib.fbus_ekf_correct_pixels(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip))
-        self._check(rc, "correct_pixels")
+        self._update("correct_pixels", ids, self._image_arrays(left, right), (), skip)
+
+    @staticmethod
+    def _pose_arrays(pos, quat):
+        return [(pos, 3, "pos", False), (quat, 4, "quat", False)]
+
+    @staticmethod
+    def _image_arrays(left, right, kind=capi.MEAS_PIXELS, geometry=capi.VIS_REFRACTIVE):
+        """left / right of the pixel and corner rows: 8 elements per marker slot, left 12 (corner positions) with VIS_CORNERS3D"""
+        w = 12 if (kind == capi.MEAS_CORNERS and geometry == capi.VIS_CORNERS3D) else 8
+        return [(left, w, "left", False), (right, 8, "right", True)]
 
     # ---- NIS and chi-square gating of the measurement updates (include/fbus_ekf.h) --------------------------------
     def set_gate(self, thresholds=None):
@@ -467,120 +460,59 @@ class BatchedFilter:
     def correct_nis(self, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None):
         """correct() that also returns (nis, dof) per filter and applies the gate (set_gate): numpy arrays for host inputs,
         device tensors for device inputs."""
-        B = self.B
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(pos, B * M * 3, "pos"); self._dev_checked(quat, B * M * 4, "quat")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            nis, dof = self._nis_outputs(ids)
-            self._keep += [nis, dof]
-            cur = self._order_in(ids, pos, quat, skip)
-            rc = self._lib.fbus_ekf_correct_nis_dev(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip),
-                                                    self._p(nis), self._p(dof))
-            self._check(rc, "correct_nis_dev")
-            self._order_out(cur)
-            return nis, dof
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        pos = self._host(pos, (B, M, 3))
-        quat = self._host(quat, (B, M, 4))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        nis, dof = self._nis_outputs(None)
-        rc = self._lib.fbus_ekf_correct_nis(self._h, M, self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip),
-                                            self._p(nis), self._p(dof))
-        self._check(rc, "correct_nis")
-        return nis, dof
+        return self._update("correct", ids, self._pose_arrays(pos, quat), (mode,), skip, nis=True)
 
     def correct_pixels_nis(self, ids, left, right=None, skip=None):
         """correct_pixels() that also returns (nis, dof) per filter and applies the gate (set_gate): numpy arrays for host
         inputs, device tensors for device inputs."""
-        B = self.B
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * 8, "left")
-            if right is not None:
-                self._dev_checked(right, B * M * 8, "right")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            nis, dof = self._nis_outputs(ids)
-            self._keep += [nis, dof]
-            cur = self._order_in(ids, left, right, skip)
-            rc = self._lib.fbus_ekf_correct_pixels_nis_dev(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip),
-                                                           self._p(nis), self._p(dof))
-            self._check(rc, "correct_pixels_nis_dev")
-            self._order_out(cur)
-            return nis, dof
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        left = self._host(left, (B, M, 8))
-        right = None if right is None else self._host(right, (B, M, 8))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        nis, dof = self._nis_outputs(None)
-        rc = self._lib.fbus_ekf_correct_pixels_nis(self._h, M, self._p(ids), self._p(left), self._p(right), self._p(skip),
-                                                   self._p(nis), self._p(dof))
-        self._check(rc, "correct_pixels_nis")
-        return nis, dof
+        return self._update("correct_pixels", ids, self._image_arrays(left, right), (), skip, nis=True)
 
     def correct_corners_nis(self, ids, left, right=None, geometry=capi.VIS_REFRACTIVE, mode=capi.MODE_NEAREST, skip=None):
         """correct_corners() that also returns (nis, dof) per filter and applies the gate (set_gate)."""
-        B = self.B
-        w = 12 if geometry == capi.VIS_CORNERS3D else 8
-        if _is_dev(ids):
-            M = ids.numel() // B
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * w, "left")
-            if right is not None:
-                self._dev_checked(right, B * M * 8, "right")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            nis, dof = self._nis_outputs(ids)
-            self._keep += [nis, dof]
-            cur = self._order_in(ids, left, right, skip)
-            rc = self._lib.fbus_ekf_correct_corners_nis_dev(self._h, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
-                                                            self._p(skip), self._p(nis), self._p(dof))
-            self._check(rc, "correct_corners_nis_dev")
-            self._order_out(cur)
-            return nis, dof
-        ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
-        M = ids.shape[1]
-        left = self._host(left, (B, M, w))
-        right = None if right is None else self._host(right, (B, M, 8))
-        skip = None if skip is None else self._host(skip, (B,), np.uint8)
-        nis, dof = self._nis_outputs(None)
-        rc = self._lib.fbus_ekf_correct_corners_nis(self._h, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
-                                                    self._p(skip), self._p(nis), self._p(dof))
-        self._check(rc, "correct_corners_nis")
-        return nis, dof
+        return self._update("correct_corners", ids, self._image_arrays(left, right, capi.MEAS_CORNERS, geometry), (geometry, mode), skip,
+                            nis=True)
 
     def applied(self):
         out = np.empty(self.B, np.uint8)
         self._check(self._lib.fbus_ekf_get_applied(self._h, self._p(out)), "get_applied")
         return out
 
+    def _frame_call(self, name, head, imu, pre, M, ids, arrays, tail, skip, n, record=None):
+        """One frame or window through fbus_ekf_<name>: head (K, or F and kcount), the IMU arrays and per, the int arguments in front of M,
+        M, ids and `arrays` (checked as n filter-frames), the int arguments behind them, skip; record: the number of frames whose
+        trajectory rows are wanted (and returned), or None"""
+        if M > 0:
+            self._rows_checked(n, M, ids, arrays, None)
+        if skip is not None:
+            self._dev_checked(skip, n, "skip")
+        accel, gyro, dt, per = imu
+        arrs = [a for a, _, _, _ in arrays]
+        out = self._traj_outputs(record) if record is not None else ()
+        cur = self._order_in(accel, gyro, dt, ids, *arrs, skip, *out)
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, *head, self._p(accel), self._p(gyro), self._p(dt), per, *pre, M,
+                                                    self._p(ids), *[self._p(a) for a in arrs], *tail, self._p(skip),
+                                                    *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if record is not None else None
+
+    def _window(self, kcount, accel, gyro, dt, ids):
+        """(kcount as int32, its pointer, F, M, per) of a window call, the IMU arrays checked"""
+        kcount = np.ascontiguousarray(kcount, np.int32)
+        F, Kt = int(kcount.size), int(kcount.sum())
+        if F > capi.MAX_WINDOW_FRAMES:
+            raise ValueError(f"at most {capi.MAX_WINDOW_FRAMES} frames per window")
+        M = ids.numel() // (self.B * F) if (ids is not None and F > 0) else 0
+        _, per = self._imu(accel, gyro, dt, Kt, "sum(kcount)")
+        return kcount, kcount.ctypes.data_as(C.POINTER(C.c_int32)), F, M, per
+
     def frame(self, accel, gyro, dt, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None, fused=False):
         """K per-sample predict launches followed by one correct launch (device arrays only);
         fused=True: the same frame as ONE launch with the records resident in registers."""
-        B = self.B
-        K = accel.numel() // (3 * B) if accel is not None else 0
-        M = ids.numel() // B if ids is not None else 0
-        per = 0
-        if K > 0:
-            per = 1 if (dt.numel() == K * B and B > 1) else 0
-            if not per and dt.numel() < K:
-                raise ValueError("dt must have K or K*B elements")
-            self._dev_checked(accel, K * B * 3, "accel"); self._dev_checked(gyro, K * B * 3, "gyro")
-            self._dev_checked(dt, dt.numel(), "dt")
-        if M > 0:
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(pos, B * M * 3, "pos")
-            self._dev_checked(quat, B * M * 4, "quat")
-        if skip is not None:
-            self._dev_checked(skip, B, "skip")
-        fn = self._lib.fbus_ekf_frame_fused_dev if fused else self._lib.fbus_ekf_frame_dev
-        cur = self._order_in(accel, gyro, dt, ids, pos, quat, skip)
-        rc = fn(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per, M,
-                                          self._p(ids), self._p(pos), self._p(quat), mode, self._p(skip))
-        self._check(rc, "frame_dev")
-        self._order_out(cur)
+        K, per = self._imu(accel, gyro, dt)
+        M = ids.numel() // self.B if ids is not None else 0
+        self._frame_call("frame_fused_dev" if fused else "frame_dev", (K,), (accel, gyro, dt, per), (), M, ids,
+                         self._pose_arrays(pos, quat), (mode,), skip, self.B)
 
     def frame_meas(self, accel, gyro, dt, ids, left, right=None, kind=capi.MEAS_PIXELS, geometry=capi.VIS_REFRACTIVE,
                    mode=capi.MODE_STACKED, skip=None):
@@ -588,28 +520,10 @@ class BatchedFilter:
         K predicts, then correct_pixels (kind = MEAS_PIXELS; right=None: left camera) or correct_corners (MEAS_CORNERS, with its
         geometry / mode).  accel, gyro: (K, B, 3); dt: (K,) or (K, B); ids: (B, M); left / right: (B, M, 8) [(B, M, 12) corner
         positions for VIS_CORNERS3D]."""
-        B = self.B
-        K = accel.numel() // (3 * B) if accel is not None else 0
-        M = ids.numel() // B if ids is not None else 0
-        per = 0
-        if K > 0:
-            per = 1 if (dt.numel() == K * B and B > 1) else 0
-            if not per and dt.numel() < K:
-                raise ValueError("dt must have K or K*B elements")
-            self._dev_checked(accel, K * B * 3, "accel"); self._dev_checked(gyro, K * B * 3, "gyro")
-            self._dev_checked(dt, dt.numel(), "dt")
-        if M > 0:
-            lw = 12 if (kind == capi.MEAS_CORNERS and geometry == capi.VIS_CORNERS3D) else 8
-            self._dev_checked(ids, B * M, "ids"); self._dev_checked(left, B * M * lw, "left")
-            if right is not None:
-                self._dev_checked(right, B * M * 8, "right")
-        if skip is not None:
-            self._dev_checked(skip, B, "skip")
-        cur = self._order_in(accel, gyro, dt, ids, left, right, skip)
-        rc = self._lib.fbus_ekf_frame_meas_fused_dev(self._h, K, self._p(accel), self._p(gyro), self._p(dt), per, kind, M,
-                                                     self._p(ids), self._p(left), self._p(right), geometry, mode, self._p(skip))
-        self._check(rc, "frame_meas_fused_dev")
-        self._order_out(cur)
+        K, per = self._imu(accel, gyro, dt)
+        M = ids.numel() // self.B if ids is not None else 0
+        self._frame_call("frame_meas_fused_dev", (K,), (accel, gyro, dt, per), (kind,), M, ids,
+                         self._image_arrays(left, right, kind, geometry), (geometry, mode), skip, self.B)
 
     def frames_meas(self, kcount, accel, gyro, dt, ids, left, right=None, kind=capi.MEAS_PIXELS, geometry=capi.VIS_REFRACTIVE,
                     mode=capi.MODE_STACKED, skip=None, record=False):
@@ -618,41 +532,9 @@ class BatchedFilter:
         (sum kcount, B); ids: (F, B, M); left / right: (F, B, M, 8) [(F, B, M, 12) for VIS_CORNERS3D]; skip: (F, B) or None.
         record=True: the window's trajectory as well (fbus_ekf_frames_meas_fused_traj_dev) -- returns (nominal (F, B, 19), pdiag (F, B, N),
         applied (F, B)), torch tensors on the handle's device: the state after every frame (FBUS_EKF.m:201-204)."""
-        B = self.B
-        kcount = np.ascontiguousarray(kcount, np.int32)
-        F, Kt = int(kcount.size), int(kcount.sum())
-        if F > capi.MAX_WINDOW_FRAMES:
-            raise ValueError(f"at most {capi.MAX_WINDOW_FRAMES} frames per window")
-        M = ids.numel() // (B * F) if (ids is not None and F > 0) else 0
-        per = 0
-        if Kt > 0:
-            per = 1 if (dt.numel() == Kt * B and B > 1) else 0
-            if not per and dt.numel() < Kt:
-                raise ValueError("dt must have sum(kcount) or sum(kcount)*B elements")
-            self._dev_checked(accel, Kt * B * 3, "accel"); self._dev_checked(gyro, Kt * B * 3, "gyro")
-            self._dev_checked(dt, dt.numel(), "dt")
-        if M > 0:
-            lw = 12 if (kind == capi.MEAS_CORNERS and geometry == capi.VIS_CORNERS3D) else 8
-            self._dev_checked(ids, F * B * M, "ids"); self._dev_checked(left, F * B * M * lw, "left")
-            if right is not None:
-                self._dev_checked(right, F * B * M * 8, "right")
-        if skip is not None:
-            self._dev_checked(skip, F * B, "skip")
-        if record:
-            out = self._traj_outputs(F)
-            cur = self._order_in(accel, gyro, dt, ids, left, right, skip, *out)
-            rc = self._lib.fbus_ekf_frames_meas_fused_traj_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
-                                                               self._p(gyro), self._p(dt), per, kind, M, self._p(ids), self._p(left),
-                                                               self._p(right), geometry, mode, self._p(skip), *[self._p(o) for o in out])
-            self._check(rc, "frames_meas_fused_traj_dev")
-            self._order_out(cur)
-            return out
-        cur = self._order_in(accel, gyro, dt, ids, left, right, skip)
-        rc = self._lib.fbus_ekf_frames_meas_fused_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel), self._p(gyro),
-                                                      self._p(dt), per, kind, M, self._p(ids), self._p(left), self._p(right), geometry, mode,
-                                                      self._p(skip))
-        self._check(rc, "frames_meas_fused_dev")
-        self._order_out(cur)
+        kcount, kp, F, M, per = self._window(kcount, accel, gyro, dt, ids)
+        return self._frame_call("frames_meas_fused_traj_dev" if record else "frames_meas_fused_dev", (F, kp), (accel, gyro, dt, per), (kind,), M,
+                                ids, self._image_arrays(left, right, kind, geometry), (geometry, mode), skip, F * self.B, F if record else None)
 
     def frames(self, kcount, accel, gyro, dt, ids, pos, quat, mode=capi.MODE_NEAREST, skip=None, record=False):
         """A window of camera frames in ONE launch (device arrays): len(kcount) times { kcount[f] predicts, one correct }
@@ -661,39 +543,9 @@ class BatchedFilter:
         quat: (F, B, M, 4); skip: (F, B) or None.  applied() afterwards reports the last frame.
         record=True: the window's trajectory as well (fbus_ekf_frames_fused_traj_dev) -- returns (nominal (F, B, 19), pdiag (F, B, N),
         applied (F, B)), torch tensors on the handle's device: the state after every frame (FBUS_EKF.m:201-204)."""
-        B = self.B
-        kcount = np.ascontiguousarray(kcount, np.int32)
-        F, Kt = int(kcount.size), int(kcount.sum())
-        if F > capi.MAX_WINDOW_FRAMES:
-            raise ValueError(f"at most {capi.MAX_WINDOW_FRAMES} frames per window")
-        M = ids.numel() // (B * F) if (ids is not None and F > 0) else 0
-        per = 0
-        if Kt > 0:
-            per = 1 if (dt.numel() == Kt * B and B > 1) else 0
-            if not per and dt.numel() < Kt:
-                raise ValueError("dt must have sum(kcount) or sum(kcount)*B elements")
-            self._dev_checked(accel, Kt * B * 3, "accel"); self._dev_checked(gyro, Kt * B * 3, "gyro")
-            self._dev_checked(dt, dt.numel(), "dt")
-        if M > 0:
-            self._dev_checked(ids, F * B * M, "ids"); self._dev_checked(pos, F * B * M * 3, "pos")
-            self._dev_checked(quat, F * B * M * 4, "quat")
-        if skip is not None:
-            self._dev_checked(skip, F * B, "skip")
-        if record:
-            out = self._traj_outputs(F)
-            cur = self._order_in(accel, gyro, dt, ids, pos, quat, skip, *out)
-            rc = self._lib.fbus_ekf_frames_fused_traj_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
-                                                          self._p(gyro), self._p(dt), per, M, self._p(ids), self._p(pos), self._p(quat),
-                                                          mode, self._p(skip), *[self._p(o) for o in out])
-            self._check(rc, "frames_fused_traj_dev")
-            self._order_out(cur)
-            return out
-        cur = self._order_in(accel, gyro, dt, ids, pos, quat, skip)
-        rc = self._lib.fbus_ekf_frames_fused_dev(self._h, F, kcount.ctypes.data_as(C.POINTER(C.c_int32)), self._p(accel),
-                                                 self._p(gyro), self._p(dt), per, M, self._p(ids), self._p(pos), self._p(quat),
-                                                 mode, self._p(skip))
-        self._check(rc, "frames_fused_dev")
-        self._order_out(cur)
+        kcount, kp, F, M, per = self._window(kcount, accel, gyro, dt, ids)
+        return self._frame_call("frames_fused_traj_dev" if record else "frames_fused_dev", (F, kp), (accel, gyro, dt, per), (), M, ids,
+                                self._pose_arrays(pos, quat), (mode,), skip, F * self.B, F if record else None)
 
     def _traj_outputs(self, F):
         """(nominal (F, B, 19), pdiag (F, B, N), applied (F, B)) on the handle's device, kept alive until the next sync()"""

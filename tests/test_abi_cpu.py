@@ -36,6 +36,20 @@ def test_status_strings_and_null_handle_errors():
     assert b"no CPU fallback" in lib.fbus_status_string(2)
     assert lib.fbus_ekf_sync(None) == 1
     assert lib.fbus_ekf_predict_dev(None, None, None, None, 0) == 1
+    # every form of every update, frame and window, and the staged element-wise calls: a null handle is refused before anything
+    # touches a device (arguments by the argtypes of capi.py: null pointers and zeros)
+    forms = ["set_state", "get_state", "set_state_dev", "get_state_dev", "l0_eval"]
+    forms += [f"predict{n}{t}" for n in ("", "_n") for t in ("", "_dev", "_async")]
+    forms += [f"correct{u}{t}" for u in ("", "_pixels") for t in ("", "_dev", "_async", "_nis", "_nis_dev")]
+    forms += [f"correct_corners{t}" for t in ("", "_dev", "_nis", "_nis_dev")]
+    forms += ["frame_dev", "frame_fused_dev", "frame_meas_fused_dev", "frames_fused_dev", "frames_fused_traj_dev",
+              "frames_meas_fused_dev", "frames_meas_fused_traj_dev"]
+    forms += [f"{u}{t}" for u in ("marker_pose", "init_gravity_bias", "pose_init", "vision_only_pose", "imu_ema") for t in ("", "_dev")]
+    assert len(set(forms)) == len(forms) == 42
+    for name in forms:
+        fn = getattr(lib, "fbus_ekf_" + name)
+        args = [0 if t in (C.c_int, C.c_size_t) else None for t in fn.argtypes]
+        assert fn(*args) == 1, name
 
 
 def test_create_rejects_bad_arguments_before_touching_the_device():
