@@ -12,6 +12,7 @@
 #include "../../include/fbus_ekf.h"
 #include "ekf_kernels.hpp"
 #include "ekf_launch.hpp"
+#include "ekf_group.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -622,6 +623,36 @@ int snapshot_t(fbus_ekf_t h, void* nom, void* pdiag, uint8_t* applied)
     return FBUS_OK;
 }
 int do_snapshot(fbus_ekf_t h, void* n, void* pd, uint8_t* a) { DISPATCH2(h, snapshot_t, h, n, pd, a); }
+// ---- hypothesis groups (ekf_group.hpp): one wave per floor(64 / G) whole groups ------------------------------------------------------------
+template <typename T, int N>
+int group_fuse_t(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nom, void* P, void* pdiag)
+{
+    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
+    const size_t lds = group_fuse_lds<T, N>(ngw);
+    if (P)
+        hipLaunchKernelGGL((group_fuse_kernel<T, N, true>), dim3(grid), dim3(BLOCK), lds, h->stream, (const T*)h->recs, h->rec_bytes, h->B, G,
+                           logw, weight, (int*)best, (T*)nom, (T*)P, (T*)pdiag);
+    else
+        hipLaunchKernelGGL((group_fuse_kernel<T, N, false>), dim3(grid), dim3(BLOCK), lds, h->stream, (const T*)h->recs, h->rec_bytes, h->B, G,
+                           logw, weight, (int*)best, (T*)nom, (T*)nullptr, (T*)pdiag);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int do_group_fuse(fbus_ekf_t h, int G, const double* lw, double* w, int32_t* best, void* nom, void* P, void* pd)
+{
+    DISPATCH2(h, group_fuse_t, h, G, lw, w, best, nom, P, pd);
+}
+template <typename T, int N>
+int group_collapse_t(fbus_ekf_t h, int G, const int32_t* src)
+{
+    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
+    h->records_warm = true;                                  // stored with the default cache policy
+    hipLaunchKernelGGL((group_collapse_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (T*)h->recs, h->rec_bytes, h->B, G, (const int*)src);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int do_group_collapse(fbus_ekf_t h, int G, const int32_t* src) { DISPATCH2(h, group_collapse_t, h, G, src); }
+
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
 int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
 {
@@ -1424,6 +1455,65 @@ int imu_ema_any(fbus_ekf_t h, Transport t, int T, void* accel, void* gyro, int r
         h->ema_has_carry = true;
         return (int)FBUS_OK;
     });
+}
+
+// ---- hypothesis groups: fbus_ekf_group_fuse / _collapse, host and device forms ----------------------------------------------------------
+int check_group(fbus_ekf_t h, const char* where, int G)
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (G < 2 || G > FBUS_GROUP_MAX)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": G = " + std::to_string(G) + " outside 2.." + std::to_string(FBUS_GROUP_MAX));
+    if (h->B % G != 0)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": the batch of " + std::to_string(h->B) + " is not a multiple of G = " + std::to_string(G));
+    return FBUS_OK;
+}
+int group_fuse_any(fbus_ekf_t h, Transport t, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
+{
+    DeviceGuard guard_(h);
+    const char* where = t == DEV ? "fbus_ekf_group_fuse_dev" : "fbus_ekf_group_fuse";
+    int rc = check_group(h, where, G);
+    if (rc != FBUS_OK) return rc;
+    if (!logw && !h->d_lik)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
+    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    const size_t es = esize(h), B = (size_t)h->B, NG = B / G, N = (size_t)h->N;
+    if (t == DEV) {          // (staged outputs are the handle's own buffers)
+        const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes;
+        const struct { const void* p; size_t bytes; } outs[5] = { { weight, B * sizeof(double) }, { best, NG * sizeof(int32_t) },
+                                                                  { nominal, NG * 19 * es }, { P, NG * N * N * es }, { pdiag, NG * N * es } };
+        for (const auto& o : outs) {
+            const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
+            if (o.p && a < r1 && a + o.bytes > r0) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
+        }
+    }
+    if (!weight && !best && !nominal && !P && !pdiag) return FBUS_OK;
+    const void* dl;
+    void *dw, *db, *dn, *dP, *dd;
+    Piece pc[6] = { in_piece(logw, B * sizeof(double), &dl), out_piece(weight, B * sizeof(double), &dw),
+                    out_piece(best, NG * sizeof(int32_t), &db), out_piece(nominal, NG * 19 * es, &dn),
+                    out_piece(P, NG * N * N * es, &dP), out_piece(pdiag, NG * N * es, &dd) };
+    return run_pieces(h, t, pc, 6, [&] {
+        return do_group_fuse(h, G, dl ? (const double*)dl : h->d_lik, (double*)dw, (int32_t*)db, dn, dP, dd);
+    });
+}
+int group_collapse_any(fbus_ekf_t h, Transport t, int G, const int32_t* src)
+{
+    DeviceGuard guard_(h);
+    const char* where = t == DEV ? "fbus_ekf_group_collapse_dev" : "fbus_ekf_group_collapse";
+    int rc = check_group(h, where, G);
+    if (rc != FBUS_OK) return rc;
+    if (!src) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": src is NULL");
+    const size_t NG = (size_t)h->B / G;
+    if (t != DEV) {
+        if (h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+        for (size_t j = 0; j < NG; ++j)
+            if (src[j] >= G)
+                return fail(h, FBUS_ERR_INVALID, std::string(where) + ": src[" + std::to_string(j) + "] = " + std::to_string(src[j]) +
+                                                 " is not a member of a group of " + std::to_string(G) + " (negative: skip the group)");
+    }
+    const void* ds;
+    Piece pc[1] = { in_piece(src, NG * sizeof(int32_t), &ds) };
+    return run_pieces(h, t, pc, 1, [&] { return do_group_collapse(h, G, (const int32_t*)ds); });
 }
 
 }  // namespace
@@ -2309,6 +2399,17 @@ int fbus_ekf_get_noise(fbus_ekf_t h, double* table)
         for (int c = 0; c < FBUS_NOISE_COLS; ++c) table[b * FBUS_NOISE_COLS + c] = fields[(size_t)c * B + b];
     return FBUS_OK;
 }
+
+int fbus_ekf_group_fuse_dev(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
+{
+    return group_fuse_any(h, DEV, G, logw, weight, best, nominal, P, pdiag);
+}
+int fbus_ekf_group_fuse(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
+{
+    return group_fuse_any(h, STAGED, G, logw, weight, best, nominal, P, pdiag);
+}
+int fbus_ekf_group_collapse_dev(fbus_ekf_t h, int G, const int32_t* src) { return group_collapse_any(h, DEV, G, src); }
+int fbus_ekf_group_collapse(fbus_ekf_t h, int G, const int32_t* src) { return group_collapse_any(h, STAGED, G, src); }
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                              void* nis, int32_t* dof)

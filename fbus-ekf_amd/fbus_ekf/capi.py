@@ -26,6 +26,7 @@ ABI_VERSION = 8                    # FBUS_ABI_VERSION of the header this mirror 
 ERR_ABI = 6
 GATE_MAX_DOF = 256                 # FBUS_GATE_MAX_DOF: a full gate table has 257 entries
 NOISE_COLS = 7                     # FBUS_NOISE_COLS: q_v q_theta q_ba q_bg r_pos r_quat r_pix (fbus_ekf_set_noise)
+GROUP_MAX = 64                     # FBUS_GROUP_MAX: the largest hypothesis group (fbus_ekf_group_fuse / _collapse)
 
 
 class FbusError(RuntimeError):
@@ -158,6 +159,10 @@ def load_library():
         "fbus_ekf_loglik_reset": ([H], C.c_int),
         "fbus_ekf_loglik_get": ([H, vp, vp, vp, vp], C.c_int),
         "fbus_ekf_loglik_get_dev": ([H, vp, vp, vp, vp], C.c_int),
+        "fbus_ekf_group_fuse": ([H, C.c_int, vp, vp, ip, vp, vp, vp], C.c_int),
+        "fbus_ekf_group_fuse_dev": ([H, C.c_int, vp, vp, ip, vp, vp, vp], C.c_int),
+        "fbus_ekf_group_collapse": ([H, C.c_int, ip], C.c_int),
+        "fbus_ekf_group_collapse_dev": ([H, C.c_int, ip], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

@@ -450,6 +450,60 @@ class BatchedFilter:
         self._check(self._lib.fbus_ekf_loglik_get(self._h, *(self._p(o) for o in out)), "loglik_get")
         return out
 
+    # ---- hypothesis groups: evidence-weighted fusion and collapse (include/fbus_ekf.h) ------------------------------------
+    def _group_count(self, G, where):
+        G = int(G)
+        if not 2 <= G <= capi.GROUP_MAX or self.B % G:
+            # (the library refuses the same values; asked first because the output shapes below depend on them)
+            self._check(self._lib.fbus_ekf_group_collapse_dev(self._h, G, None), where)
+            raise ValueError(f"{where}: G = {G} does not divide the batch of {self.B} into groups of 2..{capi.GROUP_MAX}")
+        return G, self.B // G
+
+    def group_fuse(self, G, logw=None, full_cov=True):
+        """Evidence-weighted, moment-matched fusion of every contiguous group of G filters (fbus_ekf_group_fuse_dev): returns
+        (weight (B,) float64, best (B/G,) int32, nominal (B/G, 19), P (B/G, N, N) or None, pdiag (B/G, N)), torch tensors on the
+        handle's device, stream-ordered.  logw: the per-filter log-weights -- None: the handle's likelihood sums (loglik_enable), a
+        float64 device tensor, or anything np.asarray takes (staged to the device).  full_cov=False: the diagonal alone.
+        The records are not touched; noise.group_weights is the numpy twin of (weight, best)."""
+        import torch
+        G, NG = self._group_count(G, "group_fuse_dev")
+        dev = torch.device("cuda", self.device)
+        tt = torch.float32 if self.dtype == 32 else torch.float64
+        if logw is not None:
+            if _is_dev(logw):
+                if logw.dtype != torch.float64 or not logw.is_cuda:
+                    raise ValueError(f"group_fuse: logw must be a float64 device tensor, got {logw.dtype} on {logw.device}")
+            else:
+                logw = torch.from_numpy(np.ascontiguousarray(logw, np.float64).ravel()).to(dev)
+            self._dev_checked(logw, self.B, "logw")
+        out = (torch.empty(self.B, dtype=torch.float64, device=dev), torch.empty(NG, dtype=torch.int32, device=dev),
+               torch.empty((NG, 19), dtype=tt, device=dev),
+               torch.empty((NG, self.N, self.N), dtype=tt, device=dev) if full_cov else None,
+               torch.empty((NG, self.N), dtype=tt, device=dev))
+        self._keep += [o for o in out if o is not None]
+        cur = self._order_in(logw, *out)
+        self._check(self._lib.fbus_ekf_group_fuse_dev(self._h, G, self._p(logw), *(self._p(o) for o in out)), "group_fuse_dev")
+        self._order_out(cur)
+        return out
+
+    def group_collapse(self, G, src):
+        """Overwrite every member of group j with the record of its member src[j], bit for bit (fbus_ekf_group_collapse): nominal state,
+        carried rotation, covariance and prev_id.  src: (B/G,) member indices; a negative entry skips its group, so group_fuse's `best`
+        can be passed straight in.  A device int32 tensor goes through the device form, which inspects nothing (an entry outside
+        0..G-1 leaves its group alone); anything else through the host form, which refuses an entry >= G.  Not copied: the applied
+        flags, the likelihood sums, the noise table and the carried IMU-EMA sample."""
+        G, NG = self._group_count(G, "group_collapse")
+        if _is_dev(src):
+            import torch
+            if src.dtype != torch.int32 or not src.is_cuda:
+                raise ValueError(f"group_collapse: src must be an int32 device tensor, got {src.dtype} on {src.device}")
+            self._dev_checked(src, NG, "src")
+            cur = self._order_in(src)
+            self._check(self._lib.fbus_ekf_group_collapse_dev(self._h, G, self._p(src)), "group_collapse_dev")
+            return self._order_out(cur)
+        src = self._host(src, (NG,), np.int32)
+        self._check(self._lib.fbus_ekf_group_collapse(self._h, G, self._p(src)), "group_collapse")
+
     def _nis_outputs(self, dev_like):
         if dev_like is not None:
             import torch

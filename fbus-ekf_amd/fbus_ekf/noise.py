@@ -3,7 +3,9 @@
 A noise sweep evaluates G hypotheses on one recording in one batch: noise.grid builds the Cartesian product of per-column
 scale factors around a parameter set and assigns it to the filters round-robin (filter b gets hypothesis b mod G), so every
 hypothesis is run by B / G filters.  noise.best is the other half: the per-hypothesis sum of the filters' innovation log-likelihood
-(BatchedFilter.loglik) and its arg max -- NIS cannot rank hypotheses (it falls as the noise grows), the evidence can.  numpy only.
+(BatchedFilter.loglik) and its arg max -- NIS cannot rank hypotheses (it falls as the noise grows), the evidence can.
+noise.group_weights is the numpy twin of the weights BatchedFilter.group_fuse forms on the device for contiguous groups of G filters
+(the layout grid produces when G divides B).  numpy only.
 """
 import itertools
 
@@ -62,3 +64,31 @@ def best(ll, hyp, G):
         if sel.any():
             total[g] = ll[sel].sum()
     return int(np.argmax(total)), total
+
+
+def group_weights(logw, G):
+    """The evidence weights of contiguous groups of G filters (steps 1-2 of fbus_ekf_group_fuse, include/fbus_ekf.h): group j holds
+    filters j G .. j G + G - 1.  A member is usable iff its logw is finite (NaN, +inf and -inf exclude it, with weight exactly 0);
+    with m the largest usable logw of the group, w_i = exp(logw_i - m) / sum exp(logw_k - m), summed in member order, and best is the
+    first member with logw == m.  A group without a usable member has weights 0 and best -1.
+    Returns (weight (B,) float64, best (B / G,) int32)."""
+    lw = np.asarray(logw, np.float64).ravel()
+    G = int(G)
+    if G < 1 or lw.size % G:
+        raise ValueError(f"group_weights: {lw.size} entries are not groups of {G}")
+    lw = lw.reshape(-1, G)
+    weight = np.zeros(lw.shape, np.float64)
+    best = np.full(lw.shape[0], -1, np.int32)
+    for j, row in enumerate(lw):
+        ok = np.isfinite(row)
+        if not ok.any():
+            continue
+        m = row[ok].max()
+        best[j] = int(np.flatnonzero(ok & (row == m))[0])
+        e = np.zeros(G, np.float64)
+        e[ok] = np.exp(row[ok] - m)
+        s = 0.0
+        for v in e:
+            s += v
+        weight[j] = e / s
+    return weight.ravel(), best

@@ -182,6 +182,14 @@ public:
     void loglik_dev(double* ll, int64_t* rows, int32_t* applied, int32_t* rejected) const
     { check(fbus_ekf_loglik_get_dev(h_, ll, rows, applied, rejected), "loglik_get_dev"); }
 
+    // hypothesis groups (include/fbus_ekf.h): contiguous groups of G filters, 2 <= G <= FBUS_GROUP_MAX, batch() % G == 0.  Device
+    // pointers, stream-ordered.  group_fuse_dev: logw (batch(); null = the likelihood sums) -> weight (batch()), best (batch() / G),
+    // and the moment-matched nominal (batch() / G, 19), P (batch() / G, N, N), pdiag (batch() / G, N); each output may be null.
+    // group_collapse_dev: every member of group j becomes its member src[j], bit for bit; src[j] outside 0..G-1 skips the group
+    void group_fuse_dev(int G, const double* logw, double* weight, int32_t* best, Real* nominal, Real* P, Real* pdiag) const
+    { check(fbus_ekf_group_fuse_dev(h_, G, logw, weight, best, nominal, P, pdiag), "group_fuse_dev"); }
+    void group_collapse_dev(int G, const int32_t* src) { check(fbus_ekf_group_collapse_dev(h_, G, src), "group_collapse_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

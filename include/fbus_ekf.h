@@ -108,7 +108,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *   8  fbus_ekf_set_gate, fbus_ekf_correct_nis[_dev], fbus_ekf_correct_pixels_nis[_dev], fbus_ekf_correct_corners_nis[_dev]
  *      (struct unchanged); added under 8 without a bump: fbus_ekf_set_noise[_dev], fbus_ekf_get_noise (per-filter noise; no
  *      existing meaning changed -- callers detect the feature by the symbol); likewise fbus_ekf_loglik_enable / _reset / _get /
- *      _get_dev (per-filter innovation log-likelihood sums; off by default, nothing routed differently until switched on)
+ *      _get_dev (per-filter innovation log-likelihood sums; off by default, nothing routed differently until switched on) and
+ *      fbus_ekf_group_fuse[_dev], fbus_ekf_group_collapse[_dev] (hypothesis groups; new kernels, nothing existing changed)
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -590,6 +591,51 @@ int fbus_ekf_loglik_enable(fbus_ekf_t h, int on);
 int fbus_ekf_loglik_reset(fbus_ekf_t h);
 int fbus_ekf_loglik_get(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
 int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
+
+/* ---- hypothesis groups: evidence-weighted fusion and collapse (NO reference counterpart) ---------------------------------------
+ * The reference runs one filter on one thread (C++/src/filter.cpp:190-250) and has no bank of hypotheses; these two calls are what a
+ * multiple-model bank does with the evidence above.  Group j holds the G consecutive filters j G .. j G + G - 1 (the layout a noise
+ * grid of G hypotheses has when G divides B), 2 <= G <= FBUS_GROUP_MAX, B % G == 0, any G in that range (a 3 x 3 grid is G = 9).
+ * Groups are per handle.
+ *
+ * fbus_ekf_group_fuse: per-filter log-weights -> weights, the best member, and the moment-matched state and covariance of each group.
+ *   logw     [B] double; NULL = the handle's likelihood sums `ll` (the accumulator never moves: a captured call reads the sums current at
+ *            its replay; FBUS_ERR_INVALID before the first fbus_ekf_loglik_enable(h, 1))
+ *   weight   [B] double            best  [B/G] int32 (member index 0..G-1, or -1)
+ *   nominal  [B/G][19], P [B/G][N][N], pdiag [B/G][N] in the handle's dtype and in fbus_ekf_get_state's order
+ *   Every output may be NULL (not written).  Members i = 0..G-1 of one group, in member order throughout:
+ *   1. member i is usable iff logw[i] is finite (NaN, +inf, -inf exclude it).  No usable member: weight = 0 for the whole group,
+ *      best = -1, and nominal, P, pdiag are member 0's own values, copied.
+ *   2. m = the largest usable logw; e_i = exp(logw_i - m), s = sum e_i, w_i = e_i / s in double; an excluded member gets exactly 0;
+ *      best = the smallest i with logw_i == m.
+ *   3. The chart is the best member's nominal state x*.  delta_i in R^N, error-state order p v theta ba bg [g]: plain differences
+ *      against x* except delta_theta_i = Log(conj(q*) (x) q_i): d = conj(q*) (x) q_i, negated if d_w < 0, n = |d_vec|,
+ *      delta_theta = (2 atan2(n, d_w) / n) d_vec (0 when n == 0) -- the inverse of the injection q <- normalize(q (x) dq(dtheta))
+ *      (matlab/MeasureUpdate.m:92-98).  d and delta_theta are formed in double for both record types.
+ *   4. mu = sum w_i delta_i.  The fused nominal is x* + mu on p, v, ba, bg (and g for N = 18; g of the best member for N = 15) and
+ *      q = normalize(q* (x) dq(mu_theta)).
+ *   5. Pbar = sum w_i (P_i + (delta_i - mu)(delta_i - mu)'), symmetric by construction; pdiag is its diagonal.  Each P_i stays in its
+ *      own member's tangent space: the first-order transport of P_i to the chart x* is omitted, as in standard IMM mixing.
+ *   6. A member with weight exactly 0 is skipped by a select, not multiplied by 0: a diverged hypothesis (NaN in its record, logw NaN
+ *      or -inf) does not poison its group.
+ *   7. The records, the applied flags, the likelihood sums and the noise table are not touched.
+ *   8. Every sum runs in member order: two calls on the same inputs give bit-identical outputs whatever the batch size.
+ *
+ * fbus_ekf_group_collapse: for every group with src[j] in 0..G-1, every member's whole packed record (nominal state, carried rotation,
+ *   packed covariance, prev_id) becomes member src[j]'s record, bit for bit.  Any other src[j] -- negative is the documented way to
+ *   skip a group, and `best` of group_fuse is -1 for a group without a usable member, so it can be passed straight in -- leaves the
+ *   group's bytes alone; the device form inspects nothing and the kernel never forms an address from such a value.  NOT copied: the
+ *   applied flags, the likelihood sums, the noise table and the carried IMU-EMA sample.
+ *
+ * The _dev forms take device pointers, are stream-ordered on the handle's stream and may be captured in a graph; the host forms stage
+ * their arrays and wait.  All checks are made before anything is launched: a NULL handle is FBUS_ERR_INVALID; G out of range or
+ * B % G != 0, an output that overlaps the records (the rule of fbus_ekf_snapshot_dev), src == NULL, and in the host form of collapse an
+ * entry >= G are FBUS_ERR_INVALID with a fbus_ekf_last_error text.  Added under ABI 8 without a bump: detect the feature by symbol. */
+#define FBUS_GROUP_MAX 64
+int fbus_ekf_group_fuse_dev(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag);
+int fbus_ekf_group_fuse(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag);
+int fbus_ekf_group_collapse_dev(fbus_ekf_t h, int G, const int32_t* src);
+int fbus_ekf_group_collapse(fbus_ekf_t h, int G, const int32_t* src);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
