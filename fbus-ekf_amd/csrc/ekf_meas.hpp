@@ -1465,13 +1465,180 @@ struct alignas(16) MeasLDS {
 };
 
 // =================================================================================
-// correct() from corner pixels: all visible markers, 2 (left camera) or 4 (stereo) reprojection rows per corner, one
-// linearisation point.  One filter per lane; NR waves ("roles") per 64-filter tile divide the markers among themselves
-// (role r folds markers r, r + NR, ...; their sums meet in LDS, in role order) and role 0 applies the update.
-// NO = NisOut<T> (fbus_ekf_correct_pixels_nis*, fbus_ekf_correct_corners_nis*; NR = 1 only, instantiated in a family of its own:
-// kernels_tu.hip "measnis"): the NIS and the dof of every filter, and the gate (meas_update_tail's NisState).
+// What the measurement kernels share (correct_pixels2_kernel, correct_corners2_kernel, frame_meas_kernel below and
+// correct_pixels_split_kernel, ekf_meas_split.hpp): the marker map on its way to LDS, the fetch of one marker slot, the fold of one slot,
+// the roles' sums through LDS, the filter's pose in double and the choice of the tail.  Each is written once, here.
+//
+// They are function-like MACROS (MEAS_*), and stay defined behind this header because ekf_meas_split.hpp uses them.  Every one of them was
+// first written as a __forceinline__ function (free, or a member of a small struct): each changed the instruction streams of 2 to 14 of the
+// 14 kernels of one unit -- they sit at the 256 / 512-register limits, where the allocator's result moves with the order in which the
+// inliner hands over the same operations (EXPERIMENTS -1.23 has the counts per piece).  A macro hands the compiler the token stream the
+// kernels held before, so the code objects are the ones that were measured.  Rules that keep them readable:
+//   * a macro names every variable of the kernel it reads or writes among its arguments, except where its comment says otherwise;
+//   * what it declares in the enclosing scope is listed in its comment;
+//   * the record types and everything that is not on a kernel's path are ordinary C++.
 // =================================================================================
-// the filters that leave without an update: nis = 0, dof = 0
+
+// One marker slot of a filter as measured: the id and the image coordinates of the four corners.
+// PixMeas (pixel rows): 8 (+ 8) coordinates.  CAM: 0 = left camera or stereo by the right pointer (one kernel for both), 1 = left camera
+// only, 2 = stereo only: compiled apart, the left-camera kernel carries neither the second camera's image points nor the stereo fold's
+// register pressure.
+// CornerMeas (corner rows): left 8 + right 8 image coordinates, or the 12 coordinates of the corners themselves (VIS_CORNERS3D).
+template <typename T, int CAM> struct PixMeas { int id; T l[8], r[CAM == 1 ? 1 : 8]; };
+template <typename T> struct CornerMeas { int id; T l[12], r[8]; };
+
+// The marker map (ID2SLOT, MKC) -> MeasLDS TBL by the NT threads of the workgroup, 16 bytes per thread and step, in two phases:
+// MEAS_MAP_LOAD requests it into registers, MEAS_MAP_STORE (same scope) writes them to LDS.  The kernel requests its first marker and its
+// record between the two, with its own order_fence()s: the map's loads are then the oldest in flight when the stores wait for them.
+// Declares NI, NM, PI, PM, si, sm, di, dm, vi, vm.
+#define MEAS_MAP_LOAD(NT, ID2SLOT, MKC, TBL)                                                                                            \
+    constexpr int NI = (int)sizeof(short) * (FBUS_MAX_MARKER_ID + 1) / 16, NM = (int)sizeof(double) * FBUS_MAX_MARKERS * MKC_STRIDE / 16; \
+    constexpr int PI = (NI + NT - 1) / NT, PM = (NM + NT - 1) / NT;                                                                    \
+    const u32x4* si = reinterpret_cast<const u32x4*>(ID2SLOT);                                                                          \
+    const u32x4* sm = reinterpret_cast<const u32x4*>(MKC);                                                                              \
+    u32x4* di = reinterpret_cast<u32x4*>(TBL.id2slot);                                                                                  \
+    u32x4* dm = reinterpret_cast<u32x4*>(TBL.mkc);                                                                                      \
+    u32x4 vi[PI], vm[PM];                                                                                                               \
+    _Pragma("unroll") for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; vi[q] = si[i < NI ? i : 0]; }                  \
+    _Pragma("unroll") for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; vm[q] = sm[i < NM ? i : 0]; }
+#define MEAS_MAP_STORE(NT)                                                                                                              \
+    _Pragma("unroll") for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; if (i < NI) di[i] = vi[q]; }                   \
+    _Pragma("unroll") for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; if (i < NM) dm[i] = vm[q]; }
+
+// Slot O (= filter * M + marker) of the measurement arrays into the record MM: the id and the 8 (+ 8) image coordinates as 16-byte loads
+// (a slot's 8 coordinates are 32 / 64 contiguous bytes).  The body of a kernel's fetch lambda.  LW: coordinates per slot of LEFT; RBASE:
+// the array the second eight come from.  Declares EP, pl, pr.
+#define MEAS_FETCH_PIXELS(T, CAM, MM, IDS, LEFT, LW, RBASE, O)                                                                          \
+    constexpr int EP = 16 / (int)sizeof(T);                                                                                             \
+    MM.id = IDS[O];                                                                                                                     \
+    const u32x4* pl = reinterpret_cast<const u32x4*>(LEFT + O * LW);                                                                    \
+    const u32x4* pr = reinterpret_cast<const u32x4*>((RBASE) + O * 8);                                                                  \
+    _Pragma("unroll") for (int c = 0; c < 8 / EP; ++c) {                                                                                \
+        const u32x4 vl = pl[c];                                                                                                         \
+        const T* el = reinterpret_cast<const T*>(&vl);                                                                                  \
+        _Pragma("unroll") for (int k = 0; k < EP; ++k) MM.l[c * EP + k] = el[k];                                                        \
+        if constexpr (CAM != 1) {                                                                                                       \
+            const u32x4 vr = pr[c];                                                                                                     \
+            const T* er = reinterpret_cast<const T*>(&vr);                                                                              \
+            _Pragma("unroll") for (int k = 0; k < EP; ++k) MM.r[c * EP + k] = er[k];                                                    \
+        }                                                                                                                               \
+    }
+// the corner rows' slot: 8 + 8 image coordinates, or (C3D) the 12 coordinates of the corners themselves
+#define MEAS_FETCH_CORNERS(T, MM, IDS, LEFT, LW, RBASE, C3D, O)                                                                         \
+    constexpr int EP = 16 / (int)sizeof(T);                                                                                             \
+    MM.id = IDS[O];                                                                                                                     \
+    const u32x4* pl = reinterpret_cast<const u32x4*>(LEFT + O * LW);                                                                    \
+    const u32x4* pr = reinterpret_cast<const u32x4*>((RBASE) + O * 8);                                                                  \
+    _Pragma("unroll") for (int c = 0; c < 12 / EP; ++c) {                                                                               \
+        const u32x4 vl = pl[(c < 8 / EP || C3D) ? c : 0];                                                                               \
+        const T* el = reinterpret_cast<const T*>(&vl);                                                                                  \
+        _Pragma("unroll") for (int k = 0; k < EP; ++k) MM.l[c * EP + k] = el[k];                                                        \
+    }                                                                                                                                   \
+    _Pragma("unroll") for (int c = 0; c < 8 / EP; ++c) {                                                                                \
+        const u32x4 vr = pr[c];                                                                                                         \
+        const T* er = reinterpret_cast<const T*>(&vr);                                                                                  \
+        _Pragma("unroll") for (int k = 0; k < EP; ++k) MM.r[c * EP + k] = er[k];                                                        \
+    }
+// The four corners C of a measured marker MM in the left camera frame: refractive triangulation, pin-hole DLT (vision.cpp:395-466: the
+// 4 x 4 eigen-solver stays in T) or the 3-D corners as given.  The body of a kernel's corners lambda (it returns from it).
+#define MEAS_CORNERS_OF(T, NZ, GEOMETRY, VC, VCT, MM, C)                                                                                \
+    if (GEOMETRY == VIS_REFRACTIVE) { tri_corners_refractive<T, NZ>(VC, MM.l, MM.r, C); return; }                                       \
+    _Pragma("unroll") for (int k = 0; k < 4; ++k) {                                                                                     \
+        if (GEOMETRY == VIS_CORNERS3D) {                                                                                                \
+            _Pragma("unroll") for (int i = 0; i < 3; ++i) C[k][i] = (double)MM.l[(3 * k + i) % (int)(sizeof(MM.l) / sizeof(T))];        \
+        } else {                                                                                                                        \
+            T o3[3];                                                                                                                    \
+            pinhole_corner(VCT, MM.l[2 * k], MM.l[2 * k + 1], MM.r[2 * k], MM.r[2 * k + 1], o3);                                        \
+            _Pragma("unroll") for (int i = 0; i < 3; ++i) C[k][i] = (double)o3[i];                                                      \
+        }                                                                                                                               \
+    }
+
+// The filter's position PD and carried rotation RD in double from the nominal state NOM (or its p, q, R part), and pil (filter_pil).
+// Declares PIL.
+#define MEAS_POSE_OF(L, NOM, MC, PD, RD, PIL)                                                                                           \
+    _Pragma("unroll") for (int i = 0; i < 3; ++i) PD[i] = (double)NOM[L::OFF_P3 + i];                                                   \
+    _Pragma("unroll") for (int i = 0; i < 9; ++i) RD[i] = (double)NOM[L::OFF_R + i];                                                    \
+    double PIL[3];                                                                                                                      \
+    filter_pil(RD, MC.P_IL, PIL);
+
+// The body of the pixel fold's loop: the slot CUR into the sums ACC.  EVERY slot is folded; one whose id is not in the map with slot 0's
+// frame and weight 0 (see pixel_fold_marker).  The image points of a slot that carries no marker of the map may be anything (padding is the
+// caller's: NaN included), and 0 x NaN would poison the sums: such a slot is folded with zeros.  NFOLD: the markers of the map folded so
+// far.  The left-only kernel of the square port (CAM = 1, NZ) folds in the camera frame.
+#define MEAS_FOLD_PIXEL_SLOT(T, NZ, CAM, NIS, ACC, NFOLD, TBL, CUR, STEREO, PD, RD, PIL, MC, SIZE)                                      \
+    {                                                                                                                                   \
+        const bool ok = CUR.id >= 0 && CUR.id <= FBUS_MAX_MARKER_ID;                                                                    \
+        const int slot = ok ? (int)TBL.id2slot[ok ? CUR.id : 0] : -1;                                                                   \
+        {                                                                                                                               \
+            const double wgt = slot >= 0 ? 1.0 : 0.0;                                                                                   \
+            const int sl = slot >= 0 ? slot : 0;                                                                                        \
+            double mk[9];                                                                                                               \
+            _Pragma("unroll") for (int q = 0; q < 9; ++q) mk[q] = TBL.mkc[sl * MKC_STRIDE + q];                                         \
+            constexpr int NRR = sizeof(CUR.r) / sizeof(T);                                                                              \
+            T yl_[8], yr_[NRR];                                                                                                         \
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) yl_[k] = slot >= 0 ? CUR.l[k] : T(0);                                         \
+            _Pragma("unroll") for (int k = 0; k < NRR; ++k) yr_[k] = slot >= 0 ? CUR.r[k] : T(0);                                       \
+            if constexpr (CAM == 1) pixel_fold_marker<1, T, NZ, 4, 0, NZ, NIS>(ACC, PD, RD, PIL, MC, mk, yl_, yl_, SIZE, wgt);          \
+            else if constexpr (CAM == 2) pixel_fold_marker_stereo_halves<T, NZ, NIS>(ACC, PD, RD, PIL, MC, mk, yl_, yr_, SIZE, wgt);    \
+            else if (STEREO) pixel_fold_marker_stereo_halves<T, NZ, NIS>(ACC, PD, RD, PIL, MC, mk, yl_, yr_, SIZE, wgt);                \
+            else pixel_fold_marker<1, T, NZ, 4, 0, false, NIS>(ACC, PD, RD, PIL, MC, mk, yl_, yl_, SIZE, wgt);                          \
+            NFOLD += wgt;                                                                                                               \
+        }                                                                                                                               \
+    }
+// The corner fold's: the slot MM into the sums ACC, if its id is in the map.  The body of a kernel's fold_marker lambda: it returns
+// whether.  CORNERS: the kernel's corners lambda.
+#define MEAS_FOLD_CORNER_SLOT(NIS, ACC, TBL, MM, CORNERS, PD, RD, PIL, MC, SIZE)                                                        \
+    const bool ok = MM.id >= 0 && MM.id <= FBUS_MAX_MARKER_ID;                                                                          \
+    const int slot = ok ? (int)TBL.id2slot[ok ? MM.id : 0] : -1;                                                                        \
+    if (slot < 0) return false;                                                                                                         \
+    double mk[9], C[4][3];                                                                                                              \
+    _Pragma("unroll") for (int q = 0; q < 9; ++q) mk[q] = TBL.mkc[slot * MKC_STRIDE + q];                                               \
+    CORNERS(MM, C);                                                                                                                     \
+    corner_fold_marker<NIS>(ACC, PD, RD, PIL, MC, mk, C, SIZE);                                                                         \
+    return true;
+// MODE_NEAREST: the nearest visible marker of a filter by its first corner, folded.  CPP (the C++ dialect, filter.cpp:639-664): hysteresis --
+// the previous marker (PREV_RAW) keeps its place while it is within SWITCH_THRES of the nearest -- and NEW_PREV is the marker taken.
+// FETCH, CORNERS, FOLD: the kernel's lambdas; CUR holds slot 0 on entry.
+#define MEAS_FOLD_NEAREST_CORNER(CPP, FETCH, CORNERS, FOLD, CUR, NXT, M, PREV_RAW, SWITCH_THRES, NFOLD, NEW_PREV)                       \
+    {                                                                                                                                   \
+        const int prev_id = (int)PREV_RAW;                                                                                              \
+        int min_i = -1, prev_i = -1;                                                                                                    \
+        double min_d = 10.0, prev_d = 0.0;                                                                                              \
+        _Pragma("unroll 1") for (int i = 0; i < M; ++i) {                                                                               \
+            FETCH(i + 1 < M ? i + 1 : M - 1, NXT);                                                                                      \
+            if (CUR.id >= 0) {                                                                                                          \
+                double C[4][3];                                                                                                         \
+                CORNERS(CUR, C);                                                                                                        \
+                const double dist = sqrt(C[0][0] * C[0][0] + C[0][1] * C[0][1] + C[0][2] * C[0][2]);                                    \
+                if (dist < min_d) { min_d = dist; min_i = i; }                                                                          \
+                if (CPP && CUR.id == prev_id) { prev_d = dist; prev_i = i; }                                                            \
+            }                                                                                                                           \
+            CUR = NXT;                                                                                                                  \
+        }                                                                                                                               \
+        if (min_i >= 0) {                                                                                                               \
+            if (CPP && prev_i >= 0 && fabs(prev_d - min_d) < SWITCH_THRES && prev_d != 0.0) min_i = prev_i;                             \
+            FETCH(min_i, CUR);                                                                                                          \
+            if (FOLD(CUR)) { NFOLD = 1.0; if (CPP) NEW_PREV = CUR.id; }                                                                 \
+        }                                                                                                                               \
+    }
+
+// The roles' partial sums through LDS: value i of role r >= 1 at PART_MEM[((r - 1) * (NVAL + 1) + i) * 64 + lane], the count of its folded
+// markers behind them.  Role 0 adds them up in role order (behind the workgroup's barrier).
+#define MEAS_ROLES_PUT(PART_MEM, ROLE, LANE, ACC, NFOLD)                                                                                \
+    {                                                                                                                                   \
+        double* part = PART_MEM + ((ROLE - 1) * (PixAcc::NVAL + 1)) * 64 + LANE;                                                        \
+        _Pragma("unroll") for (int i = 0; i < PixAcc::NVAL; ++i) part[i * 64] = ACC.at(i);                                              \
+        part[PixAcc::NVAL * 64] = NFOLD;                                                                                                \
+    }
+#define MEAS_ROLES_ADD(NR, PART_MEM, LANE, ACC, NFOLD)                                                                                  \
+    _Pragma("unroll") for (int r = 1; r < NR; ++r) {                                                                                    \
+        const double* part = PART_MEM + ((r - 1) * (PixAcc::NVAL + 1)) * 64 + LANE;                                                     \
+        _Pragma("unroll") for (int i = 0; i < PixAcc::NVAL; ++i) ACC.at(i) += part[i * 64];                                             \
+        NFOLD += part[PixAcc::NVAL * 64];                                                                                               \
+    }
+
+// The outputs of the NIS kernels (NO = NisOut<T>, ...; NR = 1 only, instantiated in families of their own: kernels_tu.hip "measnis", ...):
+// the NIS and the dof of every filter.  The filters that leave without an update: nis = 0, dof = 0
 template <typename T>
 __device__ __forceinline__ void nis_none(const NisOut<T>& o, int b)
 {
@@ -1505,6 +1672,25 @@ __device__ __forceinline__ bool lik_tail(const NisOut<T>& o, const NoiseIn& ni, 
     if (ns.reject) lc.rejected();
     return !ns.reject;
 }
+// The tail of a per-call kernel by its trailing pack NO, and applied[b]: the plain tail, the NIS one, the one with the likelihood sums.
+// COL: see lik_tail; ROT: the rotation the sums are finished with; W: 1 / R.  Uses the kernel's T, N, NO, NIS, nout, no, b, rs, lane, acc,
+// applied and gpark_mem.  The packed forms RETURN from the kernel.
+#define MEAS_APPLY_TAIL(COL, ROT, W, NEW_PREV)                                                                                          \
+    if constexpr (has_lik<NO...>()) {                                                                                                   \
+        applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), COL, b, rs, lane, acc, ROT, W, NEW_PREV, gpark_mem + lane) ? 1 : 0; \
+        return;                                                                                                                         \
+    }                                                                                                                                   \
+    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, ROT, W, NEW_PREV, gpark_mem + lane) ? 1 : 0; return; }     \
+    meas_update_tail<T, N>(rs, lane, acc, ROT, W, NEW_PREV, gpark_mem + lane);                                                          \
+    applied[b] = 1;
+
+// =================================================================================
+// correct() from corner pixels: all visible markers, 2 (left camera) or 4 (stereo) reprojection rows per corner, one
+// linearisation point.  One filter per lane; NR waves ("roles") per 64-filter tile divide the markers among themselves
+// (role r folds markers r, r + NR, ...; their sums meet in LDS, in role order) and role 0 applies the update.
+// NO = NisOut<T> (fbus_ekf_correct_pixels_nis*, fbus_ekf_correct_corners_nis*; NR = 1 only, instantiated in a family of its own:
+// kernels_tu.hip "measnis"): the NIS and the dof of every filter, and the gate (meas_update_tail's NisState).
+// =================================================================================
 template <typename T, int N, int NR, bool NZ, int CAM = 0, typename... NO>
 __global__ void __launch_bounds__(64 * NR)
 correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ left,
@@ -1531,66 +1717,29 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
     constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? (has_lik<NO...>() ? 37 : 36) * 64 : 1;
     __shared__ double part_mem[PART_N > GPARK_N ? PART_N : GPARK_N];
     T* gpark_mem = reinterpret_cast<T*>(part_mem);
-    // CAM: 0 = left camera or stereo by the right pointer (one kernel for both), 1 = left camera only, 2 = stereo only: compiled
-    // apart, the left-camera kernel carries neither the second camera's image points nor the stereo fold's register pressure
-    struct Meas { int id; T l[8], r[CAM == 1 ? 1 : 8]; };
+    using Meas = PixMeas<T, CAM>;
     const bool stereo = CAM == 0 ? right != nullptr : CAM == 2;
-    // the id and the 8 (+ 8) image coordinates of marker slot i: 16-byte loads (a slot's 8 coordinates are 32 / 64 contiguous bytes)
     auto fetch = [&](int i, Meas& mm) __attribute__((always_inline)) {
         const size_t o = (size_t)bc * M + i;
-        constexpr int EP = 16 / (int)sizeof(T);
-        mm.id = ids[o];
-        const u32x4* pl = reinterpret_cast<const u32x4*>(left + o * 8);
-        const u32x4* pr = reinterpret_cast<const u32x4*>((stereo ? right : left) + o * 8);
-#pragma unroll
-        for (int c = 0; c < 8 / EP; ++c) {
-            const u32x4 vl = pl[c];
-            const T* el = reinterpret_cast<const T*>(&vl);
-#pragma unroll
-            for (int k = 0; k < EP; ++k) mm.l[c * EP + k] = el[k];
-            if constexpr (CAM != 1) {
-                const u32x4 vr = pr[c];
-                const T* er = reinterpret_cast<const T*>(&vr);
-#pragma unroll
-                for (int k = 0; k < EP; ++k) mm.r[c * EP + k] = er[k];
-            }
-        }
+        MEAS_FETCH_PIXELS(T, CAM, mm, ids, left, 8, stereo ? right : left, o)
     };
     Meas cur, nxt;
     T pqr[L::NPQR];
     if constexpr (NR == 1) simd_stagger<FBUS_X_STAGGER_MEAS>();
     {
         // the marker map -> LDS (all threads), this role's first marker, the pose part of the nominal state
-        constexpr int NI = (int)sizeof(short) * (FBUS_MAX_MARKER_ID + 1) / 16, NM = (int)sizeof(double) * FBUS_MAX_MARKERS * MKC_STRIDE / 16;
-        constexpr int PI = (NI + NT - 1) / NT, PM = (NM + NT - 1) / NT;
-        const u32x4* si = reinterpret_cast<const u32x4*>(id2slot);
-        const u32x4* sm = reinterpret_cast<const u32x4*>(mc.mkc);
-        u32x4* di = reinterpret_cast<u32x4*>(tbl.id2slot);
-        u32x4* dm = reinterpret_cast<u32x4*>(tbl.mkc);
-        u32x4 vi[PI], vm[PM];
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; vi[q] = si[i < NI ? i : 0]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; vm[q] = sm[i < NM ? i : 0]; }
+        MEAS_MAP_LOAD(NT, id2slot, mc.mkc, tbl)
         order_fence();
         if (M > 0) fetch((int)role < M ? (int)role : M - 1, cur);
         order_fence();
         load_chunks<T, N, 0, RC::CH_PQR>(rs, lane, pqr);
         order_fence();
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; if (i < NI) di[i] = vi[q]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; if (i < NM) dm[i] = vm[q]; }
+        MEAS_MAP_STORE(NT)
         order_fence();
     }
     if constexpr (NR > 1) meas_barrier(); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     double pd[3], Rd[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pd[i] = (double)pqr[L::OFF_P3 + i];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rd[i] = (double)pqr[L::OFF_R + i];
-    double pil[3];
-    filter_pil(Rd, mc.P_IL, pil);
+    MEAS_POSE_OF(L, pqr, mc, pd, Rd, pil)
     PixAcc acc;
     acc.clear();
     if constexpr (NIS) acc.clear_nis();
@@ -1599,49 +1748,17 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
 #pragma unroll 1
     for (int i = (int)role; i < last; i += NR) {
         fetch(i + NR < M ? i + NR : M - 1, nxt);                // always a fresh load (no conditional merge of the two records)
-        const bool ok = cur.id >= 0 && cur.id <= FBUS_MAX_MARKER_ID;
-        const int slot = ok ? (int)tbl.id2slot[ok ? cur.id : 0] : -1;
-        {
-            // every slot is folded; one whose id is not in the map with slot 0's frame and weight 0 (see pixel_fold_marker)
-            const double wgt = slot >= 0 ? 1.0 : 0.0;
-            const int sl = slot >= 0 ? slot : 0;
-            double mk[9];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[sl * MKC_STRIDE + q];
-            // the image points of a slot that carries no marker of the map may be anything (padding is the caller's: NaN included), and
-            // 0 x NaN would poison the sums: such a slot is folded with zeros
-            constexpr int NRR = sizeof(cur.r) / sizeof(T);
-            T yl_[8], yr_[NRR];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) yl_[k] = slot >= 0 ? cur.l[k] : T(0);
-#pragma unroll
-            for (int k = 0; k < NRR; ++k) yr_[k] = slot >= 0 ? cur.r[k] : T(0);
-            if constexpr (CAM == 1) pixel_fold_marker<1, T, NZ, 4, 0, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-            else if constexpr (CAM == 2) pixel_fold_marker_stereo_halves<T, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-            else if (stereo) pixel_fold_marker_stereo_halves<T, NZ, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-            else pixel_fold_marker<1, T, NZ, 4, 0, false, NIS>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-            nfold += wgt;
-        }
+        MEAS_FOLD_PIXEL_SLOT(T, NZ, CAM, NIS, acc, nfold, tbl, cur, stereo, pd, Rd, pil, mc, size)
         cur = nxt;
     }
     if constexpr (NR > 1) {
-        // partial sums through LDS: value i of role r at part_mem[((r - 1) * (NVAL + 1) + i) * 64 + lane]
         if (role != 0) {
-            double* part = part_mem + ((role - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < PixAcc::NVAL; ++i) part[i * 64] = acc.at(i);
-            part[PixAcc::NVAL * 64] = nfold;
+            MEAS_ROLES_PUT(part_mem, role, lane, acc, nfold)
             meas_barrier();
             return;
         }
         meas_barrier();
-#pragma unroll
-        for (int r = 1; r < NR; ++r) {
-            const double* part = part_mem + ((r - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < PixAcc::NVAL; ++i) acc.at(i) += part[i * 64];
-            nfold += part[PixAcc::NVAL * 64];
-        }
+        MEAS_ROLES_ADD(NR, part_mem, lane, acc, nfold)
     }
     if (!live || nfold == 0.0) {
         if (b < B) { applied[b] = 0; if constexpr (NIS) nis_none(nout, b); }
@@ -1651,22 +1768,10 @@ correct_pixels2_kernel(T* __restrict__ recs, int B, int M, const int* __restrict
         acc.to_imu_frame(mc.adjL);
         double RM[9];
         PixAcc::camera_rotation(Rd, mc.McL, RM);
-        if constexpr (has_lik<NO...>()) {
-            applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPIX, b, rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0;
-            return;
-        }
-        if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
-        meas_update_tail<T, N>(rs, lane, acc, RM, 1.0 / rpix, -1, gpark_mem + lane);
-        applied[b] = 1;
+        MEAS_APPLY_TAIL(NOISE_RPIX, RM, 1.0 / rpix, -1)
         return;
     }
-    if constexpr (has_lik<NO...>()) {
-        applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPIX, b, rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0;
-        return;
-    }
-    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane) ? 1 : 0; return; }
-    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / rpix, -1, gpark_mem + lane);
-    applied[b] = 1;
+    MEAS_APPLY_TAIL(NOISE_RPIX, Rd, 1.0 / rpix, -1)
 }
 
 
@@ -1701,122 +1806,43 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
     constexpr int PART_N = NR > 1 ? (NR - 1) * (PixAcc::NVAL + 1) * 64 : 1, GPARK_N = sizeof(T) == 8 ? (has_lik<NO...>() ? 37 : 36) * 64 : 1;
     __shared__ double part_mem[PART_N > GPARK_N ? PART_N : GPARK_N];
     T* gpark_mem = reinterpret_cast<T*>(part_mem);
-    struct Meas { int id; T l[12], r[8]; };
+    using Meas = CornerMeas<T>;
     const bool c3d = geometry == VIS_CORNERS3D;
     const int lw = c3d ? 12 : 8;
     auto fetch = [&](int i, Meas& mm) __attribute__((always_inline)) {
         const size_t o = (size_t)bc * M + i;
-        constexpr int EP = 16 / (int)sizeof(T);
-        mm.id = ids[o];
-        const u32x4* pl = reinterpret_cast<const u32x4*>(left + o * lw);
-        const u32x4* pr = reinterpret_cast<const u32x4*>((c3d ? left : right) + o * 8);
-#pragma unroll
-        for (int c = 0; c < 12 / EP; ++c) {
-            const u32x4 vl = pl[(c < 8 / EP || c3d) ? c : 0];
-            const T* el = reinterpret_cast<const T*>(&vl);
-#pragma unroll
-            for (int k = 0; k < EP; ++k) mm.l[c * EP + k] = el[k];
-        }
-#pragma unroll
-        for (int c = 0; c < 8 / EP; ++c) {
-            const u32x4 vr = pr[c];
-            const T* er = reinterpret_cast<const T*>(&vr);
-#pragma unroll
-            for (int k = 0; k < EP; ++k) mm.r[c * EP + k] = er[k];
-        }
+        MEAS_FETCH_CORNERS(T, mm, ids, left, lw, c3d ? left : right, c3d, o)
     };
-    // the four corners of a measured marker in the left camera frame
-    auto corners = [&](const Meas& mm, double (&C)[4][3]) __attribute__((always_inline)) {
-        if (geometry == VIS_REFRACTIVE) { tri_corners_refractive<T, NZ>(vc, mm.l, mm.r, C); return; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (geometry == VIS_CORNERS3D) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) C[k][i] = (double)mm.l[3 * k + i];
-            } else {
-                T o3[3];                                 // pin-hole DLT (vision.cpp:395-466): the 4 x 4 eigen-solver stays in T
-                pinhole_corner(vct, mm.l[2 * k], mm.l[2 * k + 1], mm.r[2 * k], mm.r[2 * k + 1], o3);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) C[k][i] = (double)o3[i];
-            }
-        }
-    };
+    auto corners = [&](const Meas& mm, double (&C)[4][3]) __attribute__((always_inline)) { MEAS_CORNERS_OF(T, NZ, geometry, vc, vct, mm, C) };
     Meas cur, nxt;
     T pqr[L::NPQR];
     T prev_raw = T(0);
     if constexpr (NR == 1) simd_stagger<FBUS_X_STAGGER_MEAS>();
     {
-        constexpr int NI = (int)sizeof(short) * (FBUS_MAX_MARKER_ID + 1) / 16, NM = (int)sizeof(double) * FBUS_MAX_MARKERS * MKC_STRIDE / 16;
-        constexpr int PI = (NI + NT - 1) / NT, PM = (NM + NT - 1) / NT;
-        const u32x4* si = reinterpret_cast<const u32x4*>(id2slot);
-        const u32x4* sm = reinterpret_cast<const u32x4*>(mc.mkc);
-        u32x4* di = reinterpret_cast<u32x4*>(tbl.id2slot);
-        u32x4* dm = reinterpret_cast<u32x4*>(tbl.mkc);
-        u32x4 vi[PI], vm[PM];
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; vi[q] = si[i < NI ? i : 0]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; vm[q] = sm[i < NM ? i : 0]; }
+        MEAS_MAP_LOAD(NT, id2slot, mc.mkc, tbl)
         order_fence();
         if (M > 0) fetch((int)role < M ? (int)role : M - 1, cur);
         if (mode == MODE_NEAREST && dialect == DIALECT_CPP) prev_raw = recs[elem_index<T, N>(bc, L::OFF_PREV)];
         order_fence();
         load_chunks<T, N, 0, RC::CH_PQR>(rs, lane, pqr);
         order_fence();
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; if (i < NI) di[i] = vi[q]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; if (i < NM) dm[i] = vm[q]; }
+        MEAS_MAP_STORE(NT)
         order_fence();
     }
     if constexpr (NR > 1) meas_barrier(); else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     double pd[3], Rd[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pd[i] = (double)pqr[L::OFF_P3 + i];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rd[i] = (double)pqr[L::OFF_R + i];
-    double pil[3];
-    filter_pil(Rd, mc.P_IL, pil);
+    MEAS_POSE_OF(L, pqr, mc, pd, Rd, pil)
     PixAcc acc;
     acc.clear();
     if constexpr (NIS) acc.clear_nis();
     double nfold = 0.0;
     int new_prev = -1;
     auto fold_marker = [&](const Meas& mm) __attribute__((always_inline)) {
-        const bool ok = mm.id >= 0 && mm.id <= FBUS_MAX_MARKER_ID;
-        const int slot = ok ? (int)tbl.id2slot[ok ? mm.id : 0] : -1;
-        if (slot < 0) return false;
-        double mk[9], C[4][3];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[slot * MKC_STRIDE + q];
-        corners(mm, C);
-        corner_fold_marker<NIS>(acc, pd, Rd, pil, mc, mk, C, size);
-        return true;
+        MEAS_FOLD_CORNER_SLOT(NIS, acc, tbl, mm, corners, pd, Rd, pil, mc, size)
     };
     if (mode == MODE_NEAREST) {
-        // one role only (the launcher): nearest visible marker by its first corner
-        if (live) {
-            const int prev_id = (int)prev_raw;
-            int min_i = -1, prev_i = -1;
-            double min_d = 10.0, prev_d = 0.0;
-#pragma unroll 1
-            for (int i = 0; i < M; ++i) {
-                fetch(i + 1 < M ? i + 1 : M - 1, nxt);
-                if (cur.id >= 0) {
-                    double C[4][3];
-                    corners(cur, C);
-                    const double dist = sqrt(C[0][0] * C[0][0] + C[0][1] * C[0][1] + C[0][2] * C[0][2]);
-                    if (dist < min_d) { min_d = dist; min_i = i; }
-                    if (dialect == DIALECT_CPP && cur.id == prev_id) { prev_d = dist; prev_i = i; }
-                }
-                cur = nxt;
-            }
-            if (min_i >= 0) {
-                if (dialect == DIALECT_CPP && prev_i >= 0 && fabs(prev_d - min_d) < switch_thres && prev_d != 0.0) min_i = prev_i;
-                fetch(min_i, cur);
-                if (fold_marker(cur)) { nfold = 1.0; if (dialect == DIALECT_CPP) new_prev = cur.id; }
-            }
-        }
+        // one role only (the launcher)
+        if (live) MEAS_FOLD_NEAREST_CORNER(dialect == DIALECT_CPP, fetch, corners, fold_marker, cur, nxt, M, prev_raw, switch_thres, nfold, new_prev)
     } else {
         const int last = live ? M : 0;
 #pragma unroll 1
@@ -1828,34 +1854,19 @@ correct_corners2_kernel(T* __restrict__ recs, int B, int M, const int* __restric
     }
     if constexpr (NR > 1) {
         if (role != 0) {
-            double* part = part_mem + ((role - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < PixAcc::NVAL; ++i) part[i * 64] = acc.at(i);
-            part[PixAcc::NVAL * 64] = nfold;
+            MEAS_ROLES_PUT(part_mem, role, lane, acc, nfold)
             meas_barrier();
             return;
         }
         meas_barrier();
-#pragma unroll
-        for (int r = 1; r < NR; ++r) {
-            const double* part = part_mem + ((r - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < PixAcc::NVAL; ++i) acc.at(i) += part[i * 64];
-            nfold += part[PixAcc::NVAL * 64];
-        }
+        MEAS_ROLES_ADD(NR, part_mem, lane, acc, nfold)
     }
     if (!live || nfold == 0.0) {
         if (b < B) { applied[b] = 0; if constexpr (NIS) nis_none(nout, b); }
         return;
     }
     acc.expand_const(mc.NI);
-    if constexpr (has_lik<NO...>()) {
-        applied[b] = lik_tail<T, N>(nout, noise_in(no...), lik_out<T>(no...), NOISE_RPOS, b, rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane) ? 1 : 0;
-        return;
-    }
-    if constexpr (NIS) { applied[b] = nis_tail<T, N>(nout, b, rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane) ? 1 : 0; return; }
-    meas_update_tail<T, N>(rs, lane, acc, Rd, 1.0 / rpos, new_prev, gpark_mem + lane);
-    applied[b] = 1;
+    MEAS_APPLY_TAIL(NOISE_RPOS, Rd, 1.0 / rpos, new_prev)
 }
 
 // =================================================================================
@@ -1895,6 +1906,7 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
 {
     constexpr bool TRAJ = sizeof...(TJ) > 0;
     static_assert(!TRAJ || WINDOW, "trajectory rows are written by the window form");
+    static_assert(!(KIND == MEAS_PIXELS && CAM == 1) || NZ, "the left-only kernel folds in the camera frame: square port");
     using L = Lay<N>;
     using RC = Rec<T, N>;
     constexpr int EPC = RC::EPC, CN = RC::CH_NOM;
@@ -1913,61 +1925,15 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
     const bool stereo = (KIND == MEAS_PIXELS && CAM != 0) ? CAM == 2 : right != nullptr;
     const bool c3d = KIND == MEAS_CORNERS && geometry == VIS_CORNERS3D;
     const int lw = c3d ? 12 : 8;
-    struct Meas { int id; T l[KIND == MEAS_CORNERS ? 12 : 8], r[(KIND == MEAS_PIXELS && CAM == 1) ? 1 : 8]; };
-    // the id and the image coordinates of marker slot i (16-byte loads; the layouts of correct_pixels2 / correct_corners2_kernel)
+    using Meas = std::conditional_t<KIND == MEAS_PIXELS, PixMeas<T, CAM>, CornerMeas<T>>;
+    // the id and the image coordinates of marker slot i of frame f
     auto fetch = [&](int i, Meas& mm) __attribute__((always_inline)) {
         const size_t o = (fo + (size_t)bc) * M + i;
-        constexpr int EP = 16 / (int)sizeof(T);
-        mm.id = ids[o];
-        const u32x4* pl = reinterpret_cast<const u32x4*>(left + o * lw);
-        const u32x4* pr = reinterpret_cast<const u32x4*>(((KIND == MEAS_CORNERS ? c3d : !stereo) ? left : right) + o * 8);
-        if constexpr (KIND == MEAS_PIXELS) {
-#pragma unroll
-            for (int c = 0; c < 8 / EP; ++c) {
-                const u32x4 vl = pl[c];
-                const T* el = reinterpret_cast<const T*>(&vl);
-#pragma unroll
-                for (int k = 0; k < EP; ++k) mm.l[c * EP + k] = el[k];
-                if constexpr (CAM != 1) {
-                    const u32x4 vr = pr[c];
-                    const T* er = reinterpret_cast<const T*>(&vr);
-#pragma unroll
-                    for (int k = 0; k < EP; ++k) mm.r[c * EP + k] = er[k];
-                }
-            }
-        } else {
-#pragma unroll
-            for (int c = 0; c < 12 / EP; ++c) {
-                const u32x4 vl = pl[(c < 8 / EP || c3d) ? c : 0];
-                const T* el = reinterpret_cast<const T*>(&vl);
-#pragma unroll
-                for (int k = 0; k < EP; ++k) mm.l[c * EP + k] = el[k];
-            }
-#pragma unroll
-            for (int c = 0; c < 8 / EP; ++c) {
-                const u32x4 vr = pr[c];
-                const T* er = reinterpret_cast<const T*>(&vr);
-#pragma unroll
-                for (int k = 0; k < EP; ++k) mm.r[c * EP + k] = er[k];
-            }
-        }
+        if constexpr (KIND == MEAS_PIXELS) { MEAS_FETCH_PIXELS(T, CAM, mm, ids, left, lw, !stereo ? left : right, o) }
+        else { MEAS_FETCH_CORNERS(T, mm, ids, left, lw, c3d ? left : right, c3d, o) }
     };
-    // the four corners of a measured marker in the left camera frame (MEAS_CORNERS)
-    auto corners = [&](const Meas& mm, double (&C)[4][3]) __attribute__((always_inline)) {
-        if (geometry == VIS_REFRACTIVE) { tri_corners_refractive<T, NZ>(vc, mm.l, mm.r, C); return; }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (geometry == VIS_CORNERS3D) {
-#pragma unroll
-                for (int i = 0; i < 3; ++i) C[k][i] = (double)mm.l[(3 * k + i) % (KIND == MEAS_CORNERS ? 12 : 8)];
-            } else {
-                T o3[3];
-                pinhole_corner(vct, mm.l[2 * k], mm.l[2 * k + 1], mm.r[2 * k], mm.r[2 * k + 1], o3);
-#pragma unroll
-                for (int i = 0; i < 3; ++i) C[k][i] = (double)o3[i];
-            }
-        }
-    };
+    // (MEAS_CORNERS)
+    auto corners = [&](const Meas& mm, double (&C)[4][3]) __attribute__((always_inline)) { MEAS_CORNERS_OF(T, NZ, geometry, vc, vct, mm, C) };
     T nom[L::NNOM], P[RC::NCOVP];
     Meas cur, nxt;
     T prev_raw = T(0);
@@ -1975,25 +1941,12 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
     {
         {
             // the marker map -> LDS, the record behind it (lanes past B load their existing tile too: no branch in front of the loads)
-            constexpr int NI = (int)sizeof(short) * (FBUS_MAX_MARKER_ID + 1) / 16, NM = (int)sizeof(double) * FBUS_MAX_MARKERS * MKC_STRIDE / 16;
-            constexpr int PI = (NI + NT - 1) / NT, PM = (NM + NT - 1) / NT;
-            const u32x4* si = reinterpret_cast<const u32x4*>(id2slot);
-            const u32x4* sm = reinterpret_cast<const u32x4*>(mc.mkc);
-            u32x4* di = reinterpret_cast<u32x4*>(tbl.id2slot);
-            u32x4* dm = reinterpret_cast<u32x4*>(tbl.mkc);
-            u32x4 vi[PI], vm[PM];
-#pragma unroll
-            for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; vi[q] = si[i < NI ? i : 0]; }
-#pragma unroll
-            for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; vm[q] = sm[i < NM ? i : 0]; }
+            MEAS_MAP_LOAD(NT, id2slot, mc.mkc, tbl)
             order_fence();
             load_chunks<T, N, 0, CN, AUX_NT>(rs, lane, nom);
             load_chunks<T, N, CN, RC::NCH, AUX_NT>(rs, lane, P);
             order_fence();
-#pragma unroll
-            for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; if (i < NI) di[i] = vi[q]; }
-#pragma unroll
-            for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; if (i < NM) dm[i] = vm[q]; }
+            MEAS_MAP_STORE(NT)
             order_fence();
         }
     }
@@ -2038,12 +1991,7 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     double pd[3], Rd[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) pd[i] = (double)nom[L::OFF_P3 + i];
-#pragma unroll
-    for (int i = 0; i < 9; ++i) Rd[i] = (double)nom[L::OFF_R + i];
-    double pil[3];
-    filter_pil(Rd, mc.P_IL, pil);
+    MEAS_POSE_OF(L, nom, mc, pd, Rd, pil)
     PixAcc acc;
     acc.clear();
     double nfold = 0.0;
@@ -2053,63 +2001,15 @@ frame_meas_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* _
 #pragma unroll 1
         for (int i = 0; i < last; ++i) {
             fetch(i + 1 < M ? i + 1 : M - 1, nxt);
-            const bool ok = cur.id >= 0 && cur.id <= FBUS_MAX_MARKER_ID;
-            const int slot = ok ? (int)tbl.id2slot[ok ? cur.id : 0] : -1;
-            {
-                const double wgt = slot >= 0 ? 1.0 : 0.0;            // (every slot is folded: see pixel_fold_marker)
-                const int sl = slot >= 0 ? slot : 0;
-                double mk[9];
-#pragma unroll
-                for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[sl * MKC_STRIDE + q];
-                constexpr int NRR = sizeof(cur.r) / sizeof(T);          // (a slot without a marker of the map: zeros for its image points)
-                T yl_[8], yr_[NRR];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) yl_[k] = slot >= 0 ? cur.l[k] : T(0);
-#pragma unroll
-                for (int k = 0; k < NRR; ++k) yr_[k] = slot >= 0 ? cur.r[k] : T(0);
-                if constexpr (CAM == 1) pixel_fold_marker<1, T, NZ, 4, 0, true>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-                else if constexpr (CAM == 2) pixel_fold_marker_stereo_halves<T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-                else if (stereo) pixel_fold_marker_stereo_halves<T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-                else pixel_fold_marker<1, T, NZ>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-                nfold += wgt;
-            }
+            MEAS_FOLD_PIXEL_SLOT(T, NZ, CAM, false, acc, nfold, tbl, cur, stereo, pd, Rd, pil, mc, size)
             cur = nxt;
         }
     } else {
         auto fold_marker = [&](const Meas& mm) __attribute__((always_inline)) {
-            const bool ok = mm.id >= 0 && mm.id <= FBUS_MAX_MARKER_ID;
-            const int slot = ok ? (int)tbl.id2slot[ok ? mm.id : 0] : -1;
-            if (slot < 0) return false;
-            double mk[9], C[4][3];
-#pragma unroll
-            for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[slot * MKC_STRIDE + q];
-            corners(mm, C);
-            corner_fold_marker(acc, pd, Rd, pil, mc, mk, C, size);
-            return true;
+            MEAS_FOLD_CORNER_SLOT(false, acc, tbl, mm, corners, pd, Rd, pil, mc, size)
         };
         if (mode == MODE_NEAREST) {
-            if (live) {
-                const int prev_id = (int)prev_raw;
-                int min_i = -1, prev_i = -1;
-                double min_d = 10.0, prev_d = 0.0;
-#pragma unroll 1
-                for (int i = 0; i < M; ++i) {
-                    fetch(i + 1 < M ? i + 1 : M - 1, nxt);
-                    if (cur.id >= 0) {
-                        double C[4][3];
-                        corners(cur, C);
-                        const double dist = sqrt(C[0][0] * C[0][0] + C[0][1] * C[0][1] + C[0][2] * C[0][2]);
-                        if (dist < min_d) { min_d = dist; min_i = i; }
-                        if (DIALECT == DIALECT_CPP && cur.id == prev_id) { prev_d = dist; prev_i = i; }
-                    }
-                    cur = nxt;
-                }
-                if (min_i >= 0) {
-                    if (DIALECT == DIALECT_CPP && prev_i >= 0 && fabs(prev_d - min_d) < switch_thres && prev_d != 0.0) min_i = prev_i;
-                    fetch(min_i, cur);
-                    if (fold_marker(cur)) { nfold = 1.0; if (DIALECT == DIALECT_CPP) new_prev = cur.id; }
-                }
-            }
+            if (live) MEAS_FOLD_NEAREST_CORNER(DIALECT == DIALECT_CPP, fetch, corners, fold_marker, cur, nxt, M, prev_raw, switch_thres, nfold, new_prev)
         } else {
             const int last = live ? M : 0;
 #pragma unroll 1

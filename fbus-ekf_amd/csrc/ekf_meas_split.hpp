@@ -31,7 +31,9 @@
 
 namespace {
 
-// (late_start, chunk_sel, load_cov_chunks, direct_update_part: ekf_meas.hpp -- the fp64 tail there runs the same two parts in one wave)
+// (late_start, chunk_sel, load_cov_chunks, direct_update_part: ekf_meas.hpp -- the fp64 tail there runs the same two parts in one wave;
+// the marker map's way to LDS, the fetch of a slot, the pose in double, the body of the fold loop and the roles' sums are the MEAS_* pieces
+// of ekf_meas.hpp, the ones correct_pixels2_kernel is made of)
 
 // LDS image of the 63 coefficients + the verdict (64 values of T per lane)
 constexpr int SPLIT_NCOEF = 64;
@@ -66,46 +68,22 @@ correct_pixels_split_kernel(T* __restrict__ recs, int B, int M, const int* __res
     __shared__ double xch_mem[(PART_BYTES > COEF_BYTES ? PART_BYTES : COEF_BYTES) / 8];
     double* part_mem = xch_mem;
     T* coef_mem = reinterpret_cast<T*>(xch_mem);
-    struct Meas { int id; T l[8], r[8]; };
+    using Meas = PixMeas<T, 0>;
     const bool stereo = right != nullptr;
     auto fetch = [&](int i, Meas& mm) __attribute__((always_inline)) {
         const size_t o = (size_t)bc * M + i;
-        constexpr int EP = 16 / (int)sizeof(T);
-        mm.id = ids[o];
-        const u32x4* pl = reinterpret_cast<const u32x4*>(left + o * 8);
-        const u32x4* pr = reinterpret_cast<const u32x4*>((stereo ? right : left) + o * 8);
-#pragma unroll
-        for (int c = 0; c < 8 / EP; ++c) {
-            const u32x4 vl = pl[c], vr = pr[c];
-            const T* el = reinterpret_cast<const T*>(&vl);
-            const T* er = reinterpret_cast<const T*>(&vr);
-#pragma unroll
-            for (int k = 0; k < EP; ++k) { mm.l[c * EP + k] = el[k]; mm.r[c * EP + k] = er[k]; }
-        }
+        MEAS_FETCH_PIXELS(T, 0, mm, ids, left, 8, stereo ? right : left, o)
     };
     Meas cur, nxt;
     T pqr[L::NPQR];
     {
-        constexpr int NI = (int)sizeof(short) * (FBUS_MAX_MARKER_ID + 1) / 16, NM = (int)sizeof(double) * FBUS_MAX_MARKERS * MKC_STRIDE / 16;
-        constexpr int PI = (NI + NT - 1) / NT, PM = (NM + NT - 1) / NT;
-        const u32x4* si = reinterpret_cast<const u32x4*>(id2slot);
-        const u32x4* sm = reinterpret_cast<const u32x4*>(mc.mkc);
-        u32x4* di = reinterpret_cast<u32x4*>(tbl.id2slot);
-        u32x4* dm = reinterpret_cast<u32x4*>(tbl.mkc);
-        u32x4 vi[PI], vm[PM];
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; vi[q] = si[i < NI ? i : 0]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; vm[q] = sm[i < NM ? i : 0]; }
+        MEAS_MAP_LOAD(NT, id2slot, mc.mkc, tbl)
         order_fence();
         if (M > 0) fetch((int)role < M ? (int)role : M - 1, cur);
         order_fence();
         load_chunks<T, N, 0, RC::CH_PQR>(rs, lane, pqr);
         order_fence();
-#pragma unroll
-        for (int q = 0; q < PI; ++q) { const int i = threadIdx.x + q * NT; if (i < NI) di[i] = vi[q]; }
-#pragma unroll
-        for (int q = 0; q < PM; ++q) { const int i = threadIdx.x + q * NT; if (i < NM) dm[i] = vm[q]; }
+        MEAS_MAP_STORE(NT)
         order_fence();
     }
     meas_barrier();
@@ -114,55 +92,25 @@ correct_pixels_split_kernel(T* __restrict__ recs, int B, int M, const int* __res
     double nfold = 0.0;
     {
         double pd[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) pd[i] = (double)pqr[L::OFF_P3 + i];
-#pragma unroll
-        for (int i = 0; i < 9; ++i) Rd[i] = (double)pqr[L::OFF_R + i];
-        double pil[3];
-        filter_pil(Rd, mc.P_IL, pil);
+        MEAS_POSE_OF(L, pqr, mc, pd, Rd, pil)
         acc.clear();
         const int last = live ? M : 0;
 #pragma unroll 1
         for (int i = (int)role; i < last; i += NR) {
             fetch(i + NR < M ? i + NR : M - 1, nxt);
-            const bool ok = cur.id >= 0 && cur.id <= FBUS_MAX_MARKER_ID;
-            const int slot = ok ? (int)tbl.id2slot[ok ? cur.id : 0] : -1;
-            {
-                const double wgt = slot >= 0 ? 1.0 : 0.0;            // (every slot is folded: see pixel_fold_marker)
-                const int sl = slot >= 0 ? slot : 0;
-                double mk[9];
-#pragma unroll
-                for (int q = 0; q < 9; ++q) mk[q] = tbl.mkc[sl * MKC_STRIDE + q];
-                T yl_[8], yr_[8];                                     // (a slot without a marker of the map: zeros for its image points)
-#pragma unroll
-                for (int k = 0; k < 8; ++k) { yl_[k] = slot >= 0 ? cur.l[k] : T(0); yr_[k] = slot >= 0 ? cur.r[k] : T(0); }
-                if (stereo) pixel_fold_marker_stereo_halves<T, true>(acc, pd, Rd, pil, mc, mk, yl_, yr_, size, wgt);
-                else pixel_fold_marker<1, T, true>(acc, pd, Rd, pil, mc, mk, yl_, yl_, size, wgt);
-                nfold += wgt;
-            }
+            MEAS_FOLD_PIXEL_SLOT(T, true, 0, false, acc, nfold, tbl, cur, stereo, pd, Rd, pil, mc, size)
             cur = nxt;
         }
     }
     order_fence();
-    if (role != 0) {
-        double* part = part_mem + ((role - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-        for (int i = 0; i < PixAcc::NVAL; ++i) part[i * 64] = acc.at(i);
-        part[PixAcc::NVAL * 64] = nfold;
-    }
+    if (role != 0) MEAS_ROLES_PUT(part_mem, role, lane, acc, nfold)
     if (role == 0) {
         // ---------------- SOLVER: the chunks of P(J, J), requested in front of the exchange
         T P[RC::NCOVP];
         load_cov_chunks<T, N, 0, C_E, SEL_JJ>(rs, lane, P);
         order_fence();
         meas_barrier();                                                // (1) the other roles' sums are in LDS
-#pragma unroll
-        for (int r = 1; r < NR; ++r) {
-            const double* part = part_mem + ((r - 1) * (PixAcc::NVAL + 1)) * 64 + lane;
-#pragma unroll
-            for (int i = 0; i < PixAcc::NVAL; ++i) acc.at(i) += part[i * 64];
-            nfold += part[PixAcc::NVAL * 64];
-        }
+        MEAS_ROLES_ADD(NR, part_mem, lane, acc, nfold)
         const bool apply = live && nfold != 0.0;
         RegCoef<T> cf;
         {
@@ -207,6 +155,7 @@ correct_pixels_split_kernel(T* __restrict__ recs, int B, int M, const int* __res
         // Vector memory returns in order: once at most the LATE chunk loads (requested behind them, and stored by nobody else) are
         // outstanding, the x_c loads have been served -- the late chunks keep flying across the barrier (a full vmcnt(0) here cost
         // 1.6-2 us at config 3's size: 18.6 / 21.4 us left / stereo, against 15.9-16.1 / 18.2-18.7 with this count; tools/run_configs.py).
+        static_assert(RC::NCH - (CN + C_E) <= 63, "the late chunks in flight must fit the vmcnt field of s_waitcnt");
         if constexpr (HAS_LATE) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(RC::NCH - (CN + C_E)) : "memory");
         meas_barrier();
         if (b < B) applied[b] = apply ? 1 : 0;
