@@ -22,10 +22,11 @@ __device__ __forceinline__ unsigned my_lane() { return threadIdx.x & 63u; }
 // Stagger of the four SIMDs of a CU (round 5).  A launch of one wave per SIMD runs every wave through the same phases at the same time:
 // all four waves of a CU request their records together (and store them together at the end), sharing the CU's one path to memory
 // (~12.8 B/clk per CU: 4 x 51 KB take ~6.7 us, one wave alone ~1.7 us) while its VALUs idle; then all four compute while that path idles.
-// In the VALU-bound resident kernels (fused frames, the pixel / corner updates) a wave on SIMD k therefore sleeps k x FBUS_X_SIMD_STAGGER
+// In the VALU-bound resident kernels (fused frames, the pixel / corner updates) a wave on SIMD k therefore sleeps k x FBUS_X_STAGGER_FRAME / _MEAS
 // x 64 clocks before it asks for its record: the four load (and store) phases of a CU fall one behind the other, under the other SIMDs'
 // arithmetic.  (Round 2 staggered alternate WORKGROUPS of the memory-bound correct and found nothing: neighbouring workgroups sit on
-// different CUs, the four waves of one CU stayed in phase -- and a memory-bound kernel has no arithmetic to hide a load under.)
+// different CUs, the four waves of one CU stayed in phase -- and a memory-bound kernel has no arithmetic to hide a load under:
+// EXPERIMENTS_r1-r3.md, the (r2) table; that sleep block is no longer in correct_kernel.)
 // HW_ID (hwreg 4): SIMD_ID = bits 5:4.
 // Measured (65 536 filters, same box, profiles/r05_stagger.txt; units of 64 clocks per SIMD id, fused / per-call):
 //   0 / 0      fused pose frame 1.446e10 steps/s, fused pixel frame (M = 4) 9.36e9, correct_pixels M = 4 31.8 us, stereo 41.4 us
@@ -72,7 +73,8 @@ constexpr int AUX_DEFAULT = 0, AUX_NT = 2, AUX_SC1 = 16;
 // predict launch takes 13.8 us instead of 11.8 us (tools/exp_predict_timeline.hip).
 template <typename T>
 __device__ __forceinline__ T ld_once(const T* p) { return __builtin_nontemporal_load(p); }
-// experiment knobs (tools/ab_bench.sh builds variants with -D...)
+// experiment knobs: values, one #ifndef each (a variant library is built with FBUS_OUT + FBUS_EXTRA_FLAGS=-D..., build.py; tools/ab_bench.sh
+// alternates two libraries)
 #ifndef FBUS_X_CORRECT_ST
 // record stores of the per-call correct: sc1 = write-through.  The lines reach the Infinity Cache at once instead of sitting
 // dirty in the XCD's L2 until something evicts them, and the predict that follows streams them with the same non-temporal
@@ -80,15 +82,6 @@ __device__ __forceinline__ T ld_once(const T* p) { return __builtin_nontemporal_
 // +0.6 % at 131 072 / 262 144 (round 1's answer to the same problem, default-policy loads in the first predict behind a
 // correct, is no longer used behind correct; sc1 + nt stores lose: profiles/logs/r02_sc1.log)
 #define FBUS_X_CORRECT_ST AUX_SC1
-#endif
-#ifndef FBUS_X_SPLIT
-#define FBUS_X_SPLIT RC::CH_VAR_END
-#endif
-#ifndef FBUS_X_MEAS_NT
-#define FBUS_X_MEAS_NT 0
-#endif
-#ifndef FBUS_X_STREAM_ST
-#define FBUS_X_STREAM_ST 1      // stacked correct / fused frame: the last rank-1 pass stores each chunk when its rows are final
 #endif
 #ifndef FBUS_X_FRAME_ST
 #define FBUS_X_FRAME_ST AUX_DEFAULT    // record stores of the fused frame / frame window kernels
@@ -120,23 +113,6 @@ __device__ __forceinline__ T ld_once(const T* p) { return __builtin_nontemporal_
 // same-box A/B (5.025e9-5.035e9 -> 5.043e9-5.064e9), less than boxes differ from each other; nt keeps correct at 0.84 of peak
 #define FBUS_X_CORRECT_LD AUX_NT
 #endif
-#ifndef FBUS_X_CORRECT_STAGGER_BIT
-#define FBUS_X_CORRECT_STAGGER_BIT 3
-#endif
-#ifndef FBUS_X_CORRECT_STAGGER
-#define FBUS_X_CORRECT_STAGGER 0   // experiment: every other wave of an XCD sleeps this many x 3.9 us before it requests its record
-#endif
-#ifndef FBUS_X_FRAME_WAVES
-#define FBUS_X_FRAME_WAVES 1    // __launch_bounds__ waves per SIMD of the fused frame kernel (2 = at most 256 registers)
-#endif
-#ifndef FBUS_X_CORRECT_WAVES
-#define FBUS_X_CORRECT_WAVES 1
-#endif
-#ifndef FBUS_X_IMU_PREFETCH
-#define FBUS_X_IMU_PREFETCH 1   // predict_n / fused frame: the IMU sample of step k + 1 is requested in the middle of step k
-#endif
-template <typename T>
-__device__ __forceinline__ T ld_meas(const T* p) { return FBUS_X_MEAS_NT ? __builtin_nontemporal_load(p) : *p; }
 
 template <typename T, int N>
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t tile_rsrc(const T* recs, unsigned tile)
@@ -178,12 +154,9 @@ __device__ __forceinline__ void store_chunks(__amdgpu_buffer_rsrc_t rs, unsigned
         // 16 instead of the stored value.  LLVM's hazard recognizer pads this case only when soffset is NOT a register
         // (GCNHazardRecognizer::createsVALUHazard) -- with the 4 KiB group offset in an SGPR, as the loads have it, it
         // emits nothing.  Stores therefore carry the group offset in the VGPR offset and a constant-zero soffset: the
-        // recognizer then inserts the wait state itself, exactly where a data register is overwritten too early.
-#ifdef FBUS_X_STORE_SGPR_SOFFSET      // experiment only: UNSAFE (see above)
-        __builtin_amdgcn_raw_buffer_store_b128(v, rs, off + (c & 3) * 1024u, (c >> 2) * 4096, AUX);
-#else
+        // recognizer then inserts the wait state itself, exactly where a data register is overwritten too early.  The form with the
+        // group offset in soffset, as load_chunks has it, must NOT be written for a store.
         __builtin_amdgcn_raw_buffer_store_b128(v, rs, off + (c >> 2) * 4096u + (c & 3) * 1024u, 0, AUX);
-#endif
     }
 }
 
@@ -319,9 +292,9 @@ struct MarkerGroup {
             const int i = (i0 + g < last) ? i0 + g : last - 1;
             id[g] = my_ids[i];
 #pragma unroll
-            for (int k = 0; k < 3; ++k) yp[g][k] = ld_meas(my_pos + 3 * i + k);
+            for (int k = 0; k < 3; ++k) yp[g][k] = my_pos[3 * i + k];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) yq[g][k] = ld_meas(my_quat + 4 * i + k);
+            for (int k = 0; k < 4; ++k) yq[g][k] = my_quat[4 * i + k];
         }
     }
     __device__ __forceinline__ void resolve(const MarkerLDS<T>& t)
@@ -418,7 +391,6 @@ template <typename T, int N, int DIALECT, typename MID = NoMidHook, typename PAR
 __device__ __forceinline__ void predict_steps(T* nom, T* P, int K, const T* accel, const T* gyro, const T* dt, int dt_stride,
                                               int B, int b, QD qd, const MID& mid_last = MID(), const PARK& park = PARK())
 {
-#if FBUS_X_IMU_PREFETCH
     // The sample of step k + 1 is requested as soon as step k's kinematics have consumed sample k, i.e. ~700 VALU
     // instructions (the three covariance stages) before it is needed.  Requesting it at the top of the iteration into a
     // second buffer does not work: the compiler's s_waitcnt placement then drains vmcnt to 0 right behind the new
@@ -436,12 +408,8 @@ __device__ __forceinline__ void predict_steps(T* nom, T* P, int K, const T* acce
         predict_nominal<T, N, DIALECT, PK>(nom, cur.a, cur.w, cur.h, c);
         if constexpr (PARKED) { park.nom_out(nom); }
         __builtin_amdgcn_sched_barrier(0);
-#ifdef FBUS_X_IMU_ONCE      // experiment: every step on the first sample -- no memory access inside the loop (what does the sample's latency cost?)
-        if (k + 1 >= K) mid_last();
-#else
         if (k + 1 < K) cur.load(accel, gyro, dt, dt_stride, k + 1, B, b);
         else mid_last();                           // last step: the caller's loads for what follows the predicts
-#endif
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (PARKED) { park.rows_in(P); }
         cov_stage_p<T, N, PK>(P, c);
@@ -451,17 +419,111 @@ __device__ __forceinline__ void predict_steps(T* nom, T* P, int K, const T* acce
         if constexpr (PARKED) { __builtin_amdgcn_sched_barrier(0); }
     }
     if constexpr (PARKED) { park.rows_in(P); park.nom_in(nom); }
-#else
-    for (int k = 0; k < K; ++k) {
-        const size_t o = ((size_t)k * B + b) * 3;
-        const T a[3] = { ld_once(accel + o), ld_once(accel + o + 1), ld_once(accel + o + 2) };
-        const T w[3] = { ld_once(gyro + o), ld_once(gyro + o + 1), ld_once(gyro + o + 2) };
-        const T h = dt_stride ? ld_once(dt + (size_t)k * B + b) : dt[k];
-        predict_step<T, N, DIALECT, PK>(nom, P, a, w, h, qd);
-    }
-    mid_last();
-#endif
 }
+
+// ---------------------------------------------------------------------------------
+// what the pose-form kernels share
+// ---------------------------------------------------------------------------------
+// One definition of what correct_kernel, frame_kernel, frames_kernel, frame2_kernel and frames_team_kernel (ekf_team.hpp) wrote out each.  A piece
+// is a function where the function form leaves every kernel's instruction stream as it was (meas_row), and a function-like macro POSE_* where it
+// does not: these kernels sit at 256 - 512 registers, and what reaches them through the inliner is allocated differently (EXPERIMENTS -1.24;
+// the measurement kernels' MEAS_* macros, ekf_meas.hpp, for the same reason).
+// The measurement arrays are [rows][M] slots (ids), [rows][M][3] (pos), [rows][M][4] (quat); row = the filter, or frame * B + filter in a
+// window: a filter's M slots.
+template <typename T> struct MeasRow { const int* ids; const T* pos; const T* quat; };
+template <typename T>
+__device__ __forceinline__ MeasRow<T> meas_row(const int* ids, const T* pos, const T* quat, size_t row, int M)
+{
+    return { ids + row * M, pos + row * M * 3, quat + row * M * 4 };
+}
+
+// The prologue of the kernels that hold the record resident (frame_kernel, frames_kernel, frame2_kernel<float>): the pieces of the marker map
+// to registers first, the whole record behind them (read once: nt), the LDS copy of the map after both are on their way.  Lanes past B
+// load their existing tile too: no branch in front of the loads.
+#define POSE_LOAD_RESIDENT(T, N, DC, RS, NOM, P, TBL)                                                                                                 \
+    {                                                                                                                                                 \
+        MarkerTableRegs<T> treg;                                                                                                                      \
+        treg.load(DC);                                                                                                                                \
+        order_fence();                                                                                                                                \
+        load_chunks<T, N, 0, Rec<T, N>::CH_NOM, AUX_NT>(RS, my_lane(), NOM);                                                                          \
+        load_chunks<T, N, Rec<T, N>::CH_NOM, Rec<T, N>::NCH, AUX_NT>(RS, my_lane(), P);                                                               \
+        order_fence();                                                                                                                                \
+        treg.to_lds(TBL);                                                                                                                             \
+        order_fence();                                                                                                                                \
+    }
+
+// MODE_NEAREST in the resident kernels (MeasureUpdate.m:51-60 ; filter.cpp:639-664): the nearest visible marker of the filter's M slots by
+// its INDEX -- the measurement is fetched again by the fold loop, the record is resident and nothing queues behind a stream (correct_kernel
+// keeps the candidates' values instead).  C++ dialect: the previous marker (PREV, a record value) keeps its place while it is within
+// switch_thres of the nearest, and the marker taken is the next previous one.  -> [first, last) = the one slot to fold, or empty when the
+// marker is not in the map.  The lookup is the caller's: frame_kernel reads dc.id2slot (global memory, no id >= 0 test: an id that reaches
+// it has passed the scan's), frames_kernel and frames_team_kernel read tbl.id2slot (LDS) with the test -- kept apart on purpose, DESIGN 4.
+// SLOT_OF_ID: an expression in `id`.
+#define POSE_NEAREST_BY_INDEX(T, DIALECT, IDS, POS, M, PREV, SWITCH_THRES, SLOT_OF_ID, FIRST, LAST, NEW_PREV)                                         \
+    {                                                                                                                                                 \
+        const int prev_id = (DIALECT == DIALECT_CPP) ? (int)PREV : 0;                                                                                 \
+        int min_i = -1, prev_i = -1;                                                                                                                  \
+        T min_d = T(10), prev_d = T(0);                                                                                                               \
+        for (int i = 0; i < M; ++i) {                                                                                                                 \
+            const int id = IDS[i];                                                                                                                    \
+            if (id < 0) continue;                                                                                                                     \
+            const T x = POS[3 * i], y = POS[3 * i + 1], z = POS[3 * i + 2];                                                                           \
+            const T dist = fb_sqrt(x * x + y * y + z * z);                                                                                            \
+            if (dist < min_d) { min_d = dist; min_i = i; }                                                                                            \
+            if (DIALECT == DIALECT_CPP && id == prev_id) { prev_d = dist; prev_i = i; }                                                               \
+        }                                                                                                                                             \
+        if (min_i >= 0 && DIALECT == DIALECT_CPP && fb_abs(prev_d - min_d) < SWITCH_THRES && prev_d != T(0))                                          \
+            min_i = prev_i;                                                                                                                           \
+        int slot = -1, id = -1;                                                                                                                       \
+        if (min_i >= 0) {                                                                                                                             \
+            id = IDS[min_i];                                                                                                                          \
+            slot = SLOT_OF_ID;                                                                                                                        \
+        }                                                                                                                                             \
+        if (slot < 0) { FIRST = LAST = 0; }                                                                                                           \
+        else {                                                                                                                                        \
+            if (DIALECT == DIALECT_CPP) NEW_PREV = id;                                                                                                \
+            FIRST = min_i; LAST = min_i + 1;                                                                                                          \
+        }                                                                                                                                             \
+    }
+
+// The fold loop of the resident kernels: the measurements of slots [first, last) of a filter in groups of FBUS_MARKER_GROUP -- one round of
+// loads (fetch), the map lookups from LDS (resolve) -- and every slot whose marker is in the map handed to the caller's statement
+// (PoseFold::add, or marker_update for the Joseph form).  (correct_kernel's loop is its own: the first group comes from its prologue, and
+// the NIS kernels fold twice.)
+// ...: the statement for a slot, in terms of mg and g.  USED: the caller's count of slots used.
+#define POSE_FOLD_GROUPS(T, IDS, POS, QUAT, FIRST, LAST, TBL, USED, ...)                                                                              \
+    for (int i0 = FIRST; i0 < LAST; i0 += FBUS_MARKER_GROUP) {                                                                                        \
+        MarkerGroup<T, FBUS_MARKER_GROUP> mg;                                                                                                         \
+        mg.fetch(IDS, POS, QUAT, i0, LAST);                                                                                                           \
+        mg.resolve(TBL);                                                                                                                              \
+        _Pragma("unroll") for (int g = 0; g < FBUS_MARKER_GROUP; ++g) {                                                                               \
+            if (mg.slot[g] < 0) continue;                                                                                                             \
+            __VA_ARGS__;                                                                                                                              \
+            ++USED;                                                                                                                                   \
+        }                                                                                                                                             \
+    }
+
+// the error state DX of an update, declared and cleared
+#define POSE_DX_ZERO(T, N, DX)                                                                                                                        \
+    T DX[N];                                                                                                                                          \
+    _Pragma("unroll") for (int i = 0; i < N; ++i) DX[i] = T(0);
+
+// correct_kernel, reference mode: the 7 rows of the chosen marker -- map constants MK (of its slot, from LDS), measurement Y = position,
+// quaternion -- folded at the nominal state NOMX into ACC.  NOMX is the kernel's nom, or the opaque copy the NIS statistic folds from (NIS =
+// the PoseFold that keeps the statistic's sums).  The constants are fetched apart from the fold: the kernel asks for them in front of the
+// opaque copy, and its two folds of one marker share them.
+#define POSE_SLOT_MK(T, MK, TBL, SLOT)                                                                                                                \
+    T MK[MK_STRIDE];                                                                                                                                  \
+    _Pragma("unroll") for (int k = 0; k < 8; ++k) MK[k] = TBL.mk[(SLOT) * MK_STRIDE + k];
+#define POSE_FOLD_ONE_MARKER(T, N, NIS, ACC, FOLD, MK, NOMX, DC, Y)                                                                                   \
+    {                                                                                                                                                 \
+        MarkerCommon<T, N> mc;                                                                                                                        \
+        mc.build(NOMX, DC);                                                                                                                           \
+        FOLD.clear();                                                                                                                                 \
+        if constexpr (NIS) FOLD.clear_nis();                                                                                                          \
+        FOLD.add(NOMX, DC, mc, MK, Y, Y + 3);                                                                                                         \
+        FOLD.finish(ACC, NOMX, DC, mc);                                                                                                               \
+    }
 
 // ---------------------------------------------------------------------------------
 // kernels
@@ -500,14 +562,12 @@ constexpr int PARK_NOM_CHUNKS = 4;
 #ifndef FBUS_X_PARK_NOM_F64
 #define FBUS_X_PARK_NOM_F64 14
 #endif
-#ifndef FBUS_X_PREDICT_TWO
-#define FBUS_X_PREDICT_TWO 0
-#endif
 template <typename T> constexpr int park_nom_chunks() { return sizeof(T) == 8 ? FBUS_X_PARK_NOM_F64 : PARK_NOM_CHUNKS; }
+// (K = 1 in 256 registers, two waves per SIMD: helps between 1.5 and 2 rounds of waves only, EXPERIMENTS -1.8 -- not a bound of this kernel)
 // NZ = NoiseIn (fbus_ekf_set_noise; kernels_tu.hip family 14, every form the launcher picks): this lane's q_v q_theta q_ba q_bg in place of
 // the handle's, requested with the prologue (ahead of the record stream) and used where dc.qd is
 template <typename T, int N, int DIALECT, bool MULTI, int LD = AUX_NT, int ST = FBUS_X_PREDICT_ST, bool PARK = false, typename... NZ>
-__global__ void __launch_bounds__(BLOCK, (sizeof(T) == 4 && (PARK || (!MULTI && FBUS_X_PREDICT_TWO))) ? 2 : 1)
+__global__ void __launch_bounds__(BLOCK, (sizeof(T) == 4 && PARK) ? 2 : 1)
 predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, const T* __restrict__ gyro,
                const T* __restrict__ dt, int dt_stride, DevConst<T> dc, NZ... nz)
 {
@@ -593,8 +653,9 @@ predict_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, 
 // branch, behind the covariance stream.
 // NO = NisOut<T> (fbus_ekf_correct_nis*; kernels_tu.hip family 13, never the fp32 row-split form): the NIS and dof of the applied rows
 // (pose_nis, from the fold's Lam / b and P_JJ, in double) and the gate, decided in front of the first store of every route.
+// (the bound of one wave per SIMD is a literal: a second wave was tried and not kept, EXPERIMENTS 0.7 and I.1)
 template <typename T, int N, int DIALECT, int COV, bool JOINT, bool SPLIT = (sizeof(T) == 8), typename... NO>
-__global__ void __launch_bounds__(BLOCK, FBUS_X_CORRECT_WAVES)
+__global__ void __launch_bounds__(BLOCK, 1)
 correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, const T* __restrict__ pos,
                const T* __restrict__ quat, int mode, const unsigned char* __restrict__ skip,
                unsigned char* __restrict__ applied, DevConst<T> dc, NO... no)
@@ -620,30 +681,19 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     // NO = (NisOut<T>, NoiseIn) (fbus_ekf_set_noise; kernels_tu.hip family 16): this lane's r_pos / r_quat in place of the handle's, requested
     // in front of the record stream (written into the by-value constants: the instantiations without a table stay as they were)
     if constexpr (has_noise<NO...>()) noise_pose<T>(dc, b < B ? b : B - 1, no...);
-    const int* my_ids = ids + (size_t)bc * M;
-    const T* my_pos = pos + (size_t)bc * M * 3;
-    const T* my_quat = quat + (size_t)bc * M * 4;
+    const MeasRow<T> mr = meas_row(ids, pos, quat, (size_t)bc, M);
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
     T P[RC::NCOVP], nom[L::NNOM];
     __shared__ MarkerLDS<T> tbl;
     MarkerGroup<T, G> mg;
-    if (FBUS_X_CORRECT_STAGGER > 0 && ((blockIdx.x >> FBUS_X_CORRECT_STAGGER_BIT) & 1)) {
-#pragma unroll
-        for (int i = 0; i < FBUS_X_CORRECT_STAGGER / 4; ++i) __builtin_amdgcn_s_sleep(127);
-        if (FBUS_X_CORRECT_STAGGER % 4) __builtin_amdgcn_s_sleep(32 * (FBUS_X_CORRECT_STAGGER % 4) - 1);
-        __builtin_amdgcn_sched_barrier(0);
-    }
     // the stacked path asks for the predict-invariant covariance tail behind the fold: fewer registers are tied up
     // while the rows are built, and the first scalar update only needs it for its last rows
-    constexpr int C_SPLIT = JOINT ? FBUS_X_SPLIT : RC::NCH;
-#ifndef FBUS_X_NEAREST_INFO
-#define FBUS_X_NEAREST_INFO 1     // the reference mode (one marker, 7 rows) through the information form too: 6 passes, streamed stores
-#endif
+    constexpr int C_SPLIT = JOINT ? RC::CH_VAR_END : RC::NCH;
     // fp32 reference mode: the 7 rows of the chosen marker are folded like the rows of the stacked mode and applied as six
     // rank-1 passes whose last one streams the stores (instead of 7 row-by-row updates and a store phase behind them); the
     // same posterior -- the reference itself solves the 7 x 7 system at once (inv / LDLT), neither form is its operation order
-    constexpr bool NEAREST_INFO = !JOINT && FBUS_X_NEAREST_INFO && COV == COV_SIMPLE;
-    constexpr bool STREAM_ST = (JOINT || NEAREST_INFO) && FBUS_X_STREAM_ST;
+    constexpr bool NEAREST_INFO = !JOINT && COV == COV_SIMPLE;
+    constexpr bool STREAM_ST = JOINT || NEAREST_INFO;       // the last rank-1 pass stores each chunk when its rows are final (RowStore)
     // fp64 (LEAN): 171 covariance doubles are 342 of the 512 registers.  The six passes run in the row-split form
     // (joint_apply_early / joint_apply_late, ekf_device.hpp): factorise first, then bring in storage rows 0..8 only, run
     // the passes on them (the last one streams them out), then bring in rows 9..17 and give them their six rank-1
@@ -668,7 +718,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         treg.load(dc);
         order_fence();
         if (!JOINT && DIALECT == DIALECT_CPP) prev_raw = recs[elem_index<T, N>(bc, L::OFF_PREV)];
-        if (M > 0) mg.fetch(my_ids, my_pos, my_quat, 0, M, vec);
+        if (M > 0) mg.fetch(mr.ids, mr.pos, mr.quat, 0, M, vec);
         order_fence();
         // the whole nominal state up front (p, q, R for the rows; v, ba, bg, g only for the injection -- 12 registers
         // that save a dependent reload between the last update and the stores)
@@ -682,9 +732,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
     }
     const int last = live ? M : 0;
     if (last == 0) mg.n = 0;
-    T dx[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) dx[i] = T(0);
+    POSE_DX_ZERO(T, N, dx)
     int used = 0, new_prev = -1;
     auto lean_passes = [&](InfoFactors<T>& fac, bool go) {
         order_fence();
@@ -759,7 +807,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         // nothing -- so that the nominal loads it needs stay where they were issued; further groups in a loop
         fold_group();
         for (int i0 = G; i0 < last; i0 += G) {
-            mg.fetch(my_ids, my_pos, my_quat, i0, last, vec);
+            mg.fetch(mr.ids, mr.pos, mr.quat, i0, last, vec);
             fold_group();
         }
         fold.finish(acc, nom, dc, mc);
@@ -774,11 +822,8 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
             order_fence();
             load_chunks<T, N, C_SPLIT, RC::NCH, FBUS_X_CORRECT_LD>(rs, my_lane(), P + (C_SPLIT - RC::CH_NOM) * RC::EPC);
             if constexpr (NIS) { const bool rj = nis_gate(acc2, fold2, used, true); used = rj ? 0 : used; }
-            // the last of the six passes stores every covariance chunk as soon as its rows are final (FBUS_X_STREAM_ST)
-            if (used > 0) {
-                if constexpr (STREAM_ST) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
-                else joint_update<T, N, COV>(P, dx, acc);
-            }
+            // the last of the six passes stores every covariance chunk as soon as its rows are final
+            if (used > 0) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
         }
     } else {
         // nearest visible marker, start threshold 10   MeasureUpdate.m:51-60 ; filter.cpp:639-664.
@@ -814,7 +859,7 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
         };
         scan_group();
         for (int i0 = G; i0 < last; i0 += G) {
-            mg.fetch(my_ids, my_pos, my_quat, i0, last, vec);
+            mg.fetch(mr.ids, mr.pos, mr.quat, i0, last, vec);
             scan_group();
         }
         if (min_id >= 0 && DIALECT == DIALECT_CPP && pv_id >= 0 && fb_abs(prev_d - min_d) < dc.switch_thres && prev_d != T(0)) {
@@ -830,28 +875,17 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
             acc.clear();
             if (slot >= 0) {
                 if (DIALECT == DIALECT_CPP) new_prev = min_id;                       // filter.cpp:675
-                T mk[MK_STRIDE];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[slot * MK_STRIDE + k];
-                MarkerCommon<T, N> mc;
-                mc.build(nom, dc);
+                POSE_SLOT_MK(T, mk, tbl, slot)
                 PoseFold<T, N, DIALECT> fold;
-                fold.clear();
-                fold.add(nom, dc, mc, mk, min_y, min_y + 3);
-                fold.finish(acc, nom, dc, mc);
+                POSE_FOLD_ONE_MARKER(T, N, false, acc, fold, mk, nom, dc, min_y)
                 joint_factor<T>(acc, fac);
                 used = 1;
                 if constexpr (NIS) {                                                   // (the statistic's own fold, see opaque_nom)
                     T nomn[L::NNOM];
                     opaque_nom(nomn);
-                    MarkerCommon<T, N> mc2;
-                    mc2.build(nomn, dc);
                     InfoAcc<T> acc2;
                     PoseFold<T, N, DIALECT, true> fold2;
-                    fold2.clear();
-                    fold2.clear_nis();
-                    fold2.add(nomn, dc, mc2, mk, min_y, min_y + 3);
-                    fold2.finish(acc2, nomn, dc, mc2);
+                    POSE_FOLD_ONE_MARKER(T, N, true, acc2, fold2, mk, nomn, dc, min_y)
                     const bool rj = nis_gate(acc2, fold2, 1, false);
                     used = rj ? 0 : 1;
                     new_prev = rj ? -1 : new_prev;
@@ -864,38 +898,26 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
             bool rej = false;
             if constexpr (NIS) {
                 const int sl = slot >= 0 ? slot : 0;
-                T mk[MK_STRIDE];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[sl * MK_STRIDE + k];
+                POSE_SLOT_MK(T, mk, tbl, sl)
                 T nomn[L::NNOM];
                 opaque_nom(nomn);
-                MarkerCommon<T, N> mc;
-                mc.build(nomn, dc);
                 InfoAcc<T> acc;
                 PoseFold<T, N, DIALECT, true> fold;
-                fold.clear();
-                fold.clear_nis();
-                fold.add(nomn, dc, mc, mk, min_y, min_y + 3);
-                fold.finish(acc, nomn, dc, mc);
+                POSE_FOLD_ONE_MARKER(T, N, true, acc, fold, mk, nomn, dc, min_y)
                 rej = nis_gate(acc, fold, slot >= 0 ? 1 : 0, true);
                 nisv = slot >= 0 ? nisv : 0.0;
             }
             if (slot >= 0 && !rej) {
                 if (DIALECT == DIALECT_CPP) new_prev = min_id;                       // filter.cpp:675
-                T mk[MK_STRIDE];
-#pragma unroll
-                for (int k = 0; k < 8; ++k) mk[k] = tbl.mk[slot * MK_STRIDE + k];
-                MarkerCommon<T, N> mc;
-                mc.build(nom, dc);
+                POSE_SLOT_MK(T, mk, tbl, slot)
                 if constexpr (NEAREST_INFO) {
                     InfoAcc<T> acc;
                     PoseFold<T, N, DIALECT> fold;
-                    fold.clear();
-                    fold.add(nom, dc, mc, mk, min_y, min_y + 3);
-                    fold.finish(acc, nom, dc, mc);
-                    if constexpr (STREAM_ST) joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
-                    else joint_update<T, N, COV>(P, dx, acc);
-                } else {
+                    POSE_FOLD_ONE_MARKER(T, N, false, acc, fold, mk, nom, dc, min_y)
+                    joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_CORRECT_ST>{ rs, my_lane(), P });
+                } else {                                                                // the Joseph form: row by row
+                    MarkerCommon<T, N> mc;
+                    mc.build(nom, dc);
                     marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mk, min_y, min_y + 3);
                 }
                 used = 1;
@@ -926,8 +948,10 @@ correct_kernel(T* __restrict__ recs, int B, int M, const int* __restrict__ ids, 
 // registers in between (the reference's BatchImuProcessing + ObservationUpdate, filter.cpp:232-235).
 // Same device functions, same arithmetic as K predict launches + one correct launch; the record makes
 // one HBM round trip per frame instead of one per EKF step.
+// (the bound of one wave per SIMD is a literal: two, at most 256 registers, were tried and not kept, EXPERIMENTS 0.7; frame2_kernel is the
+// two-wave frame)
 template <typename T, int N, int DIALECT, int COV, bool JOINT>
-__global__ void __launch_bounds__(BLOCK, FBUS_X_FRAME_WAVES)
+__global__ void __launch_bounds__(BLOCK, 1)
 frame_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, const T* __restrict__ gyro,
              const T* __restrict__ dt, int dt_stride, int M, const int* __restrict__ ids, const T* __restrict__ pos,
              const T* __restrict__ quat, int mode, const unsigned char* __restrict__ skip,
@@ -940,54 +964,18 @@ frame_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, co
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
     T nom[L::NNOM], P[RC::NCOVP];
     simd_stagger<FBUS_X_STAGGER_FRAME>();
-    {
-        // map pieces first, the record behind them, the LDS copy after both are on their way (lanes past B load
-        // their existing tile too: no branch in front of the loads)
-        MarkerTableRegs<T> treg;
-        treg.load(dc);
-        order_fence();
-        load_chunks<T, N, 0, RC::CH_NOM, AUX_NT>(rs, my_lane(), nom);
-        load_chunks<T, N, RC::CH_NOM, RC::NCH, AUX_NT>(rs, my_lane(), P);
-        order_fence();
-        treg.to_lds(tbl);
-        order_fence();
-    }
+    POSE_LOAD_RESIDENT(T, N, dc, rs, nom, P, tbl)
     if (b >= B) return;
     int first = 0, last = (M > 0 && !(skip && skip[b])) ? M : 0;
     int new_prev = -1;
-    const int* my_ids = ids + (size_t)b * M;
-    const T* my_pos = pos + (size_t)b * M * 3;
-    const T* my_quat = quat + (size_t)b * M * 4;
+    const MeasRow<T> mr = meas_row(ids, pos, quat, (size_t)b, M);
     predict_steps<T, N, DIALECT>(nom, P, K, accel, gyro, dt, dt_stride, B, b, dc.qd);
 
-    if (last > 0 && mode == MODE_NEAREST) {
-        const int prev_id = (DIALECT == DIALECT_CPP) ? (int)P[L::OFF_PREV - L::OFF_COV] : 0;
-        int min_i = -1, prev_i = -1;
-        T min_d = T(10), prev_d = T(0);
-        for (int i = 0; i < M; ++i) {
-            const int id = my_ids[i];
-            if (id < 0) continue;
-            const T x = my_pos[3 * i], y = my_pos[3 * i + 1], z = my_pos[3 * i + 2];
-            const T dist = fb_sqrt(x * x + y * y + z * z);
-            if (dist < min_d) { min_d = dist; min_i = i; }
-            if (DIALECT == DIALECT_CPP && id == prev_id) { prev_d = dist; prev_i = i; }
-        }
-        if (min_i >= 0 && DIALECT == DIALECT_CPP && fb_abs(prev_d - min_d) < dc.switch_thres && prev_d != T(0))
-            min_i = prev_i;
-        int slot = -1, id = -1;
-        if (min_i >= 0) {
-            id = my_ids[min_i];
-            slot = (id <= FBUS_MAX_MARKER_ID) ? dc.id2slot[id] : -1;
-        }
-        if (slot < 0) { first = last = 0; }
-        else {
-            if (DIALECT == DIALECT_CPP) new_prev = id;
-            first = min_i; last = min_i + 1;
-        }
-    }
-    T dx[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) dx[i] = T(0);
+    if (last > 0 && mode == MODE_NEAREST)
+        POSE_NEAREST_BY_INDEX(T, DIALECT, mr.ids, mr.pos, M, P[L::OFF_PREV - L::OFF_COV], dc.switch_thres,
+                              (id <= FBUS_MAX_MARKER_ID) ? dc.id2slot[id] : -1,
+                              first, last, new_prev)
+    POSE_DX_ZERO(T, N, dx)
     int used = 0;
     InfoAcc<T> acc;
     PoseFold<T, N, DIALECT> fold;
@@ -996,25 +984,15 @@ frame_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, co
     if (joint) fold.clear();
     MarkerCommon<T, N> mc;
     mc.build(nom, dc);
-    for (int i0 = first; i0 < last; i0 += FBUS_MARKER_GROUP) {
-        MarkerGroup<T, FBUS_MARKER_GROUP> mg;
-        mg.fetch(my_ids, my_pos, my_quat, i0, last);
-        mg.resolve(tbl);
-#pragma unroll
-        for (int g = 0; g < FBUS_MARKER_GROUP; ++g) {
-            if (mg.slot[g] < 0) continue;
-            if constexpr (joint) fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-            else marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-            ++used;
-        }
-    }
-    constexpr bool STREAM_ST = joint && FBUS_X_STREAM_ST;
+    POSE_FOLD_GROUPS(T, mr.ids, mr.pos, mr.quat, first, last, tbl, used,
+                     if constexpr (joint) fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
+                     else marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]))
     bool streamed = false;
     if constexpr (joint) {
         if (used > 0) {
             fold.finish(acc, nom, dc, mc);
-            if constexpr (STREAM_ST) { joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_FRAME_ST>{ rs, my_lane(), P }); streamed = true; }
-            else joint_update<T, N, COV>(P, dx, acc);
+            joint_update<T, N, COV>(P, dx, acc, RowStore<T, N, FBUS_X_FRAME_ST>{ rs, my_lane(), P });
+            streamed = true;
         }
     }
     if (used > 0) {
@@ -1086,16 +1064,7 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
     __shared__ MarkerLDS<T> tbl;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
     T nom[L::NNOM], P[RC::NCOVP];
-    {
-        MarkerTableRegs<T> treg;
-        treg.load(dc);
-        order_fence();
-        load_chunks<T, N, 0, RC::CH_NOM, AUX_NT>(rs, my_lane(), nom);
-        load_chunks<T, N, RC::CH_NOM, RC::NCH, AUX_NT>(rs, my_lane(), P);
-        order_fence();
-        treg.to_lds(tbl);
-        order_fence();
-    }
+    POSE_LOAD_RESIDENT(T, N, dc, rs, nom, P, tbl)
     if (b >= B) return;
     if constexpr (has_noise<TJ...>()) { noise_q<T>(dc, b, traj...); noise_pose<T>(dc, b, traj...); }
     int k0 = 0, last_used = 0;
@@ -1110,37 +1079,12 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
         const size_t fo = (size_t)f * B + b;
         int first = 0, last = (M > 0 && !(skip && skip[fo])) ? M : 0;
         int new_prev = -1;
-        const int* my_ids = ids + fo * M;
-        const T* my_pos = pos + fo * M * 3;
-        const T* my_quat = quat + fo * M * 4;
-        if (last > 0 && mode == MODE_NEAREST) {
-            const int prev_id = (DIALECT == DIALECT_CPP) ? (int)P[L::OFF_PREV - L::OFF_COV] : 0;
-            int min_i = -1, prev_i = -1;
-            T min_d = T(10), prev_d = T(0);
-            for (int i = 0; i < M; ++i) {
-                const int id = my_ids[i];
-                if (id < 0) continue;
-                const T x = my_pos[3 * i], y = my_pos[3 * i + 1], z = my_pos[3 * i + 2];
-                const T dist = fb_sqrt(x * x + y * y + z * z);
-                if (dist < min_d) { min_d = dist; min_i = i; }
-                if (DIALECT == DIALECT_CPP && id == prev_id) { prev_d = dist; prev_i = i; }
-            }
-            if (min_i >= 0 && DIALECT == DIALECT_CPP && fb_abs(prev_d - min_d) < dc.switch_thres && prev_d != T(0))
-                min_i = prev_i;
-            int slot = -1, id = -1;
-            if (min_i >= 0) {
-                id = my_ids[min_i];
-                slot = (id >= 0 && id <= FBUS_MAX_MARKER_ID) ? (int)tbl.id2slot[id] : -1;
-            }
-            if (slot < 0) { first = last = 0; }
-            else {
-                if (DIALECT == DIALECT_CPP) new_prev = id;
-                first = min_i; last = min_i + 1;
-            }
-        }
-        T dx[N];
-#pragma unroll
-        for (int i = 0; i < N; ++i) dx[i] = T(0);
+        const MeasRow<T> mr = meas_row(ids, pos, quat, fo, M);
+        if (last > 0 && mode == MODE_NEAREST)
+            POSE_NEAREST_BY_INDEX(T, DIALECT, mr.ids, mr.pos, M, P[L::OFF_PREV - L::OFF_COV], dc.switch_thres,
+                                  (id >= 0 && id <= FBUS_MAX_MARKER_ID) ? (int)tbl.id2slot[id] : -1,
+                                  first, last, new_prev)
+        POSE_DX_ZERO(T, N, dx)
         int used = 0;
         InfoAcc<T> acc;
         PoseFold<T, N, DIALECT> fold;
@@ -1148,18 +1092,9 @@ frames_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* __res
         if (INFO) fold.clear();
         MarkerCommon<T, N> mc;
         mc.build(nom, dc);
-        for (int i0 = first; i0 < last; i0 += FBUS_MARKER_GROUP) {
-            MarkerGroup<T, FBUS_MARKER_GROUP> mg;
-            mg.fetch(my_ids, my_pos, my_quat, i0, last);
-            mg.resolve(tbl);
-#pragma unroll
-            for (int g = 0; g < FBUS_MARKER_GROUP; ++g) {
-                if (mg.slot[g] < 0) continue;
-                if constexpr (INFO) fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-                else marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-                ++used;
-            }
-        }
+        POSE_FOLD_GROUPS(T, mr.ids, mr.pos, mr.quat, first, last, tbl, used,
+                         if constexpr (INFO) fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
+                         else marker_update<T, N, DIALECT, COV>(P, dx, nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]))
         if constexpr (INFO) {
             if (used > 0) { fold.finish(acc, nom, dc, mc); joint_update<T, N, COV>(P, dx, acc); }
         }
@@ -1222,20 +1157,11 @@ frame2_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, c
         load_chunks<T, N, 0, CN, AUX_NT>(rs, my_lane(), nom);
         load_chunks<T, N, CN, RC::NCH, AUX_NT>(rs, my_lane(), P);
     } else {
-        MarkerTableRegs<T> treg;
-        treg.load(dc);
-        order_fence();
-        load_chunks<T, N, 0, CN, AUX_NT>(rs, my_lane(), nom);
-        load_chunks<T, N, CN, RC::NCH, AUX_NT>(rs, my_lane(), P);
-        order_fence();
-        treg.to_lds(tbl);
-        order_fence();
+        POSE_LOAD_RESIDENT(T, N, dc, rs, nom, P, tbl)
     }
     if (b >= B) return;
     const int last = (M > 0 && !(skip && skip[b])) ? M : 0;
-    const int* my_ids = ids + (size_t)b * M;
-    const T* my_pos = pos + (size_t)b * M * 3;
-    const T* my_quat = quat + (size_t)b * M * 4;
+    const MeasRow<T> mr = meas_row(ids, pos, quat, (size_t)b, M);
     const Park park{ lds_mem + threadIdx.x };
     predict_steps<T, N, DIALECT, NoMidHook, Park, FBUS_X_PACK_2W>(nom, P, K, accel, gyro, dt, dt_stride, B, b, dc.qd, NoMidHook(), park);
     order_fence();
@@ -1245,9 +1171,7 @@ frame2_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, c
     store_chunks<T, N, C_E, RC::NCH>(rs, my_lane(), P + (C_E - CN) * EPC);
     int used = 0;
     InfoFactors<T> fac;
-    T dx[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) dx[i] = T(0);
+    POSE_DX_ZERO(T, N, dx)
     if constexpr (MAP_LATE) {
         // every lane of the batch takes part (also those whose frame is skipped); the lanes past the batch end have left: the copy
         // is shared by the nact lanes that remain (wave-uniform)
@@ -1270,17 +1194,8 @@ frame2_kernel(T* __restrict__ recs, int B, int K, const T* __restrict__ accel, c
         fold.clear();
         MarkerCommon<T, N> mc;
         mc.build(nom, dc);
-        for (int i0 = 0; i0 < last; i0 += FBUS_MARKER_GROUP) {
-            MarkerGroup<T, FBUS_MARKER_GROUP> mg;
-            mg.fetch(my_ids, my_pos, my_quat, i0, last);
-            mg.resolve(tbl);
-#pragma unroll
-            for (int g = 0; g < FBUS_MARKER_GROUP; ++g) {
-                if (mg.slot[g] < 0) continue;
-                fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-                ++used;
-            }
-        }
+        POSE_FOLD_GROUPS(T, mr.ids, mr.pos, mr.quat, 0, last, tbl, used,
+                         fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]))
         if (used > 0) { fold.finish(acc, nom, dc, mc); joint_factor<T>(acc, fac); }
         order_fence();
 #pragma unroll

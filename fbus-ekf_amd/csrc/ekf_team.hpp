@@ -861,9 +861,7 @@ frames_team_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* 
             const size_t fo = (size_t)f * B + b;
             int first = 0, last = (M > 0 && live && !(skip && skip[fo])) ? M : 0;
             int new_prev = -1, used = 0;
-            const int* my_ids = ids + fo * M;
-            const T* my_pos = pos + fo * M * 3;
-            const T* my_quat = quat + fo * M * 4;
+            const MeasRow<T> mr = meas_row(ids, pos, quat, fo, M);
 #pragma unroll 1
             for (int t = 0; t <= K; ++t) {
                 if (t < K) {
@@ -873,47 +871,17 @@ frames_team_kernel(T* __restrict__ recs, int B, int F, FrameCounts kc, const T* 
                 } else if (M > 0) {
                     // the nominal state is final: marker choice (MeasureUpdate.m:51-60 ; filter.cpp:639-664) and the fold of the
                     // rows -> Lam, b in LDS, while the covariance roles run the frame's last step
-                    if (last > 0 && mode == MODE_NEAREST) {
-                        const int prev_id = (DIALECT == DIALECT_CPP) ? (int)prev_val : 0;
-                        int min_i = -1, prev_i = -1;
-                        T min_d = T(10), prev_d = T(0);
-                        for (int i = 0; i < M; ++i) {
-                            const int id = my_ids[i];
-                            if (id < 0) continue;
-                            const T x = my_pos[3 * i], y = my_pos[3 * i + 1], z = my_pos[3 * i + 2];
-                            const T dist = fb_sqrt(x * x + y * y + z * z);
-                            if (dist < min_d) { min_d = dist; min_i = i; }
-                            if (DIALECT == DIALECT_CPP && id == prev_id) { prev_d = dist; prev_i = i; }
-                        }
-                        if (min_i >= 0 && DIALECT == DIALECT_CPP && fb_abs(prev_d - min_d) < dc.switch_thres && prev_d != T(0))
-                            min_i = prev_i;
-                        int slot = -1, id = -1;
-                        if (min_i >= 0) {
-                            id = my_ids[min_i];
-                            slot = (id >= 0 && id <= FBUS_MAX_MARKER_ID) ? (int)tbl.id2slot[id] : -1;
-                        }
-                        if (slot < 0) { first = last = 0; }
-                        else {
-                            if (DIALECT == DIALECT_CPP) new_prev = id;
-                            first = min_i; last = min_i + 1;
-                        }
-                    }
+                    if (last > 0 && mode == MODE_NEAREST)
+                        POSE_NEAREST_BY_INDEX(T, DIALECT, mr.ids, mr.pos, M, prev_val, dc.switch_thres,
+                                              (id >= 0 && id <= FBUS_MAX_MARKER_ID) ? (int)tbl.id2slot[id] : -1,
+                                              first, last, new_prev)
                     InfoAcc<T> acc;
                     PoseFold<T, N, DIALECT> fold;
                     fold.clear();
                     MarkerCommon<T, N> mc;
                     mc.build(nom, dc);
-                    for (int i0 = first; i0 < last; i0 += FBUS_MARKER_GROUP) {
-                        MarkerGroup<T, FBUS_MARKER_GROUP> mg;
-                        mg.fetch(my_ids, my_pos, my_quat, i0, last);
-                        mg.resolve(tbl);
-#pragma unroll
-                        for (int g = 0; g < FBUS_MARKER_GROUP; ++g) {
-                            if (mg.slot[g] < 0) continue;
-                            fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]);
-                            ++used;
-                        }
-                    }
+                    POSE_FOLD_GROUPS(T, mr.ids, mr.pos, mr.quat, first, last, tbl, used,
+                                     fold.add(nom, dc, mc, mg.mk[g], mg.yp[g], mg.yq[g]))
                     fold.finish(acc, nom, dc, mc);
                     if (used == 0) { acc.clear(); new_prev = -1; }
 #pragma unroll
