@@ -13,6 +13,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_group.hpp"
+#include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -290,80 +291,27 @@ void timing_end(fbus_ekf_t h, int i)
     if (i >= 0) (void)hipEventRecord(h->ev_pool[i].b, h->stream);
 }
 
-// How many waves should share one 64-filter tile?  One wave per tile (the lane-per-filter kernels) fills the chip from
-// 1024 tiles on; below that the SIMDs that would idle can take a share of every filter's work instead (ekf_team.hpp).
-// Measured (rocprofv3 kernel trace, profiles/r03_team_kernels.txt), one-wave -> team:
-//   predict    4096 filters 4.52 -> 4.00 us (3 roles), 16 384: 4.80 -> 4.52, 32 768: 6.4 -> 8.8 (the roles' overlapping loads cost
-//              more than the shorter instruction streams save once the launch moves 47 MB)            => up to 256 tiles
-//   predict_n  K = 8: 4096 filters 18.8 -> 10.3 us, 16 384: 20.7 -> 17.5, 32 768: 23.2 -> 20.9                 => up to 512 tiles
-//   correct    4096 filters 6.4 -> 7.6 us, 16 384: 7.2 -> 9.2, 32 768: 10.0 -> 18: the one-wave kernel folds its markers under
-//              the load latency and the team pays two exchanges and a redundant 6 x 6 solve per role       => never by default
-// (round 4) The thresholds are fractions of the device's SIMD count (256 / 512 tiles = a quarter / half of MI355X's 1024 SIMDs: what
-// was measured is "how much of the chip a one-wave launch leaves idle"), and the batch they are compared with is the POLICY batch:
-// the handle's own unless fbus_ekf_set_policy_batch names the whole job -- team and one-wave kernels agree to fp32 rounding only,
-// so a job cut into shards (fbus::ShardedFilter) keys the choice on the total and gets the same kernels whatever the shard layout.
-// the measurement updates read the noise table: one set by the caller, or the handle's own row while the likelihood sums are on
-bool tabled(const fbus_ekf* h) { return h->noise_on || h->lik_on; }
-int policy_tiles(const fbus_ekf* h) { return ((h->policy_batch > 0 ? h->policy_batch : h->B) + 63) / 64; }
-int quarter_chip(const fbus_ekf* h) { return h->lp.simds / 4; }
-int half_chip(const fbus_ekf* h) { return h->lp.simds / 2; }
-// A noise table and the resident windows (frames_kernel / frame_meas_kernel with (TrajOut, NoiseIn): kernels_tu.hip families 19 / 20).
-// The fused frames and the frame windows of a tabled handle take them exactly where an untabled handle of the same policy batch runs
-// the ONE-WAVE resident kernels: fp32 records, more than half a chip of tiles.  A pure size rule on the policy batch (fbus_ekf_set_team
-// stays ignored while a table is set; the shards of a job agree with the unsharded run).  At or below half a chip, where untabled
-// handles take the team forms, and while the likelihood sums are on (no resident kernel feeds them): frame by frame through the per-call
-// kernels.  What a single call can still exclude -- (Joseph, nearest) pose rows, M = 0, FBUS_NO_FRAME_MEAS -- is excluded as without a table.
-bool noise_resident(const fbus_ekf* h) { return h->noise_on && !h->lik_on && h->dtype == 32 && policy_tiles(h) > half_chip(h); }
-int team_roles_predict(const fbus_ekf* h, int K)
-{
-    if (h->dtype != 32 || h->team_predict == 1 || tabled(h)) return 1;      // (a noise table, likelihood sums: the one-wave forms only)
-    if (h->team_predict >= 2) return K > 1 ? 4 : (h->team_predict > 4 ? 4 : h->team_predict);
-    const int tiles = policy_tiles(h);
-    if (K > 1) return tiles <= half_chip(h) ? 4 : 1;
-    return tiles <= quarter_chip(h) ? 3 : 1;
-}
-// correct from stereo corners (stacked mode) / from corner pixels (ekf_meas.hpp: the markers of a filter divided among the roles; these
-// kernels are bound by the VALU work per marker).  fbus_ekf_set_team's correct_roles: 1 = never, 2 = two roles, 3..4 = four;
-// 0 = four up to a quarter of the chip, two up to half.  Both record types.
-int team_roles_pixels(const fbus_ekf* h, int M)
-{
-    if (M < 2 || h->team_correct == 1 || tabled(h)) return 1;
-    if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
-    const int tiles = policy_tiles(h);
-    return tiles <= quarter_chip(h) ? 4 : (tiles <= half_chip(h) ? 2 : 1);
-}
-// (round 5) correct_pixels with the UPDATE divided between the waves of a tile as well (ekf_meas_split.hpp: a solver and an updater wave,
-// every wave below 256 registers): 0 = not this launch (the one-wave-tail kernel with team_roles_pixels' fold roles), 2 = two waves per
-// tile (from a quarter of the chip on, full-chip launches included: two waves per SIMD there), 4 = four (small launches).  fp32
-// records and the port square to the camera only; fbus_ekf_set_team's correct_roles = 1 keeps the one-wave kernel.
-int meas_split_roles(const fbus_ekf* h, int M)
+// The launch policy (ekf_route.hpp: which kernels a call runs) reads the handle through this key alone.
+static_assert(ROUTE_MODE_NEAREST == FBUS_MODE_NEAREST && ROUTE_MODE_STACKED == FBUS_MODE_STACKED && ROUTE_PIXELS == FBUS_MEAS_PIXELS &&
+              ROUTE_CORNERS == FBUS_MEAS_CORNERS && ROUTE_MAX_RESIDENT_K == 255, "ekf_route.hpp restates include/fbus_ekf.h");
+RouteKey route_key(const fbus_ekf* h)
 {
     const double* n = h->prm.port_normal;
-    if (h->dtype != 32 || M < 2 || h->team_correct == 1 || h->meas_split == 0 || tabled(h)) return 0;
-    if (!(n[0] == 0.0 && n[1] == 0.0 && n[2] == 1.0)) return 0;
-    if (h->meas_split > 0) return h->meas_split;
-    if (h->team_correct >= 2) return h->team_correct >= 3 ? 4 : 2;
-    const int tiles = policy_tiles(h);
-    return tiles <= quarter_chip(h) ? 4 : (tiles <= half_chip(h) ? 2 : 0);
+    RouteKey k;
+    k.dtype = h->dtype;
+    k.joseph = h->prm.cov_form == FBUS_COV_JOSEPH;
+    k.noise_on = h->noise_on;
+    k.lik_on = h->lik_on;
+    k.tiles = policy_tiles_of(h->policy_batch, h->B);
+    k.simds = h->lp.simds;
+    k.team_predict = h->team_predict;
+    k.team_correct = h->team_correct;
+    k.team_frame = h->team_frame;
+    k.meas_split = h->meas_split;
+    k.no_frame_meas = h->no_frame_meas;
+    k.square_port = n[0] == 0.0 && n[1] == 0.0 && n[2] == 1.0;
+    return k;
 }
-// fused frame / frame window (frames_team_kernel: the predict_n pipeline + the one-shot correct divided over the four roles).  Follows the predict
-// setting (fbus_ekf_set_team: 1 = never, 2..4 = always); FBUS_TEAM_FRAME=1|2 overrides.  Two workgroups of four waves fit a CU
-// (80 KiB of LDS, 250 registers), so the automatic choice ends at 512 tiles (profiles/logs/r03_team_frame.txt: +8 % / +12 % at
-// 32 768 filters, 0.8x at 40 960).
-bool team_frames(const fbus_ekf* h, int mode)
-{
-    if (h->dtype != 32 || h->prm.cov_form == FBUS_COV_JOSEPH || tabled(h)) return false;
-    if (!mode_ok(mode)) return false;
-    if (h->team_frame == 1 || (h->team_frame == 0 && h->team_predict == 1)) return false;
-    if (h->team_frame == 2 || h->team_predict >= 2) return true;
-    return policy_tiles(h) <= half_chip(h);
-}
-// (round 4, measured and NOT kept: a batch of more than one wave per SIMD as launches of one round each.  The per-call kernels run
-// 65 536 filters -- 52 MB of records, exactly one wave per SIMD -- at 7.7 TB/s because the records stay cache-resident from launch
-// to launch; two such launches over the two halves of 131 072 filters do NOT run at twice 12.2 us (29.1 us against 28.0 us for the
-// single launch, 60.7 against 55.8 at 262 144: tools/r4_by_batch.sh, profiles/r04_bench_by_batch.txt) -- what is lost past 65 536
-// filters is the residency (56 MB, section 4.1 of DESIGN.md), not the launch shape, and beyond it the kernels stream at the
-// 6.3-6.7 TB/s this part copies at.)
 
 template <typename T, int N, int D>
 int launch_predict_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter)
@@ -390,7 +338,7 @@ int launch_predict_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, c
     if (h->predict_ld == 2) policy = big ? 2 : 1;
     if (h->predict_policy_force >= 0) policy = h->predict_policy_force;
     h->records_warm = false;
-    const int roles = team_roles_predict(h, K);
+    const int roles = team_roles_predict(route_key(h), K);
     const auto one_wave = [&](auto... x) {
         launch_predict_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, policy, (const T*)accel, (const T*)gyro, (const T*)dt,
                                   dt_per_filter ? 1 : 0, make_dc<T>(h), h->lp, x...);
@@ -418,7 +366,7 @@ void with_update_pack(fbus_ekf_t h, const NisDst* nis, const double* no_gate, GO
     const NisOut<T> no = nis ? NisOut<T>{ (T*)nis->nis, (int*)nis->dof, h->d_gate } : NisOut<T>{ nullptr, nullptr, no_gate };
     const NoiseIn ni{ h->d_noise, h->B };
     if (h->lik_on) go(no, ni, LikOut{ h->d_lik, h->B });
-    else if (tabled(h)) go(no, ni);
+    else if (h->noise_on) go(no, ni);
     else if (nis) go(no);
     else go();
 }
@@ -429,7 +377,7 @@ int launch_correct_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, c
     const int ev = timing_begin(h, FBUS_KERNEL_CORRECT);
     h->records_warm = h->warm_after_correct;   // false: written through (sc1), the next predict streams them like any other
     // (the pose kernel always reads a gate table: "no gate" is the row of +inf behind the noise table)
-    const double* no_gate = tabled(h) ? h->d_noise + (size_t)FBUS_NOISE_COLS * h->B : nullptr;
+    const double* no_gate = tabled(route_key(h)) ? h->d_noise + (size_t)FBUS_NOISE_COLS * h->B : nullptr;
     with_update_pack<T>(h, nis, no_gate, [&](auto... x) {
         launch_correct_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                                   h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp, x...);
@@ -454,6 +402,18 @@ int launch_correct_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, c
         }                                                                                        \
     } while (0)
 
+// the kernels that exist for fp32 records only (team, resident windows): their routes are never chosen for fp64 records (ekf_route.hpp)
+#define DISPATCH_F32(h, FN, ...)                                                                 \
+    do {                                                                                         \
+        switch (((h)->dtype == 64 ? 4 : 0) | ((h)->N == 15 ? 2 : 0) | ((h)->prm.dialect == FBUS_DIALECT_CPP ? 1 : 0)) { \
+            case 0: return FN<float, 18, DIALECT_MATLAB>(__VA_ARGS__);                           \
+            case 1: return FN<float, 18, DIALECT_CPP>(__VA_ARGS__);                              \
+            case 2: return FN<float, 15, DIALECT_MATLAB>(__VA_ARGS__);                           \
+            case 3: return FN<float, 15, DIALECT_CPP>(__VA_ARGS__);                              \
+            default: return fail((h), FBUS_ERR_UNSUPPORTED, #FN ": an fp32 route for fp64 records"); \
+        }                                                                                        \
+    } while (0)
+
 int launch_predict(fbus_ekf_t h, int K, const void* a, const void* g, const void* dt, int per)
 {
     DISPATCH(h, launch_predict_t, h, K, a, g, dt, per);
@@ -465,106 +425,84 @@ int launch_correct(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, con
     DISPATCH(h, launch_correct_t, h, M, ids, pos, quat, mode, skip, nis);
 }
 
-struct TrajDst;
-template <typename T, int N, int D>
-int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
-                    int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
-                    const TrajDst* tj);
+// ---- the bodies of the frame and window routes (ekf_route.hpp; the entry points choose, these launch) ---------------------------------------
+// Output slices of a trajectory window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): [nframes][B][19], [nframes][B][N],
+// [nframes][B]; any may be null
+struct TrajDst { void* nom; void* pdiag; uint8_t* applied; };
+
+// FRAME_FUSED / FRAME_F64_FUSED: one camera frame in ONE launch, one wave per tile.  fp64 (round 4; stacked, simple form): the parked
+// K-step predict loop + the row-split passes with the record resident in registers / LDS (frame2_kernel<double>)
 template <typename T, int N, int D>
 int launch_frame_t(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter, int M,
                    const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
-    const bool f64_fused = sizeof(T) == 8 && mode == MODE_STACKED && h->prm.cov_form != FBUS_COV_JOSEPH && K > 0 && K <= 255;
-    // (a noise table: the window kernel with F = 1 where noise_resident() says so -- a window is then bit-equal to its fused frames by
-    // construction; otherwise predict_n + the per-call update, which read the table too)
-    const bool nz_resident = noise_resident(h) && K <= 255;
-    if ((sizeof(T) == 8 && !f64_fused) || (h->prm.cov_form == FBUS_COV_JOSEPH && mode != MODE_STACKED) || (tabled(h) && !nz_resident)) {
-        // no fused kernel for fp64 outside (stacked, simple) and none for the Joseph form with the reference mode's 7 row-by-row
-        // updates (it spilled): those frames are one predict_n launch and one correct launch -- the same arithmetic
-        int rc = FBUS_OK;
-        if (K > 0) rc = launch_predict_t<T, N, D>(h, K, accel, gyro, dt, dt_per_filter);
-        if (rc == FBUS_OK && M > 0) rc = launch_correct_t<T, N, D>(h, M, ids, pos, quat, mode, skip);
-        return rc;
-    }
-    if constexpr (sizeof(T) == 8) {
-        // (round 4) fp64, stacked, simple form: ONE launch per camera frame -- the parked K-step predict loop + the row-split passes
-        // with the record resident in registers / LDS (frame2_kernel<double>)
-        const int ev = timing_begin(h, FBUS_KERNEL_FRAME);
-        h->records_warm = true;
-        launch_frame_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode, false,
-                                (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp);
-        timing_end(h, ev);
-        HIP_TRY(h, hipGetLastError());
-        return FBUS_OK;
-    }
-    if constexpr (sizeof(T) == 4) {
-    if (nz_resident) {
-        const unsigned char kc1 = (unsigned char)K;
-        return launch_frames_t<T, N, D>(h, 1, &kc1, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, nullptr);
-    }
     const int ev = timing_begin(h, FBUS_KERNEL_FRAME);
     h->records_warm = true;
-    if (team_frames(h, mode) && K <= 255) {
-        const unsigned char kc1 = (unsigned char)K;
-        launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, 1, &kc1, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                      dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                      (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
-    } else
     launch_frame_k<T, N, D>(h->stream, (T*)h->recs, h->B, K, (const T*)accel, (const T*)gyro, (const T*)dt,
                             dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
                             h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), h->lp);
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
-    }
     return FBUS_OK;
 }
-
 int launch_frame(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int per, int M,
                  const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
 {
     DISPATCH(h, launch_frame_t, h, K, accel, gyro, dt, per, M, ids, pos, quat, mode, skip);
 }
 
-// Output slices of a trajectory window (fbus_ekf_frames_fused_traj_dev / _frames_meas_fused_traj_dev): [nframes][B][19], [nframes][B][N],
-// [nframes][B]; any may be null
-struct TrajDst { void* nom; void* pdiag; uint8_t* applied; };
-
-// tj: the window with frame f's rows written from its registers (frames_kernel with TrajOut; the caller has checked that the one-wave
-// resident kernel applies: fp32, not (Joseph, nearest), not the team form).  A tabled handle (noise_resident(): the caller has checked) runs
-// the same kernel with (TrajOut, NoiseIn), the window without rows with three null pointers.
+// One launch of a one-wave window kernel with the pack the entry point chose beside the route (window_pack); `go(x...)` launches it.
+// tj: frame f's rows written from its registers; a tabled handle's window without rows passes three null pointers.
+template <typename T, typename GO>
+void with_window_pack(fbus_ekf_t h, WindowPack pack, const TrajDst* tj, GO go)
+{
+    const TrajOut<T> to = tj ? TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied } : TrajOut<T>{ nullptr, nullptr, nullptr };
+    switch (pack) {
+        case PACK_TRAJ_NOISE: go(to, NoiseIn{ h->d_noise, h->B }); break;
+        case PACK_TRAJ: go(to); break;
+        case PACK_NONE: go(); break;
+    }
+}
+// WINDOW_ONE_WAVE, and FRAME_TABLED_RESIDENT with F = 1 (pose rows): frames_kernel
 template <typename T, int N, int D>
-int launch_frames_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+int launch_frames_t(fbus_ekf_t h, WindowPack pack, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
                     int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                     const TrajDst* tj)
 {
-    if constexpr (sizeof(T) == 4) {
-        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
-        h->records_warm = true;
-        const auto one_wave = [&](auto... x) {
-            launch_frames_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                     dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                     h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), x...);
-        };
-        const TrajOut<T> to = tj ? TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied } : TrajOut<T>{ nullptr, nullptr, nullptr };
-        if (noise_resident(h)) one_wave(to, NoiseIn{ h->d_noise, h->B });
-        else if (tj) one_wave(to);
-        else if (team_frames(h, mode))
-            launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
-                                          dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
-                                          (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
-        else one_wave();
-        timing_end(h, ev);
-        HIP_TRY(h, hipGetLastError());
-        return FBUS_OK;
-    }
-    return tj ? fail(h, FBUS_ERR_UNSUPPORTED, "frames_fused_traj: no resident fp64 window") : FBUS_OK;
+    const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
+    h->records_warm = true;
+    with_window_pack<T>(h, pack, tj, [&](auto... x) {
+        launch_frames_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                 dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                 h->prm.cov_form == FBUS_COV_JOSEPH, (const unsigned char*)skip, h->d_applied, make_dc<T>(h), x...);
+    });
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
 }
-
-int launch_frames(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
-                  const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, const TrajDst* tj = nullptr)
+int launch_frames(fbus_ekf_t h, WindowPack pack, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
+                  const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip, const TrajDst* tj)
 {
-    DISPATCH(h, launch_frames_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip, tj);
+    DISPATCH_F32(h, launch_frames_t, h, pack, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip, tj);
+}
+// WINDOW_TEAM, and FRAME_TEAM with F = 1: frames_team_kernel
+template <typename T, int N, int D>
+int launch_frames_team_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt,
+                         int dt_per_filter, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
+{
+    const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
+    h->records_warm = true;
+    launch_frames_team_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt,
+                                  dt_per_filter ? 1 : 0, M, (const int*)ids, (const T*)pos, (const T*)quat, mode,
+                                  (const unsigned char*)skip, h->d_applied, make_dc<T>(h));
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_frames_team(fbus_ekf_t h, int F, const unsigned char* kc, const void* a, const void* g, const void* dt, int per, int M,
+                       const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
+{
+    DISPATCH_F32(h, launch_frames_team_t, h, F, kc, a, g, dt, per, M, ids, pos, quat, mode, skip);
 }
 
 
@@ -830,7 +768,7 @@ int launch_correct_corners_t(fbus_ekf_t h, int M, const int32_t* ids, const void
     // triangulation and fold in double, non-cancelling update (ekf_meas.hpp); records written through (sc1) as correct_kernel's
     h->records_warm = h->warm_after_correct;
     // (the markers of a filter divided among the waves of a tile: the plain stacked update alone)
-    const int roles = mode == MODE_STACKED && !nis ? team_roles_pixels(h, M) : 1;
+    const int roles = mode == MODE_STACKED && !nis ? team_roles_pixels(route_key(h), M) : 1;
     with_update_pack<T>(h, nis, nullptr, [&](auto... x) {
         launch_corners2_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode,
                                    roles, h->prm.marker_size, h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
@@ -848,13 +786,14 @@ int launch_correct_pixels_t(fbus_ekf_t h, int M, const int32_t* ids, const void*
     // double-precision fold + non-cancelling update (ekf_meas.hpp), both record types, either covariance form (the form is
     // symmetric by construction and subtracts nothing on the rows the measurement shrinks: what Joseph's form is chosen for)
     h->records_warm = h->warm_after_correct;          // written through (sc1), as correct_kernel's records
-    const int split = meas_split_roles(h, M);         // (0 on a tabled handle, as team_roles_pixels is 1)
+    const RouteKey key = route_key(h);
+    const int split = meas_split_roles(key, M);       // (0 on a tabled handle, as team_roles_pixels is 1)
     if constexpr (sizeof(T) == 4) {
         if (split > 0)
             launch_pixels_split_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)left, (const T*)right, split,
                                            h->prm.marker_size, h->prm.r_pix, (const unsigned char*)skip, h->d_applied, h->d_id2slot, make_mc(h));
     }
-    if (split == 0 || sizeof(T) != 4) update_pixels<T, N, D>(h, M, ids, left, right, team_roles_pixels(h, M), skip, nullptr);
+    if (split == 0 || sizeof(T) != 4) update_pixels<T, N, D>(h, M, ids, left, right, team_roles_pixels(key, M), skip, nullptr);
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -865,66 +804,33 @@ int launch_correct_pixels(fbus_ekf_t h, int M, const int32_t* ids, const void* l
     DISPATCH(h, launch_correct_pixels_t, h, M, ids, left, right, skip);
 }
 
-// One camera frame with the north star's MeasureUpdate: K predicts + correct_pixels (kind 0) / correct_corners (kind 1).
-// ONE launch (frame_meas_kernel: record resident, covariance parked in LDS across the fold) where the per-call update would run one wave
-// per tile anyway -- fp32 records, more than half a chip of tiles (or fbus_ekf_set_team(., 1)) -- and equal to the per-call
-// sequence to fp32 rounding there (bit-equal: its update alone, K = 0, and a window to its frames); otherwise predict_n + the per-call update (whose team forms fill a small launch better than one resident wave
-// per tile could; fp64 records: the resident fold + covariance do not fit 512 registers).
-// fused: does this handle take the resident kernel (frame_meas_kernel) for M marker slots of this kind / mode?
-template <typename T>
-bool frame_meas_resident(const fbus_ekf* h, int kind, int M, int mode)
-{
-    // (a noise table: the size rule alone, see noise_resident)
-    if (tabled(h)) return sizeof(T) == 4 && M > 0 && !h->no_frame_meas && noise_resident(h);
-    const int roles = (kind == MEAS_CORNERS && mode != MODE_STACKED) ? 1 : team_roles_pixels(h, M);
-    return sizeof(T) == 4 && M > 0 && roles == 1 && !h->no_frame_meas;
-}
-// tj: the resident window (F > 1) with frame f's rows written from the registers (frame_meas_kernel with TrajOut).  A tabled handle runs
-// the window kernel with (TrajOut, NoiseIn) for F = 1 as well, and without rows with three null pointers.
+// FRAME_MEAS_RESIDENT (F = 1), WINDOW_ONE_WAVE of the measurement windows, and FRAME_TABLED_RESIDENT with F = 1 (pixel / corner rows):
+// K predicts + correct_pixels (kind 0) / correct_corners (kind 1) per frame in ONE launch (frame_meas_kernel: record resident, covariance
+// parked in LDS across the fold).  Equal to the per-call sequence to fp32 rounding (bit-equal: its update alone, K = 0, and a window
+// to its frames).
 template <typename T, int N, int D>
-int launch_frame_meas_t(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
+int launch_frame_meas_t(fbus_ekf_t h, WindowPack pack, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                         int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
                         const TrajDst* tj)
 {
-    // F = 1: one frame; F > 1: a window (the caller has checked that the resident kernel applies)
-    const int K = kc[0];
-    if (F == 1 && !frame_meas_resident<T>(h, kind, M, mode)) {
-        int rc = FBUS_OK;
-        if (K > 0) rc = launch_predict_t<T, N, D>(h, K, accel, gyro, dt, dt_per_filter);
-        if (rc == FBUS_OK && M > 0)
-            rc = kind == MEAS_PIXELS ? launch_correct_pixels_t<T, N, D>(h, M, ids, left, right, skip)
-                                     : launch_correct_corners_t<T, N, D>(h, M, ids, left, right, geometry, mode, skip);
-        return rc;
-    }
-    if constexpr (sizeof(T) == 4) {
-        const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
-        h->records_warm = h->warm_after_correct;      // written through (sc1), as the per-call updates: the next predict streams them
-        const DevConst<T> dc = make_dc<T>(h);
-        const auto go = [&](auto... x) {
-            launch_frame_meas_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt, dt_per_filter ? 1 : 0,
-                                         kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode, h->prm.marker_size,
-                                         kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
-                                         h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), dc.qd, x...);
-        };
-        const TrajOut<T> to = tj ? TrajOut<T>{ (T*)tj->nom, (T*)tj->pdiag, tj->applied } : TrajOut<T>{ nullptr, nullptr, nullptr };
-        if (noise_resident(h)) go(to, NoiseIn{ h->d_noise, h->B });
-        else if (tj) go(to);
-        else go();
-        timing_end(h, ev);
-        HIP_TRY(h, hipGetLastError());
-        return FBUS_OK;
-    }
-    return tj ? fail(h, FBUS_ERR_UNSUPPORTED, "frames_meas_fused_traj: no resident fp64 window") : FBUS_OK;
+    const int ev = timing_begin(h, FBUS_KERNEL_FRAME, F);
+    h->records_warm = h->warm_after_correct;      // written through (sc1), as the per-call updates: the next predict streams them
+    const DevConst<T> dc = make_dc<T>(h);
+    with_window_pack<T>(h, pack, tj, [&](auto... x) {
+        launch_frame_meas_k<T, N, D>(h->stream, (T*)h->recs, h->B, F, kc, (const T*)accel, (const T*)gyro, (const T*)dt, dt_per_filter ? 1 : 0,
+                                     kind, M, (const int*)ids, (const T*)left, (const T*)right, geometry, mode, h->prm.marker_size,
+                                     kind == MEAS_PIXELS ? h->prm.r_pix : h->prm.r_pos, h->prm.switch_thres, (const unsigned char*)skip,
+                                     h->d_applied, h->d_id2slot, make_mc(h), make_vc<double>(h), make_vc<T>(h), dc.qd, x...);
+    });
+    timing_end(h, ev);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
 }
-int launch_frame_meas(fbus_ekf_t h, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per, int kind,
+int launch_frame_meas(fbus_ekf_t h, WindowPack pack, int F, const unsigned char* kc, const void* accel, const void* gyro, const void* dt, int per, int kind,
                       int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode, const uint8_t* skip,
-                      const TrajDst* tj = nullptr)
+                      const TrajDst* tj)
 {
-    DISPATCH(h, launch_frame_meas_t, h, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip, tj);
-}
-bool frame_meas_is_resident(const fbus_ekf* h, int kind, int M, int mode)
-{
-    return h->dtype == 32 ? frame_meas_resident<float>(h, kind, M, mode) : false;
+    DISPATCH_F32(h, launch_frame_meas_t, h, pack, F, kc, accel, gyro, dt, per, kind, M, ids, left, right, geometry, mode, skip, tj);
 }
 
 int launch_correct_corners(fbus_ekf_t h, int M, const int32_t* ids, const void* left, const void* right, int geometry,
@@ -1020,6 +926,7 @@ bool frame_counts(int nframes, const int32_t* kcount, int kmax, unsigned char* k
 // kind: KIND_POSE (a, b = pos, quat) or FBUS_MEAS_PIXELS / FBUS_MEAS_CORNERS (a, b = left, right: device pointers); geometry and mode
 // of a pixel frame are set to the values the launchers expect.  An empty window (nframes = 0) passes: the caller returns FBUS_OK.
 constexpr int KIND_POSE = -1;
+static_assert(KIND_POSE == ROUTE_POSE, "a frame's kind is handed to ekf_route.hpp as it is");
 int check_frames(fbus_ekf_t h, const char* where, int nframes, const int32_t* kcount, int kmax, unsigned char* kc, const void* accel,
                  const void* gyro, const void* dt, int kind, int M, const void* ids, const void* a, const void* b, int& geometry,
                  int& mode, const TrajDst* tj)
@@ -1286,6 +1193,48 @@ FrameArrays frame_slice(const fbus_ekf* h, const FrameArrays& w, size_t k0, int 
     return s;
 }
 
+// One camera frame: its route asked (frame_route), then the route's launches.  kind: KIND_POSE (s.a, s.b = pos, quat) or FBUS_MEAS_PIXELS / FBUS_MEAS_CORNERS (left, right)
+int run_frame(fbus_ekf_t h, const RouteKey& key, int kind, int K, const FrameArrays& s, int geometry, int mode)
+{
+    const FrameRoute route = frame_route(key, (RouteKind)kind, mode, s.M, K);
+    const WindowPack pack = window_pack(key, false);
+    const unsigned char kc1 = (unsigned char)K;       // (the routes that count in a byte are chosen for K <= 255 only)
+    switch (route) {
+        case FRAME_PER_CALL: {
+            int rc = FBUS_OK;
+            if (K > 0) rc = launch_predict(h, K, s.accel, s.gyro, s.dt, s.per);
+            if (rc != FBUS_OK || s.M == 0) return rc;
+            if (kind == KIND_POSE) return launch_correct(h, s.M, s.ids, s.a, s.b, mode, s.skip);
+            return kind == FBUS_MEAS_PIXELS ? launch_correct_pixels(h, s.M, s.ids, s.a, s.b, s.skip)
+                                            : launch_correct_corners(h, s.M, s.ids, s.a, s.b, geometry, mode, s.skip);
+        }
+        case FRAME_F64_FUSED:
+        case FRAME_FUSED: return launch_frame(h, K, s.accel, s.gyro, s.dt, s.per, s.M, s.ids, s.a, s.b, mode, s.skip);
+        case FRAME_TEAM: return launch_frames_team(h, 1, &kc1, s.accel, s.gyro, s.dt, s.per, s.M, s.ids, s.a, s.b, mode, s.skip);
+        case FRAME_TABLED_RESIDENT:
+            if (kind == KIND_POSE) return launch_frames(h, pack, 1, &kc1, s.accel, s.gyro, s.dt, s.per, s.M, s.ids, s.a, s.b, mode, s.skip, nullptr);
+            [[fallthrough]];
+        case FRAME_MEAS_RESIDENT:
+            return launch_frame_meas(h, pack, 1, &kc1, s.accel, s.gyro, s.dt, s.per, kind, s.M, s.ids, s.a, s.b, geometry, mode, s.skip, nullptr);
+    }
+    return FBUS_ERR_INVALID;
+}
+// A window frame by frame (WINDOW_BY_FRAME, WINDOW_TEAM_FRAMES): every frame on its own route, its trajectory rows by the snapshot kernel.
+// kcount: nframes counts, each the K of its frame (a single frame's may exceed a byte)
+int run_frames(fbus_ekf_t h, const RouteKey& key, int kind, int nframes, const int32_t* kcount, const FrameArrays& w, int geometry, int mode,
+               const TrajDst* tj)
+{
+    size_t k0 = 0;
+    for (int f = 0; f < nframes; ++f) {
+        const int K = kcount[f];
+        int rc = run_frame(h, key, kind, K, frame_slice(h, w, k0, f), geometry, mode);
+        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
+        if (rc != FBUS_OK) return rc;
+        k0 += (size_t)K;
+    }
+    return FBUS_OK;
+}
+
 // fbus_ekf_frame_dev (fused = false: K predict launches + one correct launch) and fbus_ekf_frame_fused_dev
 int frame_any(fbus_ekf_t h, bool fused, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter, int M,
               const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip)
@@ -1296,13 +1245,13 @@ int frame_any(fbus_ekf_t h, bool fused, int K, const void* accel, const void* gy
     int rc = check_frames(h, fused ? "fbus_ekf_frame_fused_dev" : "fbus_ekf_frame_dev", 1, &K, std::numeric_limits<int>::max(), nullptr, accel, gyro, dt, KIND_POSE, M, ids, pos, quat,
                           geometry, mode, nullptr);
     if (rc != FBUS_OK) return rc;
-    if (fused) return launch_frame(h, K, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
+    if (fused) return run_frame(h, route_key(h), KIND_POSE, K, w, geometry, mode);
     // one event pair around the whole run of K back-to-back predict launches: a pair per launch
     // would cost ~8 us of stream time each and read ~3 us long; duration / K is the per-launch time
     const bool sampled = (h->frame_count++ % h->timing_stride) == 0;
     const int ev = (K > 0 && sampled) ? timing_begin(h, FBUS_KERNEL_PREDICT, K) : -1;
     h->timing_suspended = true;
-    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
     for (int k = 0; k < K && rc == FBUS_OK; ++k) {
         const FrameArrays s = frame_slice(h, w, (size_t)k, 0);
         rc = launch_predict(h, 1, s.accel, s.gyro, s.dt, dt_per_filter);
@@ -1325,27 +1274,16 @@ int frames_any(fbus_ekf_t h, const char* where, int nframes, const int32_t* kcou
     int geometry = 0;
     int rc = check_frames(h, where, nframes, kcount, 255, kc, accel, gyro, dt, KIND_POSE, M, ids, pos, quat, geometry, mode, tj);
     if (rc != FBUS_OK || nframes == 0) return rc;
-    // no resident-record kernel for fp64 and for (Joseph, nearest) -- see launch_frame_t: those windows run frame by frame,
-    // the same arithmetic
-    // (a noise table: the resident window that reads it where noise_resident() says so, else frame by frame through the per-call kernels)
-    const bool resident = h->dtype == 32 && !(h->prm.cov_form == FBUS_COV_JOSEPH && mode != FBUS_MODE_STACKED) &&
-                          (!tabled(h) || noise_resident(h));
-    if (resident && !tj) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
-    // with a trajectory: the one-wave window writes the rows itself; the team window (small launches) runs as one-frame launches of the
-    // same team kernel, the other routes frame by frame -- each frame's rows then come from the snapshot kernel
-    const bool team = resident && team_frames(h, mode);
-    if (resident && !team) return launch_frames(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, tj);
-    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
-    size_t k0 = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const FrameArrays s = frame_slice(h, w, k0, f);
-        rc = team ? launch_frames(h, 1, kc + f, s.accel, s.gyro, s.dt, dt_per_filter, M, s.ids, s.a, s.b, mode, s.skip)
-                  : launch_frame(h, kc[f], s.accel, s.gyro, s.dt, dt_per_filter, M, s.ids, s.a, s.b, mode, s.skip);
-        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
-        if (rc != FBUS_OK) return rc;
-        k0 += kc[f];
+    const RouteKey key = route_key(h);
+    switch (window_route(key, ROUTE_POSE, mode, M, tj != nullptr)) {
+        case WINDOW_ONE_WAVE:
+            return launch_frames(h, window_pack(key, tj != nullptr), nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip, tj);
+        case WINDOW_TEAM: return launch_frames_team(h, nframes, kc, accel, gyro, dt, dt_per_filter, M, ids, pos, quat, mode, skip);
+        case WINDOW_TEAM_FRAMES:        // (every frame's route is then FRAME_TEAM)
+        case WINDOW_BY_FRAME: break;
     }
-    return FBUS_OK;
+    const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, pos, quat, 3, 4, skip };
+    return run_frames(h, key, KIND_POSE, nframes, kcount, w, geometry, mode, tj);
 }
 
 // fbus_ekf_frame_meas_fused_dev (kcount = &K, nframes = 1, single = true: K may exceed a byte), fbus_ekf_frames_meas_fused_dev (tj = null)
@@ -1360,29 +1298,20 @@ int frames_meas_any(fbus_ekf_t h, const char* where, bool single, int nframes, c
     int rc = check_frames(h, where, nframes, kcount, single ? std::numeric_limits<int>::max() : 255, single ? nullptr : kc, accel, gyro,
                           dt, kind, M, ids, left, right, geometry, mode, tj);
     if (rc != FBUS_OK || nframes == 0) return rc;
-    if (single && kcount[0] > 255) {          // (the resident kernel counts a frame's samples in a byte)
-        rc = launch_predict(h, kcount[0], accel, gyro, dt, dt_per_filter);
-        if (rc == FBUS_OK && M > 0)
-            rc = kind == FBUS_MEAS_PIXELS ? launch_correct_pixels(h, M, ids, left, right, skip)
-                                          : launch_correct_corners(h, M, ids, left, right, geometry, mode, skip);
-        return rc;
+    // a single frame, and a window of one, run as that frame; a longer window in one launch where its frames take a resident kernel,
+    // elsewhere frame by frame through the frame's routes -- the same arithmetic
+    const RouteKey key = route_key(h);
+    switch (nframes > 1 ? window_route(key, (RouteKind)kind, mode, M, tj != nullptr) : WINDOW_BY_FRAME) {
+        case WINDOW_ONE_WAVE:
+            return launch_frame_meas(h, window_pack(key, tj != nullptr), nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right,
+                                     geometry, mode, skip, tj);
+        case WINDOW_TEAM:               // (never chosen for pixel / corner rows: their frames have no team route)
+        case WINDOW_TEAM_FRAMES:
+        case WINDOW_BY_FRAME: break;
     }
-    if (single) kc[0] = (unsigned char)kcount[0];
-    // the resident window kernel where the frame form takes the resident kernel (fp32 records, one wave per tile); elsewhere frame by
-    // frame through the frame form's routes -- the same arithmetic (with a trajectory: each frame's rows by the snapshot kernel)
-    if (single || (nframes > 1 && frame_meas_is_resident(h, kind, M, mode)))
-        return launch_frame_meas(h, nframes, kc, accel, gyro, dt, dt_per_filter, kind, M, ids, left, right, geometry, mode, skip, tj);
     const bool c3d = kind == FBUS_MEAS_CORNERS && geometry == FBUS_VIS_CORNERS3D;
     const FrameArrays w{ accel, gyro, dt, dt_per_filter, M, ids, left, right, c3d ? (size_t)12 : (size_t)8, 8, skip };
-    size_t k0 = 0;
-    for (int f = 0; f < nframes; ++f) {
-        const FrameArrays s = frame_slice(h, w, k0, f);
-        rc = launch_frame_meas(h, 1, kc + f, s.accel, s.gyro, s.dt, dt_per_filter, kind, M, s.ids, s.a, s.b, geometry, mode, s.skip);
-        if (rc == FBUS_OK && tj) rc = snapshot_row(h, *tj, f);
-        if (rc != FBUS_OK) return rc;
-        k0 += kc[f];
-    }
-    return FBUS_OK;
+    return run_frames(h, key, kind, nframes, kcount, w, geometry, mode, tj);
 }
 
 // ---- the element-wise entry points --------------------------------------------------------------------------------------------------------
@@ -1764,6 +1693,7 @@ int fbus_ekf_set_policy_batch(fbus_ekf_t h, int total_filters)
 int fbus_ekf_launch_info(fbus_ekf_t h, int what, int arg, int* value)
 {
     if (!h || !value) return FBUS_ERR_INVALID;
+    const RouteKey key = route_key(h);
     switch (what) {
         case FBUS_INFO_SIMDS: *value = h->lp.simds; break;
         case FBUS_INFO_ONE_ROUND_FILTERS: *value = h->lp.simds * 64; break;
@@ -1772,11 +1702,11 @@ int fbus_ekf_launch_info(fbus_ekf_t h, int what, int arg, int* value)
         case FBUS_INFO_MALL_MB: *value = (int)(h->mall_bytes >> 20); break;
         case FBUS_INFO_L2_KB: *value = (int)(h->l2_bytes >> 10); break;
         case FBUS_INFO_POLICY_BATCH: *value = h->policy_batch > 0 ? h->policy_batch : h->B; break;
-        case FBUS_INFO_ROLES_PREDICT: *value = team_roles_predict(h, arg > 1 ? arg : 1); break;
-        case FBUS_INFO_ROLES_MEAS: *value = team_roles_pixels(h, arg > 0 ? arg : 4); break;
-        case FBUS_INFO_TEAM_FRAMES: *value = team_frames(h, MODE_STACKED) ? 1 : 0; break;
-        case FBUS_INFO_MEAS_SPLIT: *value = meas_split_roles(h, arg > 0 ? arg : 4); break;
-        case FBUS_INFO_NOISE_RESIDENT: *value = noise_resident(h) ? 1 : 0; break;
+        case FBUS_INFO_ROLES_PREDICT: *value = team_roles_predict(key, arg > 1 ? arg : 1); break;
+        case FBUS_INFO_ROLES_MEAS: *value = team_roles_pixels(key, arg > 0 ? arg : 4); break;
+        case FBUS_INFO_TEAM_FRAMES: *value = team_frames(key, FBUS_MODE_STACKED) ? 1 : 0; break;
+        case FBUS_INFO_MEAS_SPLIT: *value = meas_split_roles(key, arg > 0 ? arg : 4); break;
+        case FBUS_INFO_NOISE_RESIDENT: *value = noise_resident(key) ? 1 : 0; break;
         default: return FBUS_ERR_INVALID;
     }
     return FBUS_OK;

@@ -321,9 +321,9 @@ int fbus_ekf_frame_fused_dev(fbus_ekf_t h, int K, const void* accel, const void*
  * flat-port model, vision.cpp:496-599 run forward) in ONE launch, the record resident in registers / LDS in between.  Same
  * arithmetic as K fbus_ekf_predict_dev calls + one fbus_ekf_correct_pixels_dev / _corners_dev call, and equal results TO FP32
  * ROUNDING (the single-step gate of tests/util.py: which product of an a b + c d becomes an FMA differs between the specialised
- * kernels); bit-equal are the update alone (K = 0) to the per-call update and a window to its sequence of frames -- where that
- * update runs one wave per tile: more than half a chip of tiles, or fbus_ekf_set_team(h, ., 1).  Smaller launches and fp64
- * records run as fbus_ekf_predict_n_dev + the per-call update.  M = 0: predicts only.  left / right: 16-byte aligned. */
+ * kernels); bit-equal are the update alone (K = 0) to the per-call update and a window to its sequence of frames.  Where the one
+ * launch is taken and where the frame runs as fbus_ekf_predict_n_dev + the per-call update: the route table, DESIGN.md 5.1 (rows
+ * "pixels, corners").  M = 0: predicts only.  left / right: 16-byte aligned. */
 enum { FBUS_MEAS_PIXELS = 0, FBUS_MEAS_CORNERS = 1 };
 int fbus_ekf_frame_meas_fused_dev(fbus_ekf_t h, int K, const void* accel, const void* gyro, const void* dt, int dt_per_filter,
                                   int kind, int M, const int32_t* ids, const void* left, const void* right, int geometry, int mode,

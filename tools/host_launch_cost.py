@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """Host-side cost of the per-call path with a launch-bound batch (B = 64): per frame through the Python wrapper, per
-frame through ctypes with pre-extracted pointers, and per launch inside the C ABI (one frame_dev call with K = 64)."""
+frame through ctypes with pre-extracted pointers, and per launch inside the C ABI (one frame_dev call with K = 64); then the host cost
+of the two fused single-frame entry points (route choice + one launch: frame_fused_dev, frame_meas_fused_dev), 2000 calls each.
+FBUS_EKF_LIB selects the library (A/B of two builds: run them alternately)."""
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "fbus-ekf_amd"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
 import torch
 from fbus_ekf import BatchedFilter, capi, synth
 B, M, K = 64, 4, 64
@@ -34,4 +38,19 @@ with BatchedFilter(B, prm) as flt:
     args = (hnd, K, p(d_acc), p(d_gyr), p(d_dt), 0, M, p(d_ids), p(d_pos), p(d_quat), 1, None)
     h, w = timed(lambda: lib.fbus_ekf_frame_dev(*args), 300)
     print(f"ctypes, one call with K = {K} predicts + correct : host {h:7.1f} us  wall {w:7.1f} us per call  = {w / (K + 1):5.2f} us per launch")
+    args = (hnd, 7, p(a7), p(g7), p(dt7), 0, M, p(d_ids), p(d_pos), p(d_quat), 1, None)
+    h, w = timed(lambda: lib.fbus_ekf_frame_fused_dev(*args), 2000)
+    print(f"ctypes, frame_fused_dev, 7 predicts + correct   : host {h:7.2f} us  wall {w:7.2f} us per call")
+    flt._keep.clear()
+# the north star's frame: pixel rows of the left camera (util.pixel_scene, as smoke() builds them)
+from util import pixel_scene
+prm.marker_size = 0.28
+truth, trot, p_ids, p_left, _ = pixel_scene(B, M, prm, 0.28, seed=5, noise=5e-4, nominal=nom)
+d_pids, d_left = torch.from_numpy(np.ascontiguousarray(p_ids, np.int32)).to(dev), f32(p_left)
+with BatchedFilter(B, prm) as flt:
+    flt.set_state(truth, trot, P, prev)
+    lib, hnd, p = flt._lib, flt._h, flt._p
+    args = (hnd, 7, p(d_acc[:7]), p(d_gyr[:7]), p(d_dt[:7]), 0, capi.MEAS_PIXELS, M, p(d_pids), p(d_left), None, capi.VIS_REFRACTIVE, 1, None)
+    h, w = timed(lambda: lib.fbus_ekf_frame_meas_fused_dev(*args), 2000)
+    print(f"ctypes, frame_meas_fused_dev, 7 predicts + pixels: host {h:7.2f} us  wall {w:7.2f} us per call")
     flt._keep.clear()
