@@ -7,9 +7,8 @@ for sub in ("../fbus-ekf_amd", "../oracle", "."):
     sys.path.insert(0, os.path.join(HERE, sub))
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
+from support import r32
 from util import cov_rel_err, cov_rel_err_blockwise, state_rel_err, _BLOCKS
-
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
 
 def blocks(got, ref):
     out = []

@@ -23,13 +23,12 @@ import numpy as np
 
 import oracle_capi as oc
 from fbus_ekf import capi, synth
+from support import frozen, r32
 from util import pixel_scene
 
 B = 129
 SIZE = 0.2                                   # marker edge [m]: 0.3 m pitch leaves room for the in-plane rotation of each marker
 PITCH = 0.3
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
 EDGE_IDS = (0, 7, 8, 511, 512, 1016, 1023)
 EDGE_SLOTS = (0, 12, 15, 16, 25, 26, 31)
 # slot order: a fixed shuffle.  Slot 0 holds id 1023, slot 31 id 0; the other five edge slots hold the other five edge ids, so that an
@@ -196,7 +195,7 @@ def pose_scene(Bn=B, M=4, dialect=0, nstate=18, frames=1):
     acc, gyr = synth.imu_samples(0, Bn, 0, 4, nom)
     s = types.SimpleNamespace(kind="pose", B=Bn, M=M, dialect=dialect, nstate=nstate, prm=prm, state=(nom, rot, P, prev),
                               ids=ids, pos=pos, quat=quat, acc=r32(acc), gyr=r32(gyr), dt=r32(np.full(4, 0.005)))
-    _CACHE[key] = s
+    _CACHE[key] = frozen(s)
     return s
 
 
@@ -234,7 +233,7 @@ def _pixel_draw(Bn, dialect, nstate):
                     c3[b, m] = _corners_in_camera(prm, truth[b], slot_of[int(ids[b, m])]).ravel()
         c3 += rng.normal(0, 0.003, c3.shape)                                  # triangulated corners: the true ones + 3 mm
         acc, gyr = synth.imu_samples(0, Bn, 0, 4, nom)
-        _CACHE[key] = (prm, (nom, rot, r32(P), prev), ids, r32(left), r32(right), r32(c3), r32(acc), r32(gyr))
+        _CACHE[key] = frozen((prm, (nom, rot, r32(P), prev), ids, r32(left), r32(right), r32(c3), r32(acc), r32(gyr)))
     return _CACHE[key]
 
 
@@ -253,7 +252,7 @@ def meas_scene(Bn=B, M=4, dialect=0, nstate=18):
     s = types.SimpleNamespace(kind="meas", B=Bn, M=M, dialect=dialect, nstate=nstate, prm=prm, state=(nom, rot, P, prev),
                               ids=ids, left=np.ascontiguousarray(left[:, :M]), right=np.ascontiguousarray(right[:, :M]),
                               c3=np.ascontiguousarray(c3[:, :M]), acc=acc, gyr=gyr, dt=r32(np.full(4, 0.005)))
-    _CACHE[key] = s
+    _CACHE[key] = frozen(s)
     return s
 
 
@@ -267,7 +266,7 @@ def twin_of(scene, seed=TWIN_SEED):
         t.ids, prev = relabel(t.prm, None, [scene.ids, prev], seed)
         t.rename = lambda a: relabel(capi.FbusParams.from_buffer_copy(scene.prm), None, a, seed)     # ids of the scene -> the twin's
         t.state = scene.state[:3] + (prev,)
-        _CACHE[key] = (t, scene)                        # (keeps `scene` alive: id() stays unique)
+        _CACHE[key] = (frozen(t), scene)                # (keeps `scene` alive: id() stays unique)
     return _CACHE[key][0]
 
 
@@ -281,7 +280,7 @@ def triangulated(scene):
             for m in range(scene.M):
                 if scene.ids[b, m] >= 0:
                     out[b, m] = oc.refraction_triangulate(vp, scene.left[b, m], scene.right[b, m])
-        _CACHE[key] = (out, scene)
+        _CACHE[key] = (frozen(out), scene)
     return _CACHE[key][0]
 
 

@@ -1,14 +1,11 @@
 """The cells of the route walks: handle states, shared inputs and the calls through the frame and window entry points, at a small batch
 placed in each size class with set_policy_batch.  Used by tests/test_routes_gpu.py (which asserts on about a hundred cells) and by
 tools/route_matrix.py (which prints every cell for comparing two builds).  The scenes come from the suite's own builders."""
-import os
-
 import numpy as np
 import torch
 
 from fbus_ekf import BatchedFilter, capi, synth
-from test_nis_gpu import _dev, _same, _setup
-from test_noise_gpu import G, imu, rows_of, state_of
+from support import G, env, imu, perturbed_setup, rows_of, state_of, to_device
 
 B = 128
 KC = (3, 0, 2)                          # IMU samples in front of each frame: unequal, one frame without any
@@ -60,7 +57,7 @@ class Data:
         self.prm, self.state = state_of(B, dtype, nstate, dialect)
         nom = self.state[0]
         a, w, dt = imu(B, 300, nom, dtype)
-        self.a, self.w, self.dt = _dev(a, npd), _dev(w, npd), _dev(dt, npd)
+        self.a, self.w, self.dt = to_device(a, npd), to_device(w, npd), to_device(dt, npd)
         ids = np.zeros((F, B, 4), np.int32)
         pos, quat = np.zeros((F, B, 4, 3)), np.zeros((F, B, 4, 4))
         for f in range(F):
@@ -69,15 +66,15 @@ class Data:
         skip = np.zeros((F, B), np.uint8)
         skip[0, 7::29] = 1
         skip[F - 1, 12] = 1
-        self.skip = _dev(skip, np.uint8)
-        self.rows = {"pose": (_dev(ids, np.int32), _dev(pos, npd), _dev(quat, npd))}
+        self.skip = to_device(skip, np.uint8)
+        self.rows = {"pose": (to_device(ids, np.int32), to_device(pos, npd), to_device(quat, npd))}
         rng = np.random.default_rng(77)
         for kind in ("stereo", "corners"):
-            prm, mnom, rot, P, prev, mids, left, right = _setup(B, dtype, nstate, dialect, kind, n=B)
+            prm, mnom, rot, P, prev, mids, left, right = perturbed_setup(B, dtype, nstate, dialect, kind, n=B)
             idsF = np.stack([mids] * F)
             idsF[1, 5] = -1
             noisy = lambda x: np.stack([x] * F) + rng.normal(0, 2e-4, (F,) + x.shape)
-            self.rows[kind] = (_dev(idsF, np.int32), _dev(noisy(left), npd), _dev(noisy(right), npd) if kind == "stereo" else None)
+            self.rows[kind] = (to_device(idsF, np.int32), to_device(noisy(left), npd), to_device(noisy(right), npd) if kind == "stereo" else None)
             self.meas_prm, self.meas_state = prm, (mnom, rot, P, prev)
         self.rows["left"] = self.rows["stereo"][:2] + (None,)
         torch.cuda.synchronize()
@@ -95,13 +92,8 @@ def make(cfg, d, meas):
     B = d.B
     prm = capi.FbusParams.from_buffer_copy(d.meas_prm if meas else d.prm)
     prm.cov_form = capi.COV_JOSEPH if cfg.joseph else capi.COV_SIMPLE
-    before = {k: os.environ.get(k) for k in cfg.env}
-    os.environ.update(cfg.env)                            # (read once, at create)
-    try:
+    with env(**cfg.env):                                  # (read once, at create)
         f = BatchedFilter(B, prm, device=0, dtype=cfg.dtype, nstate=cfg.nstate)
-    finally:
-        for k, v in before.items():
-            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
     f.set_state(*(d.meas_state if meas else d.state))
     f.set_team(*cfg.team)
     f.set_policy_batch(policy_batch(f, cfg.size))

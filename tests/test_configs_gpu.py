@@ -19,6 +19,7 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, replay, synth
 from replay_ref import OracleEngine
+from support import r32
 from util import (COV_BLOCK_TOL, COV_BLOCK_TOL_F64, COV_TOL, PLAIN_TOL, PLAIN_WINDOW_TOL, STATE_TOL, WINDOW_TOL,
                   assert_parity, cov_rel_err, cov_rel_err_blockwise, parity_errors, state_rel_err, state_rel_err_literal,
                   state_rel_err_plain)
@@ -26,7 +27,6 @@ from util import (COV_BLOCK_TOL, COV_BLOCK_TOL_F64, COV_TOL, PLAIN_TOL, PLAIN_WI
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 DT = np.float64(np.float32(0.005))
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
 
 
 def _dev():
@@ -431,7 +431,6 @@ def test_water_recording_through_the_north_stars_reprojection_rows():
     d = np.load(os.path.join(GOLD, "recordings.npz"))
     imu, image, corners = d["water_imu"], d["water_image"], d["water_corners"]
     nfr = 100
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
     for dialect in (0, 1):
         prm = capi.default_params(dialect)
         prm.marker_size = WATER_MARKER_SIDE

@@ -15,7 +15,7 @@ import pytest
 import torch
 
 from fbus_ekf import BatchedFilter, capi, gating, synth
-from test_nis_gpu import _setup
+from support import frozen, perturbed_setup, same_state, to_device
 
 pytestmark = pytest.mark.gpu
 B, M, N = 130, 2, 18
@@ -32,7 +32,7 @@ def _pose_inputs(dtype):
         nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), N, mixed_cov=True)
         acc, gyr = synth.imu_samples(0, B, 0, 3, nom)
         ids, pos, quat = synth.marker_frame(0, B, 0, M, nom, prm)
-        _CACHE["pose", dtype] = (prm, (c(nom), c(rot), c(P), prev), c(acc), c(gyr), np.ascontiguousarray(ids, np.int32), c(pos), c(quat))
+        _CACHE["pose", dtype] = frozen((prm, (c(nom), c(rot), c(P), prev), c(acc), c(gyr), np.ascontiguousarray(ids, np.int32), c(pos), c(quat)))
     return _CACHE["pose", dtype]
 
 
@@ -40,22 +40,14 @@ def _image_inputs(dtype, kind):
     """kind "stereo": pixel rows left / right (B, M, 8); "corners": left = (B, M, 12) corner positions"""
     if (kind, dtype) not in _CACHE:
         c = lambda a: np.ascontiguousarray(a, NPD[dtype])
-        prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, N, 1, kind, M=M, n=B)
-        _CACHE[kind, dtype] = (prm, (c(nom), c(rot), c(P), prev), np.ascontiguousarray(ids, np.int32), c(left), c(right))
+        prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, N, 1, kind, M=M, n=B)
+        _CACHE[kind, dtype] = frozen((prm, (c(nom), c(rot), c(P), prev), np.ascontiguousarray(ids, np.int32), c(left), c(right)))
     return _CACHE[kind, dtype]
-
-
-def _dev(a):
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _snapshot(f):
     """(records, applied) of a handle, complete"""
     return f.get_state() + (f.applied(),)
-
-
-def _equal(a, b):
-    return all(np.array_equal(x, y) for x, y in zip(a, b))
 
 
 # ---- the transports are bit-equal ---------------------------------------------------------------------------------------------------
@@ -85,7 +77,7 @@ def test_update_transports_are_bit_equal(case, dtype):
             if gate is not None:
                 f.set_gate(gate)
             name = method + ("_nis" if nis else "") + ("_async" if transport == "async" else "")
-            conv = _dev if transport == "dev" else (lambda a: a)
+            conv = to_device if transport == "dev" else (lambda a: a)
             args = [conv(a) for a in arrays]
             out = getattr(f, name)(*args, *tail, skip=conv(SKIP))
             f.sync()
@@ -96,14 +88,14 @@ def test_update_transports_are_bit_equal(case, dtype):
     ref, _ = run("dev")
     applied = ref[-1]
     assert applied.any() and not applied[SKIP == 1].any() and (SKIP == 1).any()
-    assert not _equal(ref[:4], state)                                       # (the update moved the records)
-    assert _equal(run("host")[0], ref), "host-pointer form"
+    assert not same_state(ref[:4], state)                                       # (the update moved the records)
+    assert same_state(run("host")[0], ref), "host-pointer form"
     if has_async:
-        assert _equal(run("async")[0], ref), "_async form"
+        assert same_state(run("async")[0], ref), "_async form"
     for gate in (None, gating.chi2_gate(0.999, 64)):
         sd, (nis_d, dof_d) = run("dev", nis=True, gate=gate)
         sh, (nis_h, dof_h) = run("host", nis=True, gate=gate)
-        assert _equal(sd, sh), "_nis host-pointer form"
+        assert same_state(sd, sh), "_nis host-pointer form"
         assert np.array_equal(nis_d, nis_h) and np.array_equal(dof_d, dof_h)
         assert sd[-1].any() and not sd[-1][SKIP == 1].any()
         assert np.isfinite(nis_d[sd[-1] == 1]).all() and (dof_d[sd[-1] == 1] > 0).all()
@@ -121,16 +113,16 @@ def test_predict_transports_are_bit_equal(K, per, dtype):
         with BatchedFilter(B, prm, dtype=dtype, nstate=N) as f:
             f.set_state(*state)
             if transport == "dev":
-                f.predict_n(_dev(acc[:K]), _dev(gyr[:K]), _dev(dt), K=K)
+                f.predict_n(to_device(acc[:K]), to_device(gyr[:K]), to_device(dt), K=K)
             elif transport == "host":
                 (f.predict if K == 1 else f.predict_n)(acc[:K], gyr[:K], dt)
             else:
                 f.predict_async(acc[:K], gyr[:K], dt, K=K)
             f.sync()
             got.append(f.get_state())
-    assert not _equal(got[0], state)
-    assert _equal(got[1], got[0]), "host-pointer form"
-    assert _equal(got[2], got[0]), "_async form"
+    assert not same_state(got[0], state)
+    assert same_state(got[1], got[0]), "host-pointer form"
+    assert same_state(got[2], got[0]), "_async form"
 
 
 # ---- every form refuses the same calls the same way ------------------------------------------------------------------------------------
@@ -141,7 +133,7 @@ class _Forms:
     def __init__(self, flt, host, order):
         self.f, self.lib, self.h = flt, flt._lib, flt._h
         self.host = host
-        self.dev = {k: _dev(v) if isinstance(v, np.ndarray) else v for k, v in host.items()}
+        self.dev = {k: to_device(v) if isinstance(v, np.ndarray) else v for k, v in host.items()}
         self.order = order                          # {form name: its parameters behind the handle, in order}
         self.table = np.zeros(B * capi.NOISE_COLS, np.float64)
 
@@ -170,7 +162,7 @@ class _Forms:
         if message is not None:
             assert message in self.message(), (form, self.message())
         f.sync()
-        assert _equal(_snapshot(f), before), (form, "a refused call changed the handle")
+        assert same_state(_snapshot(f), before), (form, "a refused call changed the handle")
         assert f.async_stats()["calls"] == calls
         if not self.broken:
             assert self.call(form) == 0, (form, self.message())

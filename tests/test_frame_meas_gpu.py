@@ -25,11 +25,10 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
+from support import SIZE, device_caster, r32
 from util import PLAIN_WINDOW_TOL, assert_parity, assert_window_parity, pixel_scene
 
 pytestmark = pytest.mark.gpu
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-SIZE = 0.28
 DT = np.array([0.005])
 
 
@@ -46,13 +45,6 @@ def _scene(B, M, dialect, n, seed):
     rot = r32(synth.q2R(nom[:, 6:10]).reshape(B, 9))
     prev = np.where(ids[:, 0] >= 0, ids[:, 0], 0).astype(np.int32)   # C++ dialect: the previously used marker is one in view
     return prm, nom, rot, r32(P), prev, ids, r32(left), r32(right)
-
-
-def _dev(torch, dtype):
-    dev = torch.device("cuda:0")
-    tt = torch.float32 if dtype == 32 else torch.float64
-    return lambda a: (torch.from_numpy(np.ascontiguousarray(a)).to(dev) if np.asarray(a).dtype.kind in "iu"
-                      else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev).to(tt))
 
 
 CASES = [("pixels", False, capi.MODE_STACKED), ("pixels", True, capi.MODE_STACKED),
@@ -93,7 +85,7 @@ def test_fused_frame_equals_the_per_call_sequence_and_the_oracle(dialect, n):
     skip = (np.arange(B) % 13 == 7).astype(np.uint8)
     acc, gyr = synth.imu_samples(0, B, 0, K, nom)
     acc, gyr = r32(acc), r32(gyr)
-    dd = _dev(torch, 32)
+    dd = device_caster(torch, 32)
     d = {"acc": dd(acc), "gyr": dd(gyr), "dt": dd(np.full(K, DT[0])), "ids": dd(ids), "left": dd(left), "right": dd(right),
          "skip": dd(skip)}
     vp = oc.vision_params()
@@ -156,7 +148,7 @@ def test_routes_that_do_not_take_the_fused_kernel():
     prm, nom, rot, P, prev, ids, left, right = _scene(B, M, 0, 18, seed=77)
     acc, gyr = synth.imu_samples(0, B, 0, K, nom)
     for dtype in (64, 32):
-        dd = _dev(torch, dtype)
+        dd = device_caster(torch, dtype)
         d = {"acc": dd(acc), "gyr": dd(gyr), "dt": dd(np.full(K, DT[0])), "ids": dd(ids), "left": dd(left), "right": dd(right), "skip": None}
         with BatchedFilter(B, prm, dtype=dtype) as fa, BatchedFilter(B, prm, dtype=dtype) as fb:
             fa.set_state(nom, rot, P, prev); fb.set_state(nom, rot, P, prev)
@@ -183,7 +175,7 @@ def test_rejected_calls_leave_the_state_alone(route):
     prm, nom, rot, P, prev, ids, left, right = _scene(B, M, 0, 18, seed=5)
     acc, gyr = synth.imu_samples(0, B, 0, K, nom)
     dtype = 64 if route == "fp64" else 32
-    dd = _dev(torch, dtype)
+    dd = device_caster(torch, dtype)
     with BatchedFilter(B, prm, dtype=dtype) as flt:
         if route == "resident":
             flt.set_team(1, 1)
@@ -223,7 +215,7 @@ def test_fused_frame_at_the_bench_size():
     prm.marker_size = 0.15
     nom, rot, ids, left, right = synth.pixel_wall_scene(B, M, prm, 0.15, seed=9, stereo=True)
     acc, gyr = synth.imu_samples(0, B, 0, K, nom)
-    dd = _dev(torch, 32)
+    dd = device_caster(torch, 32)
     d = {"acc": dd(acc), "gyr": dd(gyr), "dt": dd(np.full(K, DT[0])), "ids": dd(ids), "left": dd(left), "right": dd(right), "skip": None}
     out = {}
     for stereo in (False, True):
@@ -317,7 +309,7 @@ def test_window_of_frames_with_the_north_star_update(dialect, n, what, stereo, m
     ids[1, 5] = -1
     ids[2, 6, :] = 9
     skip = np.zeros((F, B), np.uint8); skip[2, 11] = 1; skip[3, 12] = 1; skip[0, 13] = 1
-    dd = _dev(torch, 32)
+    dd = device_caster(torch, 32)
     d_acc, d_gyr, d_dt = dd(acc), dd(gyr), dd(np.full(Kt, DT[0]))
     d_ids, d_left, d_right, d_skip = dd(ids), dd(left), dd(right), dd(skip)
     kind = capi.MEAS_PIXELS if what == "pixels" else capi.MEAS_CORNERS

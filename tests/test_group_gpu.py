@@ -11,6 +11,7 @@ import torch
 
 import group_ref
 from fbus_ekf import BatchedFilter, capi, noise, synth
+from support import r32, same_state
 from util import (COV_BLOCK_TOL, COV_BLOCK_TOL_F64, COV_TOL, F64_TOL, STATE_TOL, cov_rel_err, cov_rel_err_blockwise, state_rel_err,
                   state_rel_err_literal)
 
@@ -19,8 +20,6 @@ pytestmark = pytest.mark.gpu
 SHAPES = [(192, 2, 18), (192, 3, 18), (192, 8, 18), (192, 64, 18), (96, 3, 18), (96, 32, 18), (192, 3, 15), (192, 64, 15)]
 # one sigma of each error-state block p v theta ba bg g (a converged filter: sigma_theta = 1e-3 rad)
 SIGMA = np.repeat([1e-2, 2e-2, 1e-3, 5e-3, 1e-3, 5e-2], 3)
-
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
 
 
 def _inputs(B, G, N, seed=0):
@@ -190,10 +189,6 @@ def test_a_group_without_a_usable_member_reports_member_zero(B, G, N, dtype):
 
 # ---- 6. collapse ----------------------------------------------------------------------------------------------------------------------------
 
-def _same_state(a, b, rows=slice(None)):
-    return all(np.array_equal(x[rows], y[rows]) for x, y in zip(a, b))
-
-
 @pytest.mark.parametrize("dtype", [32, 64])
 @pytest.mark.parametrize("B,G,N", [(192, 3, 18), (192, 8, 18), (192, 64, 15), (96, 32, 18), (96, 3, 15)])
 def test_collapse_copies_the_source_record_bit_for_bit(B, G, N, dtype):
@@ -218,7 +213,7 @@ def test_collapse_copies_the_source_record_bit_for_bit(B, G, N, dtype):
                 for x in want:
                     x[members[j]] = x[members[j, s[j]]]
             assert len(hit) and len(hit) < NG
-            assert _same_state(after, want), f"{form}: collapsed groups / untouched groups"
+            assert same_state(after, want), f"{form}: collapsed groups / untouched groups"
             assert (after[3][members[hit]] == before[3][members[hit, s[hit]]][:, None]).all()          # prev_id travels with the record
             # one predict with the same IMU sample for every filter: the members of a collapsed group stay bit-equal
             acc = np.tile(np.array([0.1, -0.2, 9.7], f.np_dtype), (1, B, 1))
@@ -235,7 +230,7 @@ def test_collapse_copies_the_source_record_bit_for_bit(B, G, N, dtype):
         with pytest.raises(capi.FbusError) as e:
             f.group_collapse(G, src_dev)
         assert e.value.code == 1 and "src[" in str(e.value)
-        assert _same_state(f.get_state(), before)
+        assert same_state(f.get_state(), before)
 
 
 # ---- 7. with the handle's own sums ------------------------------------------------------------------------------------------------------------
@@ -298,7 +293,7 @@ def test_fuse_then_collapse_replays_from_a_graph(B, G, N, dtype):
                 before = f.get_state()
                 gid = f.graph_capture(run)
                 f.sync()
-                assert _same_state(f.get_state(), before) and not out[0].any()             # capture records, it does not execute
+                assert same_state(f.get_state(), before) and not out[0].any()             # capture records, it does not execute
                 f.graph_launch(gid)
             else:
                 run()
@@ -306,7 +301,7 @@ def test_fuse_then_collapse_replays_from_a_graph(B, G, N, dtype):
             got[how] = (_np(out), f.get_state())
     for x, y in zip(got["direct"][0], got["graph"][0]):
         assert np.array_equal(x, y)
-    assert _same_state(got["direct"][1], got["graph"][1])
+    assert same_state(got["direct"][1], got["graph"][1])
     best, after = got["graph"][0][1], got["graph"][1]
     assert best[0] == -1 and (best[1:] >= 0).all()
     members = np.arange(B).reshape(NG, G)
@@ -348,4 +343,4 @@ def test_bad_group_sizes_and_aliased_outputs_are_refused(dtype):
             args[k] = C.c_void_p(ptr + total - 8)
             assert lib.fbus_ekf_group_fuse_dev(h, 3, f._p(d_logw), *args) == 1, k
         f.sync()
-        assert _same_state(f.get_state(), before) and not d_w.any()
+        assert same_state(f.get_state(), before) and not d_w.any()

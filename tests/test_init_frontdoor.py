@@ -8,6 +8,7 @@ import pytest
 
 import oracle_capi as oc
 from fbus_ekf import capi, replay, synth
+from support import r32
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 
@@ -16,7 +17,6 @@ def _meas(B, M, dialect, seed=0):
     prm = capi.default_params(dialect)
     nom, rot, P, prev = synth.initial_state(seed, seed + B, list(prm.p0_diag), 18)
     ids, pos, quat = synth.marker_frame(seed, seed + B, 0, M, nom, prm)
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
     return prm, r32(nom), r32(rot), ids, r32(pos), r32(quat)
 
 
@@ -134,7 +134,6 @@ def test_gpu_gravity_bias_and_ema(dtype, tol):
     prm = capi.default_params(0)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), 18)
     acc, gyr = synth.imu_samples(0, B, 0, T, nom)
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
     acc, gyr = r32(acc), r32(gyr)
     with BatchedFilter(B, prm, dtype=dtype) as flt:
         flt.set_state(nom, rot, P, prev)
@@ -233,16 +232,16 @@ def test_cpp_host_mirror_runs_the_filter_thread_on_the_gpu(tmp_path):
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     B, M, dialect = 64, 3, 1
     prm = capi.default_params(dialect)
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32)
+    f32 = lambda a: np.asarray(a, np.float64).astype(np.float32)
     nom, rot, P, prev = synth.initial_state(40, 40 + B, list(prm.p0_diag), 18, mixed_cov=True)
-    nom, rot, P = r32(nom), r32(rot), r32(P)
+    nom, rot, P = f32(nom), f32(rot), f32(P)
     rng = np.random.default_rng(17)
     n_imu = 23
-    imu_a = r32(rng.normal(0, 0.3, (n_imu, 3)) + [0.1, 9.7, 0.2])
-    imu_w = r32(rng.normal(0, 0.02, (n_imu, 3)))
+    imu_a = f32(rng.normal(0, 0.3, (n_imu, 3)) + [0.1, 9.7, 0.2])
+    imu_w = f32(rng.normal(0, 0.02, (n_imu, 3)))
     ids, pos, quat = synth.marker_frame(40, 40 + B, 0, M, nom.astype(np.float64), prm)
     # one robot, B hypotheses: the front door hands every filter the same detections (those of filter 0)
-    ids0, pos0, quat0 = ids[0].astype(np.int32), r32(pos[0]), r32(quat[0])
+    ids0, pos0, quat0 = ids[0].astype(np.int32), f32(pos[0]), f32(quat[0])
     for name, arr in (("nom", nom), ("rot", rot), ("P", P), ("prev", prev.astype(np.int32)), ("imu_a", imu_a),
                       ("imu_w", imu_w), ("ids", ids0), ("pos", pos0), ("quat", quat0)):
         arr.tofile(tmp_path / f"{name}.bin")

@@ -11,7 +11,8 @@ import torch
 
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, gating, noise, replay, synth
-from test_nis_gpu import (J, SIZE, _aa2q, _call, _dev, _flt, _h, _meas, _pose_setup, _same, _scene, _setup, r32)
+from support import (J, SIZE, aa2q, make_filter, measured_rows, perturbed_setup, pose_setup, predicted_rows, r32, same_state, to_device,
+                     truth_scene, update_call)
 from util import assert_parity
 
 pytestmark = pytest.mark.gpu
@@ -24,8 +25,8 @@ GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def dense_pixels(nom, P, ids_b, left_b, right_b, prm, kind, r=None, eps=1e-6, vp=None):
     """(nis, log det S, rows, ln r) of one filter's pixel / corner rows; r: this filter's R (default: the parameters')"""
     vp = vp if vp is not None else oc.vision_params()
-    h0, vis = _h(nom, ids_b, prm, vp, kind)
-    y = _meas(ids_b, left_b, right_b, prm, kind)
+    h0, vis = predicted_rows(nom, ids_b, prm, vp, kind)
+    y = measured_rows(ids_b, left_b, right_b, prm, kind)
     H = np.zeros((len(h0), 6))
     for j in range(6):
         col = []
@@ -33,8 +34,8 @@ def dense_pixels(nom, P, ids_b, left_b, right_b, prm, kind, r=None, eps=1e-6, vp
             d = np.zeros(6); d[j] = s * eps
             x = nom.copy()
             x[0:3] += d[0:3]
-            x[6:10] = synth.qmul(nom[6:10][None], _aa2q(d[3:6])[None])[0]
-            col.append(_h(x, ids_b, prm, vp, kind)[0])
+            x[6:10] = synth.qmul(nom[6:10][None], aa2q(d[3:6])[None])[0]
+            col.append(predicted_rows(x, ids_b, prm, vp, kind)[0])
         H[:, j] = (col[0] - col[1]) / (2 * eps)
     H, res = H[vis], (y - h0)[vis]
     Rn = r if r is not None else (prm.r_pos if kind == "corners" else prm.r_pix)
@@ -85,15 +86,15 @@ def _sums(f):
 @pytest.mark.parametrize("kind", ["left", "stereo", "corners"])
 def test_pixel_and_corner_loglik_matches_the_dense_reference(kind, dtype):
     B, nstate = 4096, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
     skip = (np.arange(B) % 9 == 4).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
         with pytest.raises(capi.FbusError):
             f.loglik()                                  # before the first enable
         f.loglik_enable(True)
         f.loglik_reset()
         nom_p, _, P_p, _ = f.get_state()
-        nis, dof = _call(f, kind, ids, left, right, nis=True, skip=skip)
+        nis, dof = update_call(f, kind, ids, left, right, nis=True, skip=skip)
         applied = f.applied()
         ll, rows, app, rej = _sums(f)
         ll_d, rows_d, app_d, rej_d = f.loglik(device=True)
@@ -128,13 +129,13 @@ def test_pixel_and_corner_loglik_matches_the_dense_reference(kind, dtype):
 @pytest.mark.parametrize("mode", [capi.MODE_NEAREST, capi.MODE_STACKED])
 def test_pose_loglik_matches_the_dense_reference(mode, dialect, nstate, dtype, joseph):
     B = 4096
-    prm, nom, rot, P, prev, ids, pos, quat = _pose_setup(B, dtype, nstate, dialect, joseph)
+    prm, nom, rot, P, prev, ids, pos, quat = pose_setup(B, dtype, nstate, dialect, joseph)
     skip = (np.arange(B) % 9 == 4).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
         f.loglik_enable(True)
         f.loglik_reset()
         st0 = f.get_state()
-        nis, dof = _call(f, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
+        nis, dof = update_call(f, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
         app_u8 = f.applied()
         ll, rows, app, rej = _sums(f)
     assert np.array_equal(app, app_u8.astype(np.int32)) and np.all(rej == 0)
@@ -191,16 +192,16 @@ def _table(prm, B, col):
 @pytest.mark.parametrize("kind,mode,dialect,nstate", [("left", 1, 0, 18), ("stereo", 1, 1, 15), ("corners", 1, 0, 15),
                                                       ("corners", 0, 1, 18)])
 def test_pixel_and_corner_records_are_untouched(kind, mode, dialect, nstate, dtype, B, tabled):
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, dialect, kind)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, dialect, kind)
     skip = (np.arange(B) % 7 == 3).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
         if tabled:
             t = _table(prm, B, "r_pos" if kind == "corners" else "r_pix")
             a.set_noise(t); b.set_noise(t)
         b.loglik_enable(True)
-        na, da = _call(a, kind, ids, left, right, nis=True, mode=mode, skip=skip)
-        nb, db = _call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip)
-        assert _same(a.get_state(), b.get_state())
+        na, da = update_call(a, kind, ids, left, right, nis=True, mode=mode, skip=skip)
+        nb, db = update_call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip)
+        assert same_state(a.get_state(), b.get_state())
         assert np.array_equal(a.applied(), b.applied())
         assert np.array_equal(na, nb) and np.array_equal(da, db)
         ll, rows, app, rej = _sums(b)
@@ -221,15 +222,15 @@ POSE_ROUTES = [(nstate, joseph, B) for nstate in (18, 15) for joseph in (False, 
 @pytest.mark.parametrize("dialect", [0, 1])
 @pytest.mark.parametrize("mode", [capi.MODE_NEAREST, capi.MODE_STACKED])
 def test_pose_records_are_untouched(mode, dialect, dtype, nstate, joseph, B, tabled):
-    prm, nom, rot, P, prev, ids, pos, quat = _pose_setup(B, dtype, nstate, dialect, joseph)
+    prm, nom, rot, P, prev, ids, pos, quat = pose_setup(B, dtype, nstate, dialect, joseph)
     skip = (np.arange(B) % 9 == 4).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
         if tabled:
             t = _table(prm, B, "r_pos")
             a.set_noise(t); b.set_noise(t)
         b.loglik_enable(True)
-        na, da = _call(a, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
-        nb, db = _call(b, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
+        na, da = update_call(a, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
+        nb, db = update_call(b, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
         if dtype == 64 and dialect == 1 and mode == capi.MODE_STACKED and not tabled:
             # the stated exception (include/fbus_ekf.h): fp64 records, C++ dialect, stacked -- handle a runs the untabled kernel, b
             # the tabled one: covariance bit-equal, nominal state to the single-step gate
@@ -237,7 +238,7 @@ def test_pose_records_are_untouched(mode, dialect, dtype, nstate, joseph, B, tab
             assert np.array_equal(sa[2], sb[2]) and np.array_equal(sa[3], sb[3])
             assert_parity(sb, sa, 64, "pose _nis, accumulation on vs off, fp64 C++ stacked")
         else:
-            assert _same(a.get_state(), b.get_state())
+            assert same_state(a.get_state(), b.get_state())
         assert np.array_equal(a.applied(), b.applied())
         assert np.array_equal(na, nb) and np.array_equal(da, db)
 
@@ -249,21 +250,21 @@ def test_a_rejected_update_counts_as_rejected_and_nothing_else(kind):
     B, dtype, nstate = 4096, 32, 18
     bad = np.arange(B) % 8 == 5
     if kind == "pose":
-        prm, nom, rot, P, prev, ids, left, right = _pose_setup(B, dtype, nstate, 1, False)
+        prm, nom, rot, P, prev, ids, left, right = pose_setup(B, dtype, nstate, 1, False)
         left = left.copy()
         left[bad, 0, :] += 30 * math.sqrt(prm.r_pos)
     else:
-        prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+        prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
         left = left.copy()
         if kind == "left":
             left[bad, 0, 0:2] += 30 * math.sqrt(prm.r_pix)
         else:
             left[bad, 0, 0:3] += 30 * math.sqrt(prm.r_pos)
     thr = gating.chi2_gate(0.999)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as g:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as g:
         g.set_gate(thr)
         g.loglik_enable(True)
-        nis, dof = _call(g, kind, ids, left, right, nis=True)
+        nis, dof = update_call(g, kind, ids, left, right, nis=True)
         ag = g.applied()
         ll, rows, app, rej = _sums(g)
     rejected = (ag == 0) & (dof > 0)
@@ -280,22 +281,22 @@ def test_a_rejected_update_counts_as_rejected_and_nothing_else(kind):
 def test_accumulation_is_a_sum_and_enable_zero_freezes_it(kind, dtype):
     B, nstate = 4096, 18
     if kind == "pose":
-        prm, nom, rot, P, prev, ids, left, right = _pose_setup(B, dtype, nstate, 0, False)
+        prm, nom, rot, P, prev, ids, left, right = pose_setup(B, dtype, nstate, 0, False)
     else:
-        prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+        prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
     rng = np.random.default_rng(5)
     conv = r32 if dtype == 32 else (lambda a: a)
     sig = 1e-3 if kind == "pose" else 2e-4
     lefts = [left] + [conv(left + rng.normal(0, sig, left.shape)) for _ in range(2)]
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
         a.loglik_enable(True); b.loglik_enable(True)
         single = []
         for l in lefts:
-            _call(a, kind, ids, l, right, nis=True)
+            update_call(a, kind, ids, l, right, nis=True)
             b.loglik_reset()
-            _call(b, kind, ids, l, right, nis=True)
+            update_call(b, kind, ids, l, right, nis=True)
             single.append(_sums(b))
-            assert _same(a.get_state(), b.get_state())      # the twin is fed the same states
+            assert same_state(a.get_state(), b.get_state())      # the twin is fed the same states
         ll, rows, app, rej = _sums(a)
         assert np.array_equal(ll, (single[0][0] + single[1][0]) + single[2][0])
         assert np.array_equal(rows, single[0][1] + single[1][1] + single[2][1])
@@ -303,8 +304,8 @@ def test_accumulation_is_a_sum_and_enable_zero_freezes_it(kind, dtype):
         # enable(0): the sums stay while the records go on changing
         a.loglik_enable(False)
         before = a.get_state()
-        _call(a, kind, ids, lefts[1], right, nis=True)
-        assert not _same(a.get_state(), before)
+        update_call(a, kind, ids, lefts[1], right, nis=True)
+        assert not same_state(a.get_state(), before)
         assert all(np.array_equal(x, y) for x, y in zip(_sums(a), (ll, rows, app, rej)))
         a.loglik_reset()
         assert all(np.all(x == 0) for x in _sums(a))
@@ -319,16 +320,16 @@ def test_every_entry_point_feeds_the_same_sums(kind):
     twice.  With accumulation on all of them run predict_n + the per-call update: the sums are equal bit for bit."""
     B, dtype, nstate, F, K = 4096, 32, 18, 30, 2
     if kind == "pose":
-        prm, nom, rot, P, prev, ids, left, right = _pose_setup(B, dtype, nstate, 0, False)
+        prm, nom, rot, P, prev, ids, left, right = pose_setup(B, dtype, nstate, 0, False)
     else:
-        prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+        prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
     acc, gyr = synth.imu_samples(0, B, 0, K, nom)
     acc, gyr = r32(acc).astype(np.float32), r32(gyr).astype(np.float32)
     dt = np.full(K, 0.005, np.float32)
     ids32, l32 = np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(left, np.float32)
     q32 = np.ascontiguousarray(right, np.float32) if kind == "pose" else None
-    d_acc, d_gyr, d_dt, d_ids, d_l = _dev(acc), _dev(gyr), _dev(dt), _dev(ids32), _dev(l32)
-    d_q = _dev(q32) if kind == "pose" else None
+    d_acc, d_gyr, d_dt, d_ids, d_l = to_device(acc), to_device(gyr), to_device(dt), to_device(ids32), to_device(l32)
+    d_q = to_device(q32) if kind == "pose" else None
     rep = lambda t: t[None].expand(F, *t.shape).contiguous()
     w_acc, w_gyr, w_dt = d_acc.repeat(F, 1, 1), d_gyr.repeat(F, 1, 1), d_dt.repeat(F)
     kc = np.full(F, K, np.int32)
@@ -374,7 +375,7 @@ def test_every_entry_point_feeds_the_same_sums(kind):
     results = {}
     for name, door in (("per_call", per_call), ("host", host), ("fused", fused), ("window", lambda f: window(f, False)),
                        ("window_traj", lambda f: window(f, True)), ("graph", graph)):
-        with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+        with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
             before = f.launch_policy(M=4, K=K)
             f.loglik_enable(True)
             on = f.launch_policy(M=4, K=K)
@@ -388,7 +389,7 @@ def test_every_entry_point_feeds_the_same_sums(kind):
     ref_sums, ref_state = results["per_call"]
     assert np.all(ref_sums[2] == F) and np.all(ref_sums[3] == 0)
     for name, (sums, state) in results.items():
-        assert _same(state, ref_state), name
+        assert same_state(state, ref_state), name
         for x, y in zip(sums, ref_sums):
             assert np.array_equal(x, y), name
 
@@ -400,7 +401,7 @@ def _chi_square_scene(G, n=1024, seed=11):
     sigma_p 5 mm, sigma_theta 2.5 mrad), every scene repeated G times in a row: filter b runs hypothesis b % G on scene b // G"""
     prm = capi.default_params(0)
     prm.marker_size = SIZE
-    _, _, prev, truth, _, ids, left, right = _scene(n, 4, seed, 0.0)
+    _, _, prev, truth, _, ids, left, right = truth_scene(n, 4, seed, 0.0)
     rng = np.random.default_rng(seed + 1)
     sig = math.sqrt(prm.r_pix)
     left = left + rng.normal(0, sig, left.shape)
@@ -413,7 +414,7 @@ def _chi_square_scene(G, n=1024, seed=11):
     nom = truth.copy()
     nom[:, 0:3] -= dx[:, 0:3]
     for b in range(n):
-        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], _aa2q(-dx[b, 3:6])[None])[0]
+        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], aa2q(-dx[b, 3:6])[None])[0]
     rp = lambda a: np.repeat(a, G, axis=0)
     nom, ids, left, right, prev = rp(nom), rp(ids), rp(left), rp(right), rp(prev)
     rot = synth.q2R(nom[:, 6:10]).reshape(n * G, 9)
@@ -451,12 +452,12 @@ def test_the_sums_rank_noise_hypotheses(kind, dtype):
     assert np.array_equal(hyp, np.arange(B) % G) and hrows[3, 6] == prm.r_pix
     if dtype == 32:
         left, right = r32(left), r32(right)
-    with _flt(B, prm, dtype, 18, (nom, rot, P, prev)) as f:
+    with make_filter(B, prm, dtype, 18, (nom, rot, P, prev)) as f:
         f.set_noise(table)
         f.loglik_enable(True)
         f.loglik_reset()
         st = f.get_state()
-        _call(f, kind, ids, left, right, nis=True)
+        update_call(f, kind, ids, left, right, nis=True)
         ll, rows, app, rej = _sums(f)
     assert np.all(app == 1)
     g_best, total = noise.best(ll, hyp, G)

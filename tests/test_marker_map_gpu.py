@@ -31,8 +31,6 @@ The relabelling and padding tests are exact (np.array_equal): a lost piece of a 
 markers.  The parity tests hold every count to the fp64 oracle with the gates of tests/util.py, imported and not restated.
 M = 17 is refused by every form of the three updates with status 1 and unchanged records: tests/test_entry_forms_gpu.py asserts it.
 """
-import contextlib
-import os
 import types
 
 import numpy as np
@@ -41,6 +39,7 @@ import torch
 
 import marker_maps as mm
 import oracle_capi as oc
+import support
 from fbus_ekf import BatchedFilter, capi, noise
 from util import COV_BLOCK_TOL, COV_BLOCK_TOL_F64, COV_TOL, F64_TOL, PLAIN_TOL, STATE_TOL, assert_parity, parity_errors
 
@@ -52,21 +51,10 @@ KC = (2, 0, 1)                              # IMU samples in front of each frame
 
 
 # ---- handles and calls --------------------------------------------------------------------------------------------------------------------
-@contextlib.contextmanager
-def _env(env):
-    before = {k: os.environ.get(k) for k in env or {}}
-    os.environ.update(env or {})
-    try:
-        yield
-    finally:
-        for k, v in before.items():
-            os.environ.pop(k) if v is None else os.environ.__setitem__(k, v)
-
-
 def _handle(s, dtype=32, team=None, env=None, table=False, resident=False, state=None):
     """a handle on the scene's map and state; env: read once, at create; table: a per-filter noise table (five distinct rows,
     round-robin); resident: the policy batch above half a chip, where a tabled handle takes the resident window kernels"""
-    with _env(env):
+    with support.env(**(env or {})):
         f = BatchedFilter(s.B, s.prm, device=0, dtype=dtype, nstate=s.nstate)
     f.set_state(*(state or s.state))
     if team is not None:

@@ -9,62 +9,12 @@ import pytest
 import torch
 
 import oracle_capi as oc
-from fbus_ekf import BatchedFilter, capi, gating, synth
-from util import assert_parity, pixel_scene
+from fbus_ekf import capi, gating, synth
+from support import (J, SIZE, aa2q, make_filter, measured_rows, perturbed_setup, pose_setup, predicted_rows, r32, same_state, to_device,
+                     truth_scene, update_call, vp_tilted)
+from util import assert_parity
 
 pytestmark = pytest.mark.gpu
-SIZE = 0.28
-J = [0, 1, 2, 6, 7, 8]
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-def _aa2q(v):
-    th = np.linalg.norm(v)
-    if th == 0.0:
-        return np.array([1.0, 0.0, 0.0, 0.0])
-    return np.concatenate([[math.cos(th / 2)], math.sin(th / 2) * v / th])
-
-
-def _h(nom, ids_b, prm, vp, kind):
-    """predicted rows of one filter (marker slots in order, corners 0..3; pixels: left (+ right) per corner; corners: xyz) and
-    the visibility of each row"""
-    R_IL, P_IL, _ = synth.camera_constants(prm)
-    mids, mpos, mquat = synth.marker_table(prm)
-    c = np.array([[0, 0, 0], [0, SIZE, 0], [SIZE, SIZE, 0], [SIZE, 0, 0.0]])
-    R0 = synth.q2R(nom[6:10])
-    rows, vis = [], []
-    for mid in ids_b:
-        if mid < 0 or mid not in mids:
-            continue
-        k = list(mids).index(mid)
-        world = mpos[k] + (synth.q2R(mquat[k]) @ c.T).T
-        cam = (R_IL @ (R0.T @ (world - nom[0:3] - R0 @ P_IL).T)).T
-        if kind == "corners":
-            rows.append(cam.ravel()); vis += [True] * 12
-            continue
-        uvL, uvR, ok = oc.project_stereo(vp, cam, stereo=kind == "stereo")
-        for q in range(4):
-            rows.append(uvL[q]); vis += [ok[q]] * 2
-            if kind == "stereo":
-                rows.append(uvR[q]); vis += [ok[q]] * 2
-    return np.concatenate(rows), np.array(vis, bool)
-
-
-def _meas(ids_b, left_b, right_b, prm, kind):
-    mids = list(synth.marker_table(prm)[0])
-    y = []
-    for m, mid in enumerate(ids_b):
-        if mid < 0 or mid not in mids:
-            continue
-        if kind == "corners":
-            y.append(left_b[m]); continue
-        for q in range(4):
-            y.append(left_b[m, 2 * q:2 * q + 2])
-            if kind == "stereo":
-                y.append(right_b[m, 2 * q:2 * q + 2])
-    return np.concatenate(y)
-
-
 def nis_reference(nom, P, ids_b, left_b, right_b, prm, kind, eps=1e-6, vp=None, nearest=False):
     """(nis, dof) of one filter: r' (H P H' + R)^-1 r with H by central differences.  nearest (corner rows, Matlab dialect): the
     slot whose corner 0 is nearest (below 10 m) only"""
@@ -76,8 +26,8 @@ def nis_reference(nom, P, ids_b, left_b, right_b, prm, kind, eps=1e-6, vp=None, 
         if d[m0] < 10.0:
             keep[m0] = ids_b[m0]
         ids_b = keep
-    h0, vis = _h(nom, ids_b, prm, vp, kind)
-    y = _meas(ids_b, left_b, right_b, prm, kind)
+    h0, vis = predicted_rows(nom, ids_b, prm, vp, kind)
+    y = measured_rows(ids_b, left_b, right_b, prm, kind)
     H = np.zeros((len(h0), 6))
     for j in range(6):
         col = []
@@ -85,127 +35,13 @@ def nis_reference(nom, P, ids_b, left_b, right_b, prm, kind, eps=1e-6, vp=None, 
             d = np.zeros(6); d[j] = s * eps
             x = nom.copy()
             x[0:3] += d[0:3]
-            x[6:10] = synth.qmul(nom[6:10][None], _aa2q(d[3:6])[None])[0]
-            col.append(_h(x, ids_b, prm, vp, kind)[0])
+            x[6:10] = synth.qmul(nom[6:10][None], aa2q(d[3:6])[None])[0]
+            col.append(predicted_rows(x, ids_b, prm, vp, kind)[0])
         H[:, j] = (col[0] - col[1]) / (2 * eps)
     H, r = H[vis], (y - h0)[vis]
     Rn = prm.r_pos if kind == "corners" else prm.r_pix
     S = H @ P[np.ix_(J, J)] @ H.T + Rn * np.eye(len(r))
     return float(r @ np.linalg.solve(S, r)), len(r)
-
-
-_SCENES = {}
-
-
-def _scene(n, M, seed, noise):
-    key = (n, M, seed, noise)
-    if key not in _SCENES:
-        prm = capi.default_params(0)
-        prm.marker_size = SIZE
-        nom0, _, P, prev = synth.initial_state(0, n, list(prm.p0_diag), 18, mixed_cov=True)
-        _SCENES[key] = (nom0, P, prev) + tuple(pixel_scene(n, M, prm, SIZE, seed=seed, noise=noise, nominal=nom0))
-    return _SCENES[key]
-
-
-def _scene_tilted(n, M, seed, noise):
-    key = ("tilted", n, M, seed, noise)
-    if key not in _SCENES:
-        prm = capi.default_params(0)
-        prm.marker_size = SIZE
-        for i in range(3):
-            prm.port_normal[i] = float(TILT[i])
-        nom0, _, P, prev = synth.initial_state(0, n, list(prm.p0_diag), 18, mixed_cov=True)
-        _SCENES[key] = (nom0, P, prev) + tuple(pixel_scene(n, M, prm, SIZE, seed=seed, noise=noise, nominal=nom0, vision=_vp_tilted()))
-    return _SCENES[key]
-
-
-TILT = np.array([0.03, -0.02, 1.0]) / np.linalg.norm([0.03, -0.02, 1.0])
-
-
-def _vp_tilted():
-    vp = oc.vision_params()
-    for i in range(3):
-        vp.normal[i] = float(TILT[i])
-    return vp
-
-
-def _setup(B, dtype, nstate, dialect, kind, M=4, seed=3, n=256, tilted=False):
-    """B filters (a 256-filter scene tiled), perturbed by a few mm / mrad from the truth"""
-    prm = capi.default_params(dialect)
-    prm.marker_size = SIZE
-    if tilted:
-        for i in range(3):
-            prm.port_normal[i] = float(TILT[i])
-    nom0, P, prev, truth, _, ids, left, right = (_scene_tilted if tilted else _scene)(n, M, seed, 5e-4)
-    rep = (B + n - 1) // n
-    tile = lambda a: np.concatenate([a] * rep)[:B]
-    truth, P, prev, ids, left, right = map(tile, (truth, P, prev, ids, left, right))
-    rng = np.random.default_rng(seed + 1)
-    nom = truth.copy()
-    nom[:, 0:3] += rng.normal(0, 0.004, (B, 3))
-    nom[:, 6:10] = synth.qmul(nom[:, 6:10], np.concatenate([np.ones((B, 1)), rng.normal(0, 0.002, (B, 3))], axis=1))
-    nom[:, 6:10] /= np.linalg.norm(nom[:, 6:10], axis=1, keepdims=True)
-    P = P[:, :nstate, :nstate]
-    if kind == "corners":                             # triangulated corners: the true ones + 3 mm
-        R_IL, P_IL, _ = synth.camera_constants(prm)
-        left = np.zeros((B, M, 12))
-        for b in range(n):
-            h, _ = _h(truth[b], ids[b], prm, None, "corners")
-            left[b, :len(h) // 12] = h.reshape(-1, 12)
-        left = tile(left[:n]) + rng.normal(0, 0.003, left.shape)
-    if dtype == 32:
-        nom, P, left, right = r32(nom), r32(P), r32(left), r32(right)
-    rot = synth.q2R(nom[:, 6:10]).reshape(B, 9)
-    if dtype == 32:
-        rot = r32(rot)
-    return prm, nom, rot, P, prev, ids, left, right
-
-
-def _flt(B, prm, dtype, nstate, state, roles=0):
-    f = BatchedFilter(B, prm, device=0, dtype=dtype, nstate=nstate)
-    f.set_state(*state)
-    if roles:
-        f.set_team(0, roles)
-    return f
-
-
-def _dev(a, dt=None):
-    return torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
-
-
-def _call(f, kind, ids, left, right, nis=False, mode=capi.MODE_STACKED, skip=None, host=False):
-    """one update through the device entry points (host=True: the host-pointer ones, numpy in and out); kind "pose": left = pos,
-    right = quat"""
-    npd = f.np_dtype
-    conv = (lambda a, dt=None: None if a is None else np.ascontiguousarray(a, dt)) if host else (lambda a, dt=None: None if a is None else _dev(a, dt))
-    di, dl = conv(ids, np.int32), conv(left, npd)
-    dr = conv(right, npd) if kind in ("stereo", "pose") else None
-    ds = None if skip is None else conv(skip, np.uint8)
-    if kind == "pose":
-        out = (f.correct_nis if nis else f.correct)(di, dl, dr, mode, ds)
-    elif kind == "corners":
-        out = (f.correct_corners_nis if nis else f.correct_corners)(di, dl, None, capi.VIS_CORNERS3D, mode, ds)
-    else:
-        out = (f.correct_pixels_nis if nis else f.correct_pixels)(di, dl, dr, ds)
-    f.sync()
-    if nis:
-        if host:
-            return out[0].astype(np.float64), out[1]
-        return out[0].cpu().numpy().astype(np.float64), out[1].cpu().numpy()
-    return None
-
-
-def _same(a, b):
-    ok = all(np.array_equal(x, y) for x, y in zip(a, b))
-    if not ok:
-        for name, x, y in zip(("nominal", "rot", "P", "prev"), a, b):
-            x, y = np.asarray(x), np.asarray(y)
-            d = x.reshape(len(x), -1) != y.reshape(len(y), -1)
-            if d.any():
-                diff = np.abs(x.astype(np.float64) - y.astype(np.float64)).reshape(len(x), -1)
-                print(f"differs: {name} in {int(d.any(axis=1).sum())} filters, columns {np.nonzero(d.any(axis=0))[0][:12]}, "
-                      f"max |diff| {diff.max():.3e}")
-    return ok
 
 
 KINDS = ["left", "stereo", "corners"]
@@ -215,10 +51,10 @@ KINDS = ["left", "stereo", "corners"]
 @pytest.mark.parametrize("kind", KINDS)
 def test_nis_matches_the_reference_algebra(kind, dtype):
     B, nstate = 4096, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
         nom_p, _, P_p, _ = f.get_state()
-        nis, dof = _call(f, kind, ids, left, right, nis=True)
+        nis, dof = update_call(f, kind, ids, left, right, nis=True)
         applied = f.applied()
     worst = 0.0
     for b in range(256):
@@ -237,15 +73,15 @@ def test_nis_matches_the_reference_algebra(kind, dtype):
 def test_no_gate_is_the_twin_bit_for_bit(kind, mode, dialect, nstate, dtype, roles):
     """65 536 filters: the twin's own route is the one-wave kernel; 4096: the twin pinned to it (set_team(., 1))"""
     B = 65536 if roles == 0 else 4096
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, dialect, kind)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, dialect, kind)
     skip = (np.arange(B) % 7 == 3).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as b, \
-            _flt(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as c:
-        _call(a, kind, ids, left, right, mode=mode, skip=skip)
-        nis, dof = _call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip)
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as b, \
+            make_filter(B, prm, dtype, nstate, (nom, rot, P, prev), roles) as c:
+        update_call(a, kind, ids, left, right, mode=mode, skip=skip)
+        nis, dof = update_call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip)
         # NULL outputs
-        di, dl, ds = _dev(ids, np.int32), _dev(left, c.np_dtype), _dev(skip, np.uint8)       # (alive until the sync)
-        dr = _dev(right, c.np_dtype) if kind == "stereo" else None
+        di, dl, ds = to_device(ids, np.int32), to_device(left, c.np_dtype), to_device(skip, np.uint8)       # (alive until the sync)
+        dr = to_device(right, c.np_dtype) if kind == "stereo" else None
         torch.cuda.synchronize()
         if kind == "corners":
             rc = c._lib.fbus_ekf_correct_corners_nis_dev(c._h, ids.shape[1], c._p(di), c._p(dl), None, capi.VIS_CORNERS3D, mode,
@@ -256,7 +92,7 @@ def test_no_gate_is_the_twin_bit_for_bit(kind, mode, dialect, nstate, dtype, rol
         assert rc == 0
         sa, sb, sc = a.get_state(), b.get_state(), c.get_state()
         aa, ab, ac = a.applied(), b.applied(), c.applied()
-    assert _same(sa, sb) and _same(sa, sc)
+    assert same_state(sa, sb) and same_state(sa, sc)
     assert np.array_equal(aa, ab) and np.array_equal(aa, ac)
     assert np.all(dof[skip == 1] == 0) and np.all(nis[skip == 1] == 0)
     assert np.all((dof > 0) == (ab == 1))
@@ -270,7 +106,7 @@ def test_nis_is_chi_square_distributed(kind):
     B, M, n = 8192, 4, 1024
     prm = capi.default_params(0)
     prm.marker_size = SIZE
-    nom0, P0, prev, truth, _, ids, left, right = _scene(n, M, 11, 0.0)
+    nom0, P0, prev, truth, _, ids, left, right = truth_scene(n, M, 11, 0.0)
     rep = B // n
     truth, ids, left, right, prev = (np.concatenate([a] * rep) for a in (truth, ids, left, right, prev))
     rng = np.random.default_rng(12)
@@ -285,11 +121,11 @@ def test_nis_is_chi_square_distributed(kind):
     nom = truth.copy()
     nom[:, 0:3] -= dx[:, 0:3]
     for b in range(B):
-        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], _aa2q(-dx[b, 3:6])[None])[0]
+        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], aa2q(-dx[b, 3:6])[None])[0]
     rot = synth.q2R(nom[:, 6:10]).reshape(B, 9)
     for dtype in (32, 64):
-        with _flt(B, prm, dtype, 18, (nom, rot, np.broadcast_to(P, (B, 18, 18)).copy(), prev)) as f:
-            nis, dof = _call(f, kind, ids, r32(left) if dtype == 32 else left, r32(right) if dtype == 32 else right, nis=True)
+        with make_filter(B, prm, dtype, 18, (nom, rot, np.broadcast_to(P, (B, 18, 18)).copy(), prev)) as f:
+            nis, dof = update_call(f, kind, ids, r32(left) if dtype == 32 else left, r32(right) if dtype == 32 else right, nis=True)
         ok = dof > 0
         ratio = float(np.mean(nis[ok] / dof[ok]))
         thr = gating.chi2_gate(0.99, int(dof.max()))
@@ -303,7 +139,7 @@ def test_nis_is_chi_square_distributed(kind):
 @pytest.mark.parametrize("kind", ["left", "corners"])
 def test_the_gate_rejects_exactly_nis_above_its_threshold(kind, B):
     dtype, nstate = 32, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
     bad = np.arange(B) % 8 == 5
     left = left.copy()
     # one corner of slot 0 30 sigma off in every coordinate (a corner on a reflection; a rigid shift of all four would be taken
@@ -313,12 +149,12 @@ def test_the_gate_rejects_exactly_nis_above_its_threshold(kind, B):
     else:
         left[bad, 0, 0:3] += 30 * math.sqrt(prm.r_pos)
     thr = gating.chi2_gate(0.999)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as g, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as u:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as g, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as u:
         before = g.get_state()
         g.set_gate(thr)
-        nis, dof = _call(g, kind, ids, left, right, nis=True)
+        nis, dof = update_call(g, kind, ids, left, right, nis=True)
         after, ag = g.get_state(), g.applied()
-        _call(u, kind, ids, left, right, nis=True)
+        update_call(u, kind, ids, left, right, nis=True)
         ungated, au = u.get_state(), u.applied()
     rej = (ag == 0) & (dof > 0)
     assert np.array_equal(rej, (dof > 0) & (nis > thr[dof]))
@@ -333,8 +169,8 @@ def test_the_gate_rejects_exactly_nis_above_its_threshold(kind, B):
 
 def test_validation_and_graph_replay():
     B, dtype, nstate, kind = 4096, 32, 18, "left"
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
         before = f.get_state()
         with pytest.raises(capi.FbusError):
             f.set_gate([math.inf, 1.0, float("nan")])
@@ -344,12 +180,12 @@ def test_validation_and_graph_replay():
             f.set_gate(np.full(capi.GATE_MAX_DOF + 2, math.inf))
         f.set_gate(gating.chi2_gate(0.999, 31))         # M = 4, left camera: dof up to 32 -- one entry short
         with pytest.raises(capi.FbusError):
-            _call(f, kind, ids, left, right, nis=True)
+            update_call(f, kind, ids, left, right, nis=True)
         with pytest.raises(capi.FbusError):
-            _call(f, "corners", ids, np.zeros((B, 4, 12)), None, nis=True)     # corners stacked: up to 48
-        assert _same(f.get_state(), before)
+            update_call(f, "corners", ids, np.zeros((B, 4, 12)), None, nis=True)     # corners stacked: up to 48
+        assert same_state(f.get_state(), before)
         f.set_gate(gating.chi2_gate(0.999, 32))
-        di, dl = _dev(ids, np.int32), _dev(left, np.float32)
+        di, dl = to_device(ids, np.int32), to_device(left, np.float32)
         nis_d = torch.empty(B, dtype=torch.float32, device="cuda")
         dof_d = torch.empty(B, dtype=torch.int32, device="cuda")
         torch.cuda.synchronize()                        # (the raw calls below do not order against torch's stream)
@@ -367,7 +203,7 @@ def test_validation_and_graph_replay():
         f.set_state(*before)
         run()
         f.sync()
-        assert _same(f.get_state(), g_state) and np.array_equal(f.applied(), g_app)
+        assert same_state(f.get_state(), g_state) and np.array_equal(f.applied(), g_app)
         assert np.array_equal(nis_d.cpu().numpy(), g_nis) and np.array_equal(dof_d.cpu().numpy(), g_dof)
 
 
@@ -379,13 +215,13 @@ def test_tilted_port_nis_and_twin(kind, dtype):
     """the general-normal kernels (NZ = false; the left camera as CAM = 1 with the IMU-frame rows): NIS against the reference with
     the same normal, and no table == the twin's one-wave kernel bit for bit"""
     B, nstate = 4096, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind, tilted=True)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev), 1) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev), 1) as b:
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind, tilted=True)
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev), 1) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev), 1) as b:
         nom_p, _, P_p, _ = b.get_state()
-        _call(a, kind, ids, left, right)
-        nis, dof = _call(b, kind, ids, left, right, nis=True)
-        assert _same(a.get_state(), b.get_state()) and np.array_equal(a.applied(), b.applied())
-    vp = _vp_tilted()
+        update_call(a, kind, ids, left, right)
+        nis, dof = update_call(b, kind, ids, left, right, nis=True)
+        assert same_state(a.get_state(), b.get_state()) and np.array_equal(a.applied(), b.applied())
+    vp = vp_tilted()
     worst = 0.0
     for k in range(64):
         ref, rdof = nis_reference(nom_p[k].astype(np.float64), P_p[k].astype(np.float64), ids[k], left[k], right[k], prm, kind, vp=vp)
@@ -398,10 +234,10 @@ def test_tilted_port_nis_and_twin(kind, dtype):
 @pytest.mark.parametrize("dtype", [32, 64])
 def test_corner_nearest_nis_matches_the_reference(dtype):
     B, nstate = 4096, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, "corners")
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, "corners")
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as f:
         nom_p, _, P_p, _ = f.get_state()
-        nis, dof = _call(f, "corners", ids, left, right, nis=True, mode=capi.MODE_NEAREST)
+        nis, dof = update_call(f, "corners", ids, left, right, nis=True, mode=capi.MODE_NEAREST)
     worst = 0.0
     for k in range(128):
         ref, rdof = nis_reference(nom_p[k].astype(np.float64), P_p[k].astype(np.float64), ids[k], left[k], None, prm, "corners",
@@ -417,10 +253,10 @@ def test_small_launch_twin_agrees_to_the_single_step_gate(kind):
     """4096 filters with the default team choice: the twin divides the markers among several waves per tile (fp32 left: the split
     update), the _nis form runs one wave per tile -- the same update to rounding"""
     B, dtype, nstate = 4096, 32, 18
-    prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
-        _call(a, kind, ids, left, right)
-        _call(b, kind, ids, left, right, nis=True)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+        update_call(a, kind, ids, left, right)
+        update_call(b, kind, ids, left, right, nis=True)
         sa, sb = a.get_state(), b.get_state()
         assert np.array_equal(a.applied(), b.applied())
     e = assert_parity(sb, sa, dtype, f"_nis vs team twin, {kind}")
@@ -431,33 +267,22 @@ def test_small_launch_twin_agrees_to_the_single_step_gate(kind):
 def test_host_pointer_forms_equal_the_device_forms(kind):
     B, dtype, nstate = 4096, 32, 18
     if kind == "pose":
-        prm, nom, rot, P, prev, ids, left, right = _pose_setup(B, dtype, nstate, 1, False)
+        prm, nom, rot, P, prev, ids, left, right = pose_setup(B, dtype, nstate, 1, False)
     else:
-        prm, nom, rot, P, prev, ids, left, right = _setup(B, dtype, nstate, 0, kind)
+        prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, dtype, nstate, 0, kind)
     mode = capi.MODE_STACKED
     skip = (np.arange(B) % 5 == 1).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
         gate = gating.chi2_gate(0.999, 64)
         a.set_gate(gate); b.set_gate(gate)
-        nd, dd = _call(a, kind, ids, left, right, nis=True, mode=mode, skip=skip)
-        nh, dh = _call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip, host=True)
+        nd, dd = update_call(a, kind, ids, left, right, nis=True, mode=mode, skip=skip)
+        nh, dh = update_call(b, kind, ids, left, right, nis=True, mode=mode, skip=skip, host=True)
         assert isinstance(nh, np.ndarray) and dh.dtype == np.int32
         assert np.array_equal(nd, nh) and np.array_equal(dd, dh)
-        assert _same(a.get_state(), b.get_state()) and np.array_equal(a.applied(), b.applied())
+        assert same_state(a.get_state(), b.get_state()) and np.array_equal(a.applied(), b.applied())
 
 
 # ---- the pose rows ------------------------------------------------------------------------------------------------------------------
-
-def _pose_setup(B, dtype, nstate, dialect, joseph, M=4):
-    prm = capi.default_params(dialect)
-    if joseph:
-        prm.cov_form = capi.COV_JOSEPH
-    nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), nstate, mixed_cov=True)
-    ids, pos, quat = synth.marker_frame(0, B, 0, M, nom, prm)
-    if dtype == 32:
-        nom, rot, P, pos, quat = (r32(a) for a in (nom, rot, P, pos, quat))
-    return prm, nom, rot, P, prev, ids, pos, quat
-
 
 def pose_nis_reference(orc, nom, rot, P, ids_b, pos_b, quat_b, used_ids, prm):
     """r' (H P H' + R)^-1 r over the 7 rows of each used marker (the oracle's h, H, r: MeasureUpdate.m:67-88 / filter.cpp:684-721)"""
@@ -482,12 +307,12 @@ def pose_nis_reference(orc, nom, rot, P, ids_b, pos_b, quat_b, used_ids, prm):
 def test_pose_nis_matches_the_reference_and_the_twin(mode, dialect, nstate, dtype, joseph, B):
     if B == 65536 and (nstate != 18 or joseph):
         pytest.skip("the full-chip launch: N = 18, simple form")
-    prm, nom, rot, P, prev, ids, pos, quat = _pose_setup(B, dtype, nstate, dialect, joseph)
+    prm, nom, rot, P, prev, ids, pos, quat = pose_setup(B, dtype, nstate, dialect, joseph)
     skip = (np.arange(B) % 9 == 4).astype(np.uint8)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as a, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as b:
         st0 = b.get_state()
-        _call(a, "pose", ids, pos, quat, mode=mode, skip=skip)
-        nis, dof = _call(b, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
+        update_call(a, "pose", ids, pos, quat, mode=mode, skip=skip)
+        nis, dof = update_call(b, "pose", ids, pos, quat, nis=True, mode=mode, skip=skip)
         if dtype == 64 and dialect == 1 and mode == capi.MODE_STACKED:
             # the one route that is not bit-identical (include/fbus_ekf.h): fp64 records, C++ dialect, stacked -- the covariance is,
             # the nominal state differs in the last bits (<= 2e-15); held to the single-step gate
@@ -495,7 +320,7 @@ def test_pose_nis_matches_the_reference_and_the_twin(mode, dialect, nstate, dtyp
             assert np.array_equal(sa[2], sb[2]) and np.array_equal(sa[3], sb[3])
             assert_parity(sb, sa, 64, "pose _nis vs twin, fp64 C++ stacked")
         else:
-            assert _same(a.get_state(), b.get_state())
+            assert same_state(a.get_state(), b.get_state())
         assert np.array_equal(a.applied(), b.applied())
         app = b.applied()
     n = 256
@@ -533,17 +358,17 @@ def test_pose_nis_matches_the_reference_and_the_twin(mode, dialect, nstate, dtyp
 @pytest.mark.parametrize("B", [4096, 65536])
 def test_pose_gate_rejects_exactly_nis_above_its_threshold(B):
     dtype, nstate = 32, 18
-    prm, nom, rot, P, prev, ids, pos, quat = _pose_setup(B, dtype, nstate, 1, False)
+    prm, nom, rot, P, prev, ids, pos, quat = pose_setup(B, dtype, nstate, 1, False)
     bad = np.arange(B) % 8 == 5
     pos = pos.copy()
     pos[bad, 0, :] += 30 * math.sqrt(prm.r_pos)          # one marker's position 30 sigma off
     thr = gating.chi2_gate(0.999)
-    with _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as g, _flt(B, prm, dtype, nstate, (nom, rot, P, prev)) as u:
+    with make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as g, make_filter(B, prm, dtype, nstate, (nom, rot, P, prev)) as u:
         before = g.get_state()
         g.set_gate(thr)
-        nis, dof = _call(g, "pose", ids, pos, quat, nis=True)
+        nis, dof = update_call(g, "pose", ids, pos, quat, nis=True)
         after, ag = g.get_state(), g.applied()
-        _call(u, "pose", ids, pos, quat, nis=True)
+        update_call(u, "pose", ids, pos, quat, nis=True)
         ungated, au = u.get_state(), u.applied()
     rej = (ag == 0) & (dof > 0)
     assert np.array_equal(rej, (dof > 0) & (nis > thr[dof]))

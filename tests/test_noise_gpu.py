@@ -11,102 +11,17 @@ import pytest
 import torch
 
 from fbus_ekf import BatchedFilter, capi, gating, noise, replay, synth
-from test_nis_gpu import J, SIZE, _aa2q, _call, _dev, _same, _scene, _setup, r32
+from support import (B_ODD, G, J, SIZE, aa2q, assert_twin, imu, perturbed_setup, r32, rows_of, run_twins, same_state, state_of,
+                     to_device, truth_scene, update_call, with_row)
 from util import state_rel_err, state_rel_err_literal
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-G = 5
-B_ODD = 4160 + 37                              # a partial last tile
-FACT = np.array([0.1, 0.3, 1.0, 3.0, 10.0])
-
-
-def rows_of(prm):
-    """G rows, column c of row g = default x FACT[(g + 2c) % G]: every row differs from every other in every column"""
-    base = noise.row_of(prm)
-    return np.array([[base[c] * FACT[(g + 2 * c) % G] for c in range(7)] for g in range(G)])
-
-
-def with_row(prm, row):
-    p = capi.FbusParams.from_buffer_copy(prm)
-    for i in range(4):
-        p.q_diag[i] = float(row[i])
-    p.r_pos, p.r_quat, p.r_pix = float(row[4]), float(row[5]), float(row[6])
-    return p
-
-
-def handle(B, prm, dtype, nstate, state, pin=True, policy_batch=0):
-    f = BatchedFilter(B, prm, device=0, dtype=dtype, nstate=nstate)
-    f.set_state(*state)
-    if pin:
-        f.set_team(1, 1)                       # the one-wave forms (what a tabled handle runs)
-    if policy_batch:
-        f.set_policy_batch(policy_batch)
-    return f
-
-
 def pose_inputs(B, M, nom, prm, dtype):
     ids, pos, quat = synth.marker_frame(0, B, 0, M, nom, prm)
     if dtype == 32:
         pos, quat = r32(pos), r32(quat)
     return ids, pos, quat
-
-
-def run_twins(B, prm, dtype, nstate, state, step, pin=True, policy_batch=0):
-    """step(handle) on a tabled handle and on G twins; returns the tabled handle's outputs and, per filter, the twin's"""
-    rows = rows_of(prm)
-    g = np.arange(B) % G
-    with handle(B, prm, dtype, nstate, state, pin, policy_batch) as f:
-        f.set_noise(rows[g])
-        out = step(f)
-        st = f.get_state()
-        app = f.applied()
-    ref_out, ref_st, ref_app = None, None, None
-    for k in range(G):
-        with handle(B, with_row(prm, rows[k]), dtype, nstate, state, pin, policy_batch) as t:
-            o = step(t)
-            s = t.get_state()
-            a = t.applied()
-        sel = g == k
-        if ref_st is None:
-            ref_st = [np.array(x) for x in s]
-            ref_app = np.array(a)
-            ref_out = None if o is None else [np.array(x) for x in o]
-        for x, y in zip(ref_st, s):
-            x[sel] = y[sel]
-        ref_app[sel] = a[sel]
-        if o is not None:
-            for x, y in zip(ref_out, o):
-                x[sel] = y[sel]
-    return (st, app, out), (ref_st, ref_app, ref_out)
-
-
-def assert_twin(got, ref, near_nominal=False):
-    (st, app, out), (rst, rapp, rout) = got, ref
-    if near_nominal:                            # fp64 C++-dialect stacked pose through the NIS kernel (include/fbus_ekf.h)
-        np.testing.assert_allclose(st[0], rst[0], rtol=0, atol=2e-15)
-        assert all(np.array_equal(x, y) for x, y in zip(st[1:], rst[1:]))
-    else:
-        assert _same(st, rst)
-    assert np.array_equal(app, rapp)
-    if out is not None:
-        assert all(np.array_equal(x, y) for x, y in zip(out, rout))
-
-
-def state_of(B, dtype, nstate, dialect):
-    prm = capi.default_params(dialect)
-    nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), nstate, mixed_cov=True)
-    if dtype == 32:
-        nom, rot, P = r32(nom), r32(rot), r32(P)
-    return prm, (nom, rot, P, prev)
-
-
-def imu(B, K, nom, dtype):
-    a, w = synth.imu_samples(0, B, 0, K, nom)
-    dt = np.full(K, 0.005)
-    if dtype == 32:
-        a, w, dt = r32(a), r32(w), r32(dt)
-    return a, w, dt
 
 
 # ---- 1. twin bit-equality, every per-call route -------------------------------------------------------------------------------
@@ -156,9 +71,9 @@ def test_pose_correct_equals_its_twins(dialect, nstate, mode, joseph, dtype, nis
 @pytest.mark.parametrize("kind,mode,dialect,nstate", [("left", 1, 0, 18), ("stereo", 1, 1, 15), ("corners", 1, 0, 15),
                                                       ("corners", 0, 1, 18)])
 def test_meas_updates_equal_their_twins(kind, mode, dialect, nstate, dtype, nis):
-    prm, nom, rot, P, prev, ids, left, right = _setup(B_ODD, dtype, nstate, dialect, kind)
+    prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B_ODD, dtype, nstate, dialect, kind)
     skip = (np.arange(B_ODD) % 7 == 3).astype(np.uint8)
-    step = lambda f: _call(f, kind, ids, left, right, nis=nis, mode=mode, skip=skip)
+    step = lambda f: update_call(f, kind, ids, left, right, nis=nis, mode=mode, skip=skip)
     assert_twin(*run_twins(B_ODD, prm, dtype, nstate, (nom, rot, P, prev), step))
 
 
@@ -170,8 +85,8 @@ def test_identity_table_changes_nothing(dtype):
     prm, state = state_of(B, dtype, nstate, dialect)
     a, w, dt = imu(B, 7, state[0], dtype)
     ids, pos, quat = pose_inputs(B, 4, state[0], prm, dtype)
-    _, pnom, prot, pP, pprev, pids, pleft, pright = _setup(B, dtype, nstate, dialect, "stereo")
-    _, cnom, crot, cP, cprev, cids, cleft, cright = _setup(B, dtype, nstate, dialect, "corners")
+    _, pnom, prot, pP, pprev, pids, pleft, pright = perturbed_setup(B, dtype, nstate, dialect, "stereo")
+    _, cnom, crot, cP, cprev, cids, cleft, cright = perturbed_setup(B, dtype, nstate, dialect, "corners")
 
     def run(f):
         f.predict(a[0], w[0], dt[:1])
@@ -180,12 +95,12 @@ def test_identity_table_changes_nothing(dtype):
         f.correct(ids, pos, quat, capi.MODE_NEAREST)
         out = [f.get_state()]
         f.set_state(pnom, prot, pP, pprev)
-        _call(f, "left", pids, pleft, pright)
-        _call(f, "stereo", pids, pleft, pright)
+        update_call(f, "left", pids, pleft, pright)
+        update_call(f, "stereo", pids, pleft, pright)
         out.append(f.get_state())
         f.set_state(cnom, crot, cP, cprev)
-        _call(f, "corners", cids, cleft, cright, mode=capi.MODE_STACKED)
-        _call(f, "corners", cids, cleft, cright, mode=capi.MODE_NEAREST)
+        update_call(f, "corners", cids, cleft, cright, mode=capi.MODE_STACKED)
+        update_call(f, "corners", cids, cleft, cright, mode=capi.MODE_NEAREST)
         out.append(f.get_state())
         return out
 
@@ -198,7 +113,7 @@ def test_identity_table_changes_nothing(dtype):
         np.testing.assert_array_equal(f1.get_noise(), noise.from_params(prm, B))
         got = run(f1)
     for x, y in zip(got, ref):
-        assert _same(x, y)
+        assert same_state(x, y)
     # set_noise(None): back to the existing kernels (a handle never given a table)
     with BatchedFilter(B_ODD, prm, dtype=dtype, nstate=nstate) as f2, BatchedFilter(B_ODD, prm, dtype=dtype, nstate=nstate) as f3:
         _, st = state_of(B_ODD, dtype, nstate, dialect)
@@ -213,7 +128,7 @@ def test_identity_table_changes_nothing(dtype):
         for f in (f2, f3):
             f.predict_n(a2, w2, dt2)
             f.correct(i2, p2, q2, capi.MODE_STACKED)
-        assert _same(f2.get_state(), f3.get_state())
+        assert same_state(f2.get_state(), f3.get_state())
 
 
 # ---- 3. oracle parity per row ---------------------------------------------------------------------------------------------------
@@ -265,7 +180,7 @@ def test_windows_equal_their_frames(dtype):
     quat = np.zeros((F, B, M, 4))
     for f in range(F):
         ids[f], pos[f], quat[f] = pose_inputs(B, M, state[0], prm, dtype)
-    _, pnom, prot, pP, pprev, pids, pleft, pright = _setup(B, dtype, nstate, 0, "left")
+    _, pnom, prot, pP, pprev, pids, pleft, pright = perturbed_setup(B, dtype, nstate, 0, "left")
     pix_ids = np.stack([pids] * F)
     pix_left = np.stack([pleft] * F)
     dtt = np.tile(dt[:K], F)
@@ -274,8 +189,8 @@ def test_windows_equal_their_frames(dtype):
             h.set_state(*state)
             h.set_noise(rows)
         npd = win.np_dtype
-        traj = win.frames(kc, _dev(a, npd), _dev(w, npd), _dev(dtt, npd), _dev(ids, np.int32), _dev(pos, npd), _dev(quat, npd),
-                          capi.MODE_STACKED, record=True)
+        traj = win.frames(kc, to_device(a, npd), to_device(w, npd), to_device(dtt, npd), to_device(ids, np.int32), to_device(pos, npd),
+                          to_device(quat, npd), capi.MODE_STACKED, record=True)
         torch.cuda.synchronize()
         traj = [t.cpu().numpy() for t in traj]
         snaps = []
@@ -284,21 +199,22 @@ def test_windows_equal_their_frames(dtype):
             one.correct(ids[f], pos[f], quat[f], capi.MODE_STACKED)
             one.sync()
             snaps.append([t.cpu().numpy() for t in one.snapshot()])
-        assert _same(win.get_state(), one.get_state())
+        assert same_state(win.get_state(), one.get_state())
         for f in range(F):
             for x, y in zip(traj, snaps[f]):
                 assert np.array_equal(x[f], y)
         for h in (win, one):
             h.set_state(pnom, prot, pP, pprev)
-        traj = win.frames_meas(kc, _dev(a, npd), _dev(w, npd), _dev(dtt, npd), _dev(pix_ids, np.int32), _dev(pix_left, npd), record=True)
+        traj = win.frames_meas(kc, to_device(a, npd), to_device(w, npd), to_device(dtt, npd), to_device(pix_ids, np.int32),
+                               to_device(pix_left, npd), record=True)
         torch.cuda.synchronize()
         traj = [t.cpu().numpy() for t in traj]
         snaps = []
         for f in range(F):
             one.predict_n(a[f * K:(f + 1) * K], w[f * K:(f + 1) * K], dt[:K])
-            _call(one, "left", pids, pleft, None)
+            update_call(one, "left", pids, pleft, None)
             snaps.append([t.cpu().numpy() for t in one.snapshot()])
-        assert _same(win.get_state(), one.get_state())
+        assert same_state(win.get_state(), one.get_state())
         for f in range(F):
             for x, y in zip(traj, snaps[f]):
                 assert np.array_equal(x[f], y)
@@ -344,7 +260,7 @@ def test_nis_tracks_r():
     B, M, n = 3 * 8192, 4, 1024
     prm = capi.default_params(0)
     prm.marker_size = SIZE
-    nom0, P0, prev, truth, _, ids, left, right = _scene(n, M, 11, 0.0)
+    nom0, P0, prev, truth, _, ids, left, right = truth_scene(n, M, 11, 0.0)
     rep = B // n
     truth, ids, left, right, prev = (np.concatenate([a] * rep) for a in (truth, ids, left, right, prev))
     rng = np.random.default_rng(12)
@@ -358,7 +274,7 @@ def test_nis_tracks_r():
     nom = truth.copy()
     nom[:, 0:3] -= dx[:, 0:3]
     for b in range(B):
-        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], _aa2q(-dx[b, 3:6])[None])[0]
+        nom[b, 6:10] = synth.qmul(truth[b, 6:10][None], aa2q(-dx[b, 3:6])[None])[0]
     rot = synth.q2R(nom[:, 6:10]).reshape(B, 9)
     scale = np.array([0.25, 1.0, 4.0])
     g = np.arange(B) % 3
@@ -367,7 +283,7 @@ def test_nis_tracks_r():
     with BatchedFilter(B, prm, dtype=64, nstate=18) as f:
         f.set_state(nom, rot, np.broadcast_to(P, (B, 18, 18)).copy(), prev)
         f.set_noise(table)
-        nis, dof = _call(f, "left", ids, left, None, nis=True)
+        nis, dof = update_call(f, "left", ids, left, None, nis=True)
     means = []
     for k in range(3):
         ok = (dof > 0) & (g == k)
@@ -389,8 +305,8 @@ def test_graph_replay_sees_rewritten_values():
     rows = rows_of(prm)
     a, w, dt = imu(B, 1, state[0], dtype)
     ids, pos, quat = pose_inputs(B, 4, state[0], prm, dtype)
-    da, dw, ddt = _dev(a[0], np.float32), _dev(w[0], np.float32), _dev(dt[:1], np.float32)
-    di, dp, dq = _dev(ids, np.int32), _dev(pos, np.float32), _dev(quat, np.float32)
+    da, dw, ddt = to_device(a[0], np.float32), to_device(w[0], np.float32), to_device(dt[:1], np.float32)
+    di, dp, dq = to_device(ids, np.int32), to_device(pos, np.float32), to_device(quat, np.float32)
     torch.cuda.synchronize()
 
     def step(f):
@@ -409,14 +325,14 @@ def test_graph_replay_sees_rewritten_values():
         ref.set_noise(t1)
         step(ref)
         ref.sync()
-        assert _same(gph.get_state(), ref.get_state())
+        assert same_state(gph.get_state(), ref.get_state())
         gph.set_noise(t2)                      # rewritten in place: the graph reads the new values
         ref.set_noise(t2)
         gph.graph_launch(gid)
         gph.sync()
         step(ref)
         ref.sync()
-        assert _same(gph.get_state(), ref.get_state())
+        assert same_state(gph.get_state(), ref.get_state())
 
 
 def test_validation_and_routes():

@@ -21,8 +21,8 @@ import pytest
 import torch
 
 from fbus_ekf import BatchedFilter, capi, noise, replay, synth
-from test_nis_gpu import _dev, _same, _setup, r32
-from test_noise_gpu import B_ODD, G, assert_twin, handle, imu, rows_of, run_twins, state_of, with_row
+from support import (B_ODD, G, assert_twin, handle, imu, perturbed_setup, r32, rows_of, run_twins, same_state, state_of, to_device,
+                     with_row)
 from util import state_rel_err_literal
 
 pytestmark = pytest.mark.gpu
@@ -63,9 +63,9 @@ class PoseWindow:
         for f in range(F):
             ids[f], pos[f], quat[f] = synth.marker_frame(0, B, f, M, nom, prm)
         ids[1, 5] = -1                          # a filter without a marker in one frame
-        self.a, self.w, self.dt = _dev(a, F32), _dev(w, F32), _dev(dt, F32)
-        self.ids, self.pos, self.quat = _dev(ids, np.int32), _dev(pos, F32), _dev(quat, F32)
-        self.skip = _dev(skip_mask(B), np.uint8)
+        self.a, self.w, self.dt = to_device(a, F32), to_device(w, F32), to_device(dt, F32)
+        self.ids, self.pos, self.quat = to_device(ids, np.int32), to_device(pos, F32), to_device(quat, F32)
+        self.skip = to_device(skip_mask(B), np.uint8)
         torch.cuda.synchronize()
 
     def launch(self, f, mode, record=False):
@@ -100,7 +100,7 @@ class MeasWindow:
 
     def __init__(self, B, nstate, dialect, kind, tilted=False):
         self.kind = kind
-        self.prm, nom, rot, P, prev, ids, left, right = _setup(B, 32, nstate, dialect, kind, tilted=tilted)
+        self.prm, nom, rot, P, prev, ids, left, right = perturbed_setup(B, 32, nstate, dialect, kind, tilted=tilted)
         self.state = (nom, rot, P, prev)
         rng = np.random.default_rng(77)
         sd = 2e-4
@@ -110,10 +110,10 @@ class MeasWindow:
         idsF[min(2, F - 1), 6, :] = 9           # ids the map does not hold
         leftF = r32(np.stack([left] * F) + rng.normal(0, sd, (F,) + left.shape))
         rightF = r32(np.stack([right] * F) + rng.normal(0, sd, (F,) + right.shape))
-        self.a, self.w, self.dt = _dev(a, F32), _dev(w, F32), _dev(dt, F32)
-        self.ids, self.left = _dev(idsF, np.int32), _dev(leftF, F32)
-        self.right = _dev(rightF, F32) if kind == "stereo" else None
-        self.skip = _dev(skip_mask(B), np.uint8)
+        self.a, self.w, self.dt = to_device(a, F32), to_device(w, F32), to_device(dt, F32)
+        self.ids, self.left = to_device(idsF, np.int32), to_device(leftF, F32)
+        self.right = to_device(rightF, F32) if kind == "stereo" else None
+        self.skip = to_device(skip_mask(B), np.uint8)
         self.mk = capi.MEAS_CORNERS if kind == "corners" else capi.MEAS_PIXELS
         self.geo = capi.VIS_CORNERS3D if kind == "corners" else capi.VIS_REFRACTIVE
         torch.cuda.synchronize()
@@ -158,7 +158,7 @@ def tabled(B, prm, nstate, state, policy_batch, dtype=32):
 
 
 def same_handles(x, y):
-    return _same(x.get_state(), y.get_state()) and np.array_equal(x.applied(), y.applied())
+    return same_state(x.get_state() + (x.applied(),), y.get_state() + (y.applied(),))
 
 
 # ---- 1. twins -------------------------------------------------------------------------------------------------------------------
@@ -380,7 +380,7 @@ def test_sweep_on_the_recording_equals_its_twins():
             ref = twin.get_state()
             ref_app = twin.applied()
         sel = g == k
-        assert _same([x[sel] for x in got], [x[sel] for x in ref]), f"row {k}"
+        assert same_state([x[sel] for x in got], [x[sel] for x in ref]), f"row {k}"
         assert np.array_equal(got_app[sel], ref_app[sel])
         ends.append(ref[0][0].astype(np.float64))
     spread = min(state_rel_err_literal(ends[i][None], ends[j][None]) for i in range(G) for j in range(G) if i != j)

@@ -15,9 +15,9 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import capi, synth
 from replay_ref import OracleEngine
+from support import SIZE
 from util import parity_errors, pixel_scene
 
-SIZE = 0.28
 
 
 def _proj(lib, vp, X, which):

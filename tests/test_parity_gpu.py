@@ -13,42 +13,13 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, replay, synth
 from replay_ref import OracleEngine
+from support import DT, imu_of, markers_of, params_of, r32, state_batch
 from util import (COV_BLOCK_TOL, COV_TOL, PLAIN_TOL, PLAIN_WINDOW_TOL, STATE_TOL, WINDOW_TOL, assert_parity, assert_window_parity, cov_rel_err,
                   cov_rel_err_blockwise, parity_errors, rot_rel_err, state_rel_err, state_rel_err_literal,
                   state_rel_err_plain)
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DT = np.array([np.float64(np.float32(0.005))])
-
-
-def _params(dialect, cov_form=0):
-    p = capi.default_params(dialect)
-    p.cov_form = cov_form
-    return p
-
-
-def _r32(a):
-    """round to fp32-representable values so the GPU (fp32) and the oracle (fp64) see IDENTICAL inputs."""
-    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-def _batch(B, dialect, n, mixed=True, seed_off=0):
-    prm = _params(dialect)
-    nom, rot, P, prev = synth.initial_state(seed_off, seed_off + B, list(prm.p0_diag), n, mixed_cov=mixed)
-    return prm, _r32(nom), _r32(rot), _r32(P), prev
-
-
-def _imu(lo, hi, step, K, nom):
-    a, g = synth.imu_samples(lo, hi, step, K, nom)
-    return _r32(a), _r32(g)
-
-
-def _markers(lo, hi, frame, M, nom, prm):
-    ids, pos, quat = synth.marker_frame(lo, hi, frame, M, nom, prm)
-    return ids, _r32(pos), _r32(quat)
-
-
 def _check(flt, eng, dtype, what, state_tol=STATE_TOL, cov_tol=COV_TOL, plain_tol=PLAIN_TOL, cov_block_tol=COV_BLOCK_TOL):
     """the parity gate of tests/util.py (literal, sigma-aware and plain per-block state error, rotation, max-norm and
     block-wise covariance error, symmetry, marker id) between the device state and the oracle's"""
@@ -63,9 +34,9 @@ def _check(flt, eng, dtype, what, state_tol=STATE_TOL, cov_tol=COV_TOL, plain_to
 def test_predict_single_step(dialect, n, dtype):
     B = 320                                   # five waves, last tile partial on purpose below
     B -= 7
-    prm, nom, rot, P, prev = _batch(B, dialect, n)
-    acc, gyr = _imu(0, B, 0, 1, nom)
-    dt = _r32(np.random.default_rng(3).uniform(0.001, 0.01, B))
+    prm, nom, rot, P, prev = state_batch(B, dialect, n)
+    acc, gyr = imu_of(0, B, 0, 1, nom)
+    dt = r32(np.random.default_rng(3).uniform(0.001, 0.01, B))
     with BatchedFilter(B, prm, dtype=dtype, nstate=n) as flt:
         eng = OracleEngine(B, dialect, n)
         flt.set_state(nom, rot, P, prev)
@@ -84,13 +55,13 @@ def test_predict_large_rotation_increments(dialect):
     """rotation increments on both sides of the 0.5 rad switch between the polynomial and the library sin/cos
     (|w| dt / 2 from 0.05 to 1.5 rad: fast tumbling / long gaps between IMU samples), mixed inside one wave"""
     B = 256
-    prm, nom, rot, P, prev = _batch(B, dialect, 18)
-    acc, gyr = _imu(0, B, 0, 1, nom)
+    prm, nom, rot, P, prev = state_batch(B, dialect, 18)
+    acc, gyr = imu_of(0, B, 0, 1, nom)
     rng = np.random.default_rng(5)
     axis = rng.normal(size=(B, 3)); axis /= np.linalg.norm(axis, axis=1, keepdims=True)
     half_angle = rng.uniform(0.05, 1.5, B)
-    dt = _r32(rng.uniform(0.02, 0.2, B))
-    gyr0 = _r32(axis * (2 * half_angle / dt)[:, None] + nom[:, 13:16])
+    dt = r32(rng.uniform(0.02, 0.2, B))
+    gyr0 = r32(axis * (2 * half_angle / dt)[:, None] + nom[:, 13:16])
     with BatchedFilter(B, prm) as flt:
         eng = OracleEngine(B, dialect, 18)
         flt.set_state(nom, rot, P, prev)
@@ -106,10 +77,10 @@ def test_predict_large_rotation_increments(dialect):
 @pytest.mark.parametrize("dialect", [0, 1])
 def test_correct_single_step(dialect, mode, n, dtype):
     B, M = 256, 4
-    prm, nom, rot, P, prev = _batch(B, dialect, n)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     rng = np.random.default_rng(5)
-    pos = _r32(pos + rng.normal(0, 0.02, pos.shape))      # non-trivial innovations
+    pos = r32(pos + rng.normal(0, 0.02, pos.shape))      # non-trivial innovations
     ids[0] = -1                                           # nothing visible
     ids[1] = [9, -1, 9, -1]                               # only an id outside the map
     ids[2, 1] = -1
@@ -133,7 +104,7 @@ def test_golden_vectors(dialect):
     for n in (18, 15):
         t = f"d{dialect}_n{n}"
         B = g[t + "_nom"].shape[0]
-        with BatchedFilter(B, _params(dialect), dtype=32, nstate=n) as flt:
+        with BatchedFilter(B, params_of(dialect), dtype=32, nstate=n) as flt:
             flt.set_state(g[t + "_nom"], g[t + "_rot"], g[t + "_P"], g[t + "_prev"])
             flt.predict(g[t + "_acc"], g[t + "_gyr"], g[t + "_dt"])
             nom, rot, P, _ = flt.get_state()
@@ -160,7 +131,7 @@ def test_golden_vectors(dialect):
 def test_free_running_100_frames(dialect):
     """200 Hz IMU + 30 Hz stereo pattern (7,7,6 predicts per correct), M = 4, 100 frames."""
     B, M, n = 128, 4, 18
-    prm, nom, rot, P, prev = _batch(B, dialect, n, mixed=False)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n, mixed=False)
     with BatchedFilter(B, prm, dtype=32, nstate=n) as flt:
         eng = OracleEngine(B, dialect, n)
         flt.set_state(nom, rot, P, prev)
@@ -169,12 +140,12 @@ def test_free_running_100_frames(dialect):
         worst = (0.0, 0.0)
         for frame in range(100):
             K = (7, 7, 6)[frame % 3]
-            acc, gyr = _imu(0, B, step, K, nom)
+            acc, gyr = imu_of(0, B, step, K, nom)
             step += K
             for k in range(K):
                 flt.predict(acc[k], gyr[k], DT)
                 eng.predict(acc[k], gyr[k], DT)
-            ids, pos, quat = _markers(0, B, frame, M, nom, prm)
+            ids, pos, quat = markers_of(0, B, frame, M, nom, prm)
             mode = 1 if frame % 2 else 0
             flt.correct(ids, pos, quat, mode)
             eng.correct(ids, pos, quat, mode)
@@ -193,7 +164,7 @@ def test_land_recording_slice_replay():
     """config 1 plumbing on the GPU: the committed land-recording slice through replay()."""
     d = np.load(os.path.join(GOLD, "land_slice.npz"))
     for dialect, key in ((0, "states_matlab"), (1, "states_cpp")):
-        prm = _params(dialect)
+        prm = params_of(dialect)
         with BatchedFilter(1, prm, dtype=32, nstate=18) as flt:
             states, npred = replay.replay(flt, d["imu"], d["image"], prm, max_frames=len(d[key]))
         assert (npred == d["npredict"]).all()
@@ -214,8 +185,8 @@ def test_land_recording_slice_replay():
 # ------------------------------------------------------------------ algebraic properties on the device
 def test_predict_n_equals_repeated_predict():
     B, K = 192, 5
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    acc, gyr = _imu(0, B, 0, K, nom)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    acc, gyr = imu_of(0, B, 0, K, nom)
     dt = np.full(K, DT[0])
     with BatchedFilter(B, prm) as a, BatchedFilter(B, prm) as b:
         a.set_state(nom, rot, P, prev)
@@ -231,16 +202,16 @@ def test_predict_n_equals_repeated_predict():
 @pytest.mark.parametrize("dialect", [0, 1])
 def test_joseph_form_equals_simple_form(dialect):
     B, M = 128, 4
-    prm, nom, rot, P, prev = _batch(B, dialect, 18)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
-    with BatchedFilter(B, _params(dialect, 0), dtype=64) as a, BatchedFilter(B, _params(dialect, 1), dtype=64) as b:
+    prm, nom, rot, P, prev = state_batch(B, dialect, 18)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
+    with BatchedFilter(B, params_of(dialect, 0), dtype=64) as a, BatchedFilter(B, params_of(dialect, 1), dtype=64) as b:
         for f in (a, b):
             f.set_state(nom, rot, P, prev)
             f.correct(ids, pos, quat, 1)
         sa, sb = a.get_state(), b.get_state()
         assert state_rel_err(sa[0], sb[0], sa[2])[0] < 1e-10          # algebraic identity, fp64 kernels
         assert cov_rel_err(sa[2], sb[2]) < 1e-10 and cov_rel_err_blockwise(sa[2], sb[2]) < 1e-10
-    with BatchedFilter(B, _params(dialect, 1)) as b:
+    with BatchedFilter(B, params_of(dialect, 1)) as b:
         b.set_state(nom, rot, P, prev)
         b.correct(ids, pos, quat, 1)
         eng = OracleEngine(B, dialect, 18, cov_form=1)
@@ -251,8 +222,8 @@ def test_joseph_form_equals_simple_form(dialect):
 
 def test_one_stacked_marker_is_the_nearest_marker_update():
     B = 128
-    prm, nom, rot, P, prev = _batch(B, 1, 18)
-    ids, pos, quat = _markers(0, B, 0, 1, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 1, 18)
+    ids, pos, quat = markers_of(0, B, 0, 1, nom, prm)
     prev = ids[:, 0].copy()
     with BatchedFilter(B, prm) as a, BatchedFilter(B, prm) as b:
         a.set_state(nom, rot, P, prev)
@@ -269,11 +240,11 @@ def test_one_stacked_marker_is_the_nearest_marker_update():
 @pytest.mark.parametrize("dialect", [0, 1])
 def test_n15_is_n18_without_gravity_uncertainty(dialect):
     B, M = 128, 4
-    prm, nom, rot, P15, prev = _batch(B, dialect, 15)
+    prm, nom, rot, P15, prev = state_batch(B, dialect, 15)
     P18 = np.zeros((B, 18, 18))
     P18[:, :15, :15] = P15
-    acc, gyr = _imu(0, B, 0, 3, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    acc, gyr = imu_of(0, B, 0, 3, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     for dtype, tol in ((64, 1e-10), (32, STATE_TOL)):
         with BatchedFilter(B, prm, nstate=15, dtype=dtype) as a, BatchedFilter(B, prm, nstate=18, dtype=dtype) as b:
             a.set_state(nom, rot, P15, prev)
@@ -291,8 +262,8 @@ def test_n15_is_n18_without_gravity_uncertainty(dialect):
 
 def test_skip_mask_and_state_roundtrip():
     B, M = 100, 2
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     skip = (np.arange(B) % 3 == 0).astype(np.uint8)
     with BatchedFilter(B, prm, dtype=64) as flt:
         flt.set_state(nom, rot, P, prev)
@@ -316,8 +287,8 @@ def test_nearest_marker_among_many_slots(dialect):
     runs over four groups; in the C++ dialect the previously used marker sits in a late group (hysteresis,
     filter.cpp:652-664) for half of the filters"""
     B = 96                                          # not a multiple of 64: a ragged last tile
-    prm, nom, rot, P, prev = _batch(B, dialect, 18)
-    ids, pos, quat = _markers(0, B, 3, 12, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, dialect, 18)
+    ids, pos, quat = markers_of(0, B, 3, 12, nom, prm)
     ids16 = np.full((B, 16), -1, np.int32); ids16[:, [0, 1, 2, 4, 5, 7, 8, 9, 11, 12, 14, 15]] = ids
     pos16 = np.zeros((B, 16, 3)); quat16 = np.zeros((B, 16, 4)); quat16[:, :, 0] = 1
     pos16[:, [0, 1, 2, 4, 5, 7, 8, 9, 11, 12, 14, 15]] = pos
@@ -339,8 +310,8 @@ def test_skip_mask_ragged_batch_and_invisible_markers(mode):
     """lanes that are skipped, lanes past the batch end and filters without any visible marker run through the same
     prologue as live lanes: nothing of theirs may be written"""
     B, M = 100, 4
-    prm, nom, rot, P, prev = _batch(B, 1, 18)
-    ids, pos, quat = _markers(0, B, 1, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 1, 18)
+    ids, pos, quat = markers_of(0, B, 1, M, nom, prm)
     ids = ids.copy()
     ids[5::10] = -1                                 # no visible marker at all
     ids[3::10, 1:] = -1                             # one visible marker
@@ -373,11 +344,11 @@ def test_full_batch_properties_and_shard_equality():
     spot check on a strided subset, and sharded == unsharded bit for bit."""
     import torch
     B, M, n = 65536, 4, 18
-    prm = _params(0)
+    prm = params_of(0)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), n)
-    nom, rot, P = _r32(nom), _r32(rot), _r32(P)
-    acc, gyr = _imu(0, B, 0, 3, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    nom, rot, P = r32(nom), r32(rot), r32(P)
+    acc, gyr = imu_of(0, B, 0, 3, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d_acc, d_gyr, d_dt = f32(acc), f32(gyr), f32(np.full(3, DT[0]))
@@ -419,10 +390,10 @@ def test_row_split_correct_of_large_launches(dialect, n):
     kernels_tu.hip): parity with the oracle on a strided subset, and the same posterior as the one-wave kernel that the two
     half batches get (different evaluation order of the same six rank-1 passes, so fp32-close, not bit-equal)."""
     B, M = 131072, 4
-    prm = _params(dialect)
+    prm = params_of(dialect)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), n)
-    nom, rot, P = _r32(nom), _r32(rot), _r32(P)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    nom, rot, P = r32(nom), r32(rot), r32(P)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     ids[5] = -1
     ids[70, 1:] = -1
 
@@ -455,11 +426,11 @@ def test_two_wave_frame_and_predict_n_of_large_launches(dialect, n):
     subset and fp32-closeness to the one-wave kernels that the two half batches get"""
     import torch
     B, M, K = 131072, 4, 5
-    prm = _params(dialect)
+    prm = params_of(dialect)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), n)
-    nom, rot, P = _r32(nom), _r32(rot), _r32(P)
-    acc, gyr = _imu(0, B, 0, K, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    nom, rot, P = r32(nom), r32(rot), r32(P)
+    acc, gyr = imu_of(0, B, 0, K, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     ids[5] = -1                                                 # a filter that sees nothing: predicted record only
     skip = np.zeros(B, np.uint8); skip[9] = 1                   # ... and one whose camera frame is masked
     dev = torch.device("cuda:0")
@@ -511,10 +482,10 @@ def test_frame_window_equals_a_sequence_of_fused_frames(dialect, mode):
     B, M = 1000 - 3, 4
     kcount = [7, 0, 6, 3]
     F, Kt = len(kcount), sum(kcount)
-    prm, nom, rot, P, prev = _batch(B, dialect, 18)
-    acc, gyr = _imu(0, B, 0, Kt, nom)
+    prm, nom, rot, P, prev = state_batch(B, dialect, 18)
+    acc, gyr = imu_of(0, B, 0, Kt, nom)
     dev = torch.device("cuda:0")
-    frames = [_markers(0, B, f, M, nom, prm) for f in range(F)]
+    frames = [markers_of(0, B, f, M, nom, prm) for f in range(F)]
     ids = np.stack([f[0] for f in frames]); pos = np.stack([f[1] for f in frames]); quat = np.stack([f[2] for f in frames])
     ids[1, 5] = -1
     ids[2, 6, :] = 9
@@ -588,14 +559,14 @@ def test_fused_frame_equals_per_call_launches(dialect, mode):
     """one launch per frame (records resident in registers) vs K predict launches + one correct launch"""
     import torch
     B, M, K = 1000, 4, 7
-    prm, nom, rot, P, prev = _batch(B, dialect, 18)
-    acc, gyr = _imu(0, B, 0, 2 * K, nom)
+    prm, nom, rot, P, prev = state_batch(B, dialect, 18)
+    acc, gyr = imu_of(0, B, 0, 2 * K, nom)
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d_acc, d_gyr, d_dt = f32(acc), f32(gyr), f32(np.full(K, DT[0]))
     frames = []
     for f in range(2):
-        ids, pos, quat = _markers(0, B, f, M, nom, prm)
+        ids, pos, quat = markers_of(0, B, f, M, nom, prm)
         ids[5] = -1
         ids[6, :] = 9
         frames.append((torch.from_numpy(ids).to(dev), f32(pos), f32(quat)))
@@ -656,14 +627,14 @@ def test_fp64_resident_frame_and_predict_n(dialect, n):
     Types of the reference: common.hpp:205-247; operations: filter.cpp:533-616, 622-741."""
     import torch
     B, M, K = 1000, 4, 7
-    prm, nom, rot, P, prev = _batch(B, dialect, n)
-    acc, gyr = _imu(0, B, 0, 2 * K, nom)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n)
+    acc, gyr = imu_of(0, B, 0, 2 * K, nom)
     dev = torch.device("cuda:0")
     f64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev)
     d_acc, d_gyr, d_dt = f64(acc), f64(gyr), f64(np.full(K, DT[0]))
     frames = []
     for f in range(2):
-        ids, pos, quat = _markers(0, B, f, M, nom, prm)
+        ids, pos, quat = markers_of(0, B, f, M, nom, prm)
         ids[5] = -1
         ids[6, :] = 9
         frames.append((torch.from_numpy(ids).to(dev), f64(pos), f64(quat)))
@@ -711,8 +682,8 @@ def test_fp64_resident_frame_and_predict_n(dialect, n):
 def test_sixteen_marker_slots_stacked():
     """config 5 shape: M = 16 slots per frame (12 distinct map markers + 4 absent), stacked 84-row update"""
     B = 192
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    ids, pos, quat = _markers(0, B, 0, 12, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    ids, pos, quat = markers_of(0, B, 0, 12, nom, prm)
     ids16 = np.full((B, 16), -1, np.int32); ids16[:, 2:14] = ids
     pos16 = np.zeros((B, 16, 3)); pos16[:, 2:14] = pos
     quat16 = np.zeros((B, 16, 4)); quat16[:, :, 0] = 1; quat16[:, 2:14] = quat
@@ -733,7 +704,7 @@ def test_long_run_stability_and_degenerate_inputs():
     (w == 0 and a zero correction, which are 0/0 in both reference dialects) leave the state finite."""
     import torch
     B, M = 4096, 4
-    prm = _params(0)
+    prm = params_of(0)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), 18)
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
@@ -778,10 +749,10 @@ def test_device_state_io_records_aliasing_and_checkpoint_resume():
     and checkpoint -> resume: copying the packed records into a fresh handle continues bit for bit."""
     import torch
     B = 777
-    prm, nom, rot, P, prev = _batch(B, 1, 18)
+    prm, nom, rot, P, prev = state_batch(B, 1, 18)
     prev = (np.arange(B) % 3).astype(np.int32)
-    acc, gyr = _imu(0, B, 0, 4, nom)
-    dt = _r32(np.random.default_rng(1).uniform(0.002, 0.008, (4, B)))
+    acc, gyr = imu_of(0, B, 0, 4, nom)
+    dt = r32(np.random.default_rng(1).uniform(0.002, 0.008, (4, B)))
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     with BatchedFilter(B, prm) as a, BatchedFilter(B, prm) as b:
@@ -816,9 +787,9 @@ def test_hip_graph_replay_equals_eager_launches():
     """a captured frame (7 predict launches + 1 correct launch) replayed from a HIP graph == the eager launches"""
     import torch
     B, M, K = 4096, 4, 7
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    acc, gyr = _imu(0, B, 0, K, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    acc, gyr = imu_of(0, B, 0, K, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d = [f32(acc), f32(gyr), f32(np.full(K, DT[0])), torch.from_numpy(ids).to(dev), f32(pos), f32(quat)]
@@ -843,9 +814,9 @@ def test_parity_gate_goes_red_on_a_mutated_result():
     relative 1e-3 / a factor of two -- every such mutation must turn the gate red.  (The round-1 gate,
     max|dP| / max|P| alone, let a doubled position block pass at 1.3e-6 because P_gg ~ 100 dominates it.)"""
     B, M = 256, 4
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    acc, gyr = _imu(0, B, 0, 1, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    acc, gyr = imu_of(0, B, 0, 1, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     with BatchedFilter(B, prm) as flt:
         eng = OracleEngine(B, 0, 18)
         flt.set_state(nom, rot, P, prev)
@@ -885,9 +856,9 @@ def test_frame_entry_points_validate_before_they_launch():
     import ctypes as C
     import torch
     B, K, M = 256, 3, 2
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    acc, gyr = _imu(0, B, 0, K, nom)
-    ids, pos, quat = _markers(0, B, 0, M, nom, prm)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    acc, gyr = imu_of(0, B, 0, K, nom)
+    ids, pos, quat = markers_of(0, B, 0, M, nom, prm)
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d_acc, d_gyr, d_dt = f32(acc), f32(gyr), f32(np.full(K, DT[0]))
@@ -933,8 +904,8 @@ def test_streams_are_ordered_by_wait_and_signal():
     handed back with signal_stream, and set_stream(torch stream) shares the stream outright (handle 0 = the legacy default stream)"""
     import torch
     B = 4096
-    prm, nom, rot, P, prev = _batch(B, 0, 18)
-    acc, gyr = _imu(0, B, 0, 1, nom)
+    prm, nom, rot, P, prev = state_batch(B, 0, 18)
+    acc, gyr = imu_of(0, B, 0, 1, nom)
     dev = torch.device("cuda:0")
     eng = OracleEngine(B, 0, 18)
     eng.set_state(nom, rot, P, prev)

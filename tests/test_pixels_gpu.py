@@ -14,27 +14,15 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
+from support import SIZE, perturbed_setup, r32
 from util import (COV_BLOCK_TOL, COV_TOL, PLAIN_TOL, STATE_TOL, WINDOW_TOL, assert_parity, parity_errors, pixel_scene)
 
 pytestmark = pytest.mark.gpu
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-SIZE = 0.28
 
 
-def _scene(B, M, dialect, seed, noise=5e-4):
-    prm = capi.default_params(dialect)
-    prm.marker_size = SIZE
-    nom0, _, P, prev = synth.initial_state(0, B, list(prm.p0_diag), 18, mixed_cov=True)
-    truth, _, ids, left, right = pixel_scene(B, M, prm, SIZE, seed=seed, noise=noise, nominal=nom0)
-    rng = np.random.default_rng(seed + 1)
-    nom = truth.copy()
-    nom[:, 0:3] += rng.normal(0, 0.004, (B, 3))                      # innovations of a few mm / mrad
-    dq = np.concatenate([np.ones((B, 1)), rng.normal(0, 0.002, (B, 3))], axis=1)
-    nom[:, 6:10] = synth.qmul(nom[:, 6:10], dq)
-    nom[:, 6:10] /= np.linalg.norm(nom[:, 6:10], axis=1, keepdims=True)
-    nom = r32(nom)
-    rot = r32(synth.q2R(nom[:, 6:10]).reshape(B, 9))
-    return prm, nom, rot, r32(P), prev, ids, r32(left), r32(right)
+def _scene(B, M, dialect, seed):
+    """B filters of their own scene, fp32-representable, the prior from the dialect's own p0_diag"""
+    return perturbed_setup(B, 32, 18, dialect, "stereo", M=M, seed=seed, n=B, prior_dialect=dialect)
 
 
 def _oracle_update(B, dialect, n, nom, rot, P, prev, ids, left, rgt, r_pix, skip=None, analytic=True, cov_form=oc.SIMPLE, vision=None):

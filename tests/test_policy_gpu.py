@@ -2,49 +2,23 @@
 wave per SIMD, and the policy batch that makes the kernel-family choice independent of the shard layout.
 No reference counterpart for any of it (the reference runs one filter on one thread, C++/src/filter.cpp:190-250); the arithmetic
 that must not change is ImuUpdate.m:36-82 / MeasureUpdate.m:37-103."""
-import os
-
 import numpy as np
 import pytest
 
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
+from support import DT, env, r32
 from util import PLAIN_WINDOW_TOL, assert_parity
 
 pytestmark = pytest.mark.gpu
-DT = np.array([np.float64(np.float32(0.005))])
-
-
-def _r32(a):
-    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-class _env:
-    """environment knobs are read ONCE, at fbus_ekf_create: set them around the construction of a handle"""
-
-    def __init__(self, **kw):
-        self.kw = {k: str(v) for k, v in kw.items()}
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kw}
-        os.environ.update(self.kw)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 def _inputs(B, M, dialect=0, seed=0, with_cov=True):
     prm = capi.default_params(dialect)
     nom, rot, P, prev = synth.initial_state(seed, seed + B, list(prm.p0_diag), 18, mixed_cov=with_cov, with_cov=with_cov)
-    nom, rot = _r32(nom), _r32(rot)
-    P = _r32(P) if P is not None else None
+    nom, rot = r32(nom), r32(rot)
+    P = r32(P) if P is not None else None
     acc, gyr = synth.imu_samples(seed, seed + B, 0, 3, nom)
     ids, pos, quat = synth.marker_frame(seed, seed + B, 0, M, nom, prm)
-    return prm, nom, rot, P, prev, _r32(acc), _r32(gyr), ids, _r32(pos), _r32(quat)
+    return prm, nom, rot, P, prev, r32(acc), r32(gyr), ids, r32(pos), r32(quat)
 
 
 def _run(flt, nom, rot, P, prev, acc, gyr, ids, pos, quat):
@@ -69,7 +43,7 @@ def test_launch_policy_follows_the_device_and_halves_with_half_the_simds():
     quarter = p["simds"] // 4
     # 16 384 filters = 256 tiles: a quarter of a 1024-SIMD chip -> the per-call predict and the measurement folds divide the work
     assert (p["roles_predict"], p["roles_meas"], p["team_frames"]) == ((3, 4, True) if 256 <= quarter else (1, 2 if 256 <= 2 * quarter else 1, 256 <= 2 * quarter))
-    with _env(FBUS_FAKE_SIMDS=p["simds"] // 2):
+    with env(FBUS_FAKE_SIMDS=p["simds"] // 2):
         with BatchedFilter(16384, prm) as flt:
             h = flt.launch_policy(M=4, K=7)
     assert h["simds"] == p["simds"] // 2 and h["one_round_filters"] == p["one_round_filters"] // 2
@@ -79,7 +53,7 @@ def test_launch_policy_follows_the_device_and_halves_with_half_the_simds():
         assert (h["roles_predict"], h["roles_meas"]) == (1, 2)          # 256 tiles are half of a 512-SIMD device
         with BatchedFilter(8192, prm) as flt:
             assert flt.launch_info(capi.INFO_ROLES_PREDICT, 1) == 3      # 128 tiles: a quarter of this device ...
-        with _env(FBUS_FAKE_SIMDS=512):
+        with env(FBUS_FAKE_SIMDS=512):
             with BatchedFilter(8192, prm) as flt:
                 assert flt.launch_info(capi.INFO_ROLES_PREDICT, 1) == 3  # ... and exactly a quarter of the halved one
             with BatchedFilter(8256, prm) as flt:
@@ -94,7 +68,7 @@ def test_parity_holds_with_half_the_simds():
     with BatchedFilter(B, prm) as flt:
         simds = flt.launch_info(capi.INFO_SIMDS)
         ref = _run(flt, nom, rot, None, prev, acc, gyr, ids, pos, quat)
-    with _env(FBUS_FAKE_SIMDS=simds // 2):
+    with env(FBUS_FAKE_SIMDS=simds // 2):
         with BatchedFilter(B, prm) as flt:
             assert flt.launch_info(capi.INFO_TWO_WAVE_MIN_B) == simds // 2 * 64 + 1
             got = _run(flt, nom, rot, None, prev, acc, gyr, ids, pos, quat)
@@ -123,7 +97,7 @@ def test_more_filters_than_one_wave_per_simd(B):
     prm, nom, rot, P, prev, acc, gyr, ids, pos, quat = _inputs(B, M, with_cov=False)
     res = {}
     for two in (1 << 30, None):
-        with _env(**({"FBUS_TWO_WAVE_MIN_B": two} if two else {})):
+        with env(**({"FBUS_TWO_WAVE_MIN_B": two} if two else {})):
             with BatchedFilter(B, prm) as flt:
                 one_round = flt.launch_info(capi.INFO_ONE_ROUND_FILTERS)
                 assert flt.launch_info(capi.INFO_TWO_WAVE_MIN_B) == (two if two else one_round + 1)
@@ -154,7 +128,7 @@ def test_shards_equal_the_single_handle_bit_for_bit_under_the_policy_batch():
     total, M, K = 24576, 4, 7
     prm, nom, rot, P, prev, acc3, gyr3, ids, pos, quat = _inputs(total, M, with_cov=False)
     acc, gyr = synth.imu_samples(0, total, 0, K, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
+    acc, gyr = r32(acc), r32(gyr)
     dts = np.full(K, DT[0])
 
     def job(flt, lo, hi):
@@ -207,7 +181,7 @@ def test_shards_of_a_job_above_one_round_equal_the_single_handle_bit_for_bit():
     total, M, K = 73728, 4, 5
     prm, nom, rot, P, prev, acc3, gyr3, ids, pos, quat = _inputs(total, M, with_cov=False)
     acc, gyr = synth.imu_samples(0, total, 0, K, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
+    acc, gyr = r32(acc), r32(gyr)
     dts = np.full(K, DT[0])
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).cuda()
 
@@ -268,11 +242,11 @@ def test_config4_partition_262144_filters_as_eight_shards_of_32768():
     Kt = sum(pattern)
     prm = capi.default_params(0)
     nom, rot, _, prev = synth.initial_state(0, total, list(prm.p0_diag), 18, with_cov=False)
-    nom, rot = _r32(nom), _r32(rot)
+    nom, rot = r32(nom), r32(rot)
     acc, gyr = synth.imu_samples(0, total, 0, Kt, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
+    acc, gyr = r32(acc), r32(gyr)
     frames = [synth.marker_frame(0, total, f, M, nom, prm) for f in range(len(pattern) + 1)]
-    ids = np.stack([f[0] for f in frames]); pos = _r32(np.stack([f[1] for f in frames])); quat = _r32(np.stack([f[2] for f in frames]))
+    ids = np.stack([f[0] for f in frames]); pos = r32(np.stack([f[1] for f in frames])); quat = r32(np.stack([f[2] for f in frames]))
     dev = torch.device("cuda:0")
     f32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d_dt = torch.full((max(pattern),), float(DT[0]), dtype=torch.float32, device=dev)
@@ -351,7 +325,7 @@ def test_config4_partition_262144_filters_as_eight_shards_of_32768():
 
         def q():
             if fp32_records:
-                eng.nominal[...] = _r32(eng.nominal); eng.rot[...] = _r32(eng.rot); eng.P[...] = _r32(eng.P)
+                eng.nominal[...] = r32(eng.nominal); eng.rot[...] = r32(eng.rot); eng.P[...] = r32(eng.P)
         for kind, a in steps:
             if kind == "p":
                 eng.predict(acc[a][sub], gyr[a][sub], DT)

@@ -13,7 +13,7 @@ import pytest
 
 from fbus_ekf import capi
 from route_cells import CFGS, KC, KINDS, NEAREST, STACKED, data_of, make, one_frame, window
-from test_nis_gpu import _same
+from support import same_state
 
 pytestmark = pytest.mark.gpu
 
@@ -99,7 +99,7 @@ def test_window_signature_and_window_equals_its_frames(cfg):
                 k0 += K
             s.sync()
             assert counts(s) == expect, what
-            assert _same(w.get_state(), s.get_state()) and np.array_equal(w.applied(), s.applied()), what
+            assert same_state(w.get_state(), s.get_state()) and np.array_equal(w.applied(), s.applied()), what
 
 
 @pytest.mark.parametrize("cfg", [CFGS[i] for i in (0, 1, 7, 8, 12)], ids=repr)

@@ -12,23 +12,11 @@ import pytest
 
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
+from support import DT, r32, state_batch
 from util import assert_parity, assert_window_parity, parity_errors
 
 pytestmark = pytest.mark.gpu
-DT = np.array([np.float64(np.float32(0.005))])
-
-
-def _r32(a):
-    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-
-
-def _batch(B, dialect, n, seed_off=0):
-    prm = capi.default_params(dialect)
-    nom, rot, P, prev = synth.initial_state(seed_off, seed_off + B, list(prm.p0_diag), n, mixed_cov=True)
-    return prm, _r32(nom), _r32(rot), _r32(P), prev
-
-
-def _same(a, b, what, ulps=2.0, nominal_exact=True):
+def _same_to_ulps(a, b, what, ulps=2.0, nominal_exact=True):
     """nominal state, rotation bit-equal (or to `ulps` fp32 ulps), marker id equal; covariance equal to `ulps` fp32 ulps of
     sqrt(P_ii P_jj)"""
     for x, y, name in zip((a[0], a[1]), (b[0], b[1]), ("nominal", "rot")):
@@ -49,10 +37,10 @@ def test_team_predict_equals_one_wave_predict(dialect, n):
     """one ImuUpdate per launch: 2, 3 and 4 roles against the one-wave kernel, ragged batch, per-filter and scalar dt,
     several steps in a row (every stored byte of the record is compared through get_state)"""
     B = 5 * 64 - 9
-    prm, nom, rot, P, prev = _batch(B, dialect, n)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n)
     acc, gyr = synth.imu_samples(0, B, 0, 3, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
-    dtb = _r32(np.random.default_rng(3).uniform(0.001, 0.01, B))
+    acc, gyr = r32(acc), r32(gyr)
+    dtb = r32(np.random.default_rng(3).uniform(0.001, 0.01, B))
     ref = None
     for roles in (1, 2, 3, 4):
         with BatchedFilter(B, prm, nstate=n) as flt:
@@ -69,7 +57,7 @@ def test_team_predict_equals_one_wave_predict(dialect, n):
             eng.predict(acc[0], gyr[0], dtb); eng.predict(acc[1], gyr[1], DT); eng.predict(acc[2], gyr[2], DT)
             assert_parity(ref, eng.get_state(), 32, f"one-wave predict x3 dialect {dialect} N {n}", plain_tol=5e-3)
         else:
-            _same(got, ref, f"predict, {roles} roles, dialect {dialect}, N {n}", ulps=4.0, nominal_exact=False)
+            _same_to_ulps(got, ref, f"predict, {roles} roles, dialect {dialect}, N {n}", ulps=4.0, nominal_exact=False)
 
 
 @pytest.mark.parametrize("n", [18, 15])
@@ -78,11 +66,11 @@ def test_team_predict_n_equals_one_wave_predict_n(dialect, n):
     """K samples per launch with the rows handed on through LDS between the steps: K = 1, 2, 3, 8 against the one-wave predict_n
     and against K per-call predicts"""
     B = 3 * 64 + 5
-    prm, nom, rot, P, prev = _batch(B, dialect, n, seed_off=11)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n, seed_off=11)
     for K in (2, 3, 8):
         acc, gyr = synth.imu_samples(11, 11 + B, 0, K, nom)
-        acc, gyr = _r32(acc), _r32(gyr)
-        dts = _r32(np.random.default_rng(K).uniform(0.002, 0.008, K))
+        acc, gyr = r32(acc), r32(gyr)
+        dts = r32(np.random.default_rng(K).uniform(0.002, 0.008, K))
         out = {}
         for roles in (1, 4):
             with BatchedFilter(B, prm, nstate=n) as flt:
@@ -90,7 +78,7 @@ def test_team_predict_n_equals_one_wave_predict_n(dialect, n):
                 flt.set_state(nom, rot, P, prev)
                 flt.predict_n(acc, gyr, dts)
                 out[roles] = flt.get_state()
-        _same(out[4], out[1], f"predict_n K = {K}, dialect {dialect}, N {n}", ulps=2.0 * K, nominal_exact=False)
+        _same_to_ulps(out[4], out[1], f"predict_n K = {K}, dialect {dialect}, N {n}", ulps=2.0 * K, nominal_exact=False)
         with BatchedFilter(B, prm, nstate=n) as flt:
             flt.set_team(1, 1)
             flt.set_state(nom, rot, P, prev)
@@ -106,11 +94,11 @@ def test_team_is_the_default_for_small_batches():
     an explicit set_team; correct stays on the one-wave kernel) -- and the whole per-call frame (K predicts + correct) stays
     inside the parity gate"""
     B, M, n, dialect = 4096, 4, 18, 0
-    prm, nom, rot, P, prev = _batch(B, dialect, n, seed_off=3)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n, seed_off=3)
     acc, gyr = synth.imu_samples(3, 3 + B, 0, 7, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
+    acc, gyr = r32(acc), r32(gyr)
     ids, pos, quat = synth.marker_frame(3, 3 + B, 0, M, nom, prm)
-    pos, quat = _r32(pos), _r32(quat)
+    pos, quat = r32(pos), r32(quat)
     out = {}
     for setting in ("default", "explicit"):
         with BatchedFilter(B, prm) as flt:
@@ -141,11 +129,11 @@ def test_team_kernels_parity_at_the_config_batch_sizes(B):
     32 768 / 65 536 filters with the (one-wave) correct behind them, same gate and same oracle as every other kernel, on a strided
     subset; and the whole batch against the one-wave kernels (every filter)"""
     dialect, n, M = 0, 18, 4
-    prm, nom, rot, P, prev = _batch(B, dialect, n, seed_off=21)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n, seed_off=21)
     acc, gyr = synth.imu_samples(21, 21 + B, 0, 8, nom)
-    acc, gyr = _r32(acc), _r32(gyr)
+    acc, gyr = r32(acc), r32(gyr)
     ids, pos, quat = synth.marker_frame(21, 21 + B, 0, M, nom, prm)
-    pos, quat = _r32(pos), _r32(quat)
+    pos, quat = r32(pos), r32(quat)
     sub = np.arange(0, B, max(1, B // 97))
     dts = np.full(7, DT[0])
 
@@ -179,8 +167,8 @@ def test_team_kernels_parity_at_the_config_batch_sizes(B):
     eng.predict(acc[0][sub], gyr[0][sub], DT)
     eng.correct(ids[sub], pos[sub], quat[sub], capi.MODE_NEAREST)
     assert_parity([x[sub] for x in team[3]], eng.get_state(), 32, f"team correct nearest, {B} filters", plain_tol=5e-3)
-    _same(team[0], one[0], f"team vs one-wave predict, {B} filters", nominal_exact=False)
-    _same(team[1], one[1], f"team vs one-wave predict_n, {B} filters", ulps=16.0, nominal_exact=False)
+    _same_to_ulps(team[0], one[0], f"team vs one-wave predict, {B} filters", nominal_exact=False)
+    _same_to_ulps(team[1], one[1], f"team vs one-wave predict_n, {B} filters", ulps=16.0, nominal_exact=False)
     for i in (2, 3):
         e = parity_errors(team[i], one[i])
         # the two paths run different instruction streams through the 8 predicts (team: roles, the packed forms of fewer stages) and
@@ -189,12 +177,12 @@ def test_team_kernels_parity_at_the_config_batch_sizes(B):
 
 
 def _window_inputs(B, dialect, n, M, kcount, seed_off=0):
-    prm, nom, rot, P, prev = _batch(B, dialect, n, seed_off)
+    prm, nom, rot, P, prev = state_batch(B, dialect, n, seed_off=seed_off)
     Kt = sum(kcount)
     acc, gyr = synth.imu_samples(seed_off, seed_off + B, 0, Kt, nom)
     frames = [synth.marker_frame(seed_off, seed_off + B, f, M, nom, prm) for f in range(len(kcount))]
-    ids = np.stack([f[0] for f in frames]); pos = _r32(np.stack([f[1] for f in frames])); quat = _r32(np.stack([f[2] for f in frames]))
-    return prm, nom, rot, P, prev, _r32(acc), _r32(gyr), ids, pos, quat
+    ids = np.stack([f[0] for f in frames]); pos = r32(np.stack([f[1] for f in frames])); quat = r32(np.stack([f[2] for f in frames]))
+    return prm, nom, rot, P, prev, r32(acc), r32(gyr), ids, pos, quat
 
 
 @pytest.mark.parametrize("n", [18, 15])
@@ -261,7 +249,7 @@ def test_team_frame_is_the_default_for_small_batches_and_long_windows():
     kcount = [int(x) for x in rng.integers(0, 10, 64)]
     F, Kt = len(kcount), sum(kcount)
     prm, nom, rot, P, prev, acc, gyr, ids, pos, quat = _window_inputs(B, dialect, n, M, kcount, seed_off=9)
-    dtb = _r32(rng.uniform(0.003, 0.007, (Kt, B)))
+    dtb = r32(rng.uniform(0.003, 0.007, (Kt, B)))
     dev = torch.device("cuda:0")
     dd = lambda a: torch.from_numpy(np.ascontiguousarray(a, np.float32)).to(dev)
     d_acc, d_gyr, d_dt = dd(acc), dd(gyr), dd(dtb)

@@ -14,21 +14,13 @@ import numpy as np
 import pytest
 
 from fbus_ekf import BatchedFilter, capi, replay, synth
+from support import SIZE, device_caster, r32
 from util import pixel_scene, state_rel_err, state_rel_err_literal
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
-SIZE = 0.28
 DT = 0.005
-
-
-def _dev(torch, dtype):
-    dev = torch.device("cuda:0")
-    tt = torch.float32 if dtype == 32 else torch.float64
-    return lambda a: (torch.from_numpy(np.ascontiguousarray(a)).to(dev) if np.asarray(a).dtype.kind in "iu"
-                      else torch.from_numpy(np.ascontiguousarray(a, np.float64)).to(dev).to(tt))
 
 
 def _records(flt):
@@ -96,7 +88,7 @@ def test_north_star_window_rows_are_its_frames(dialect, n, what, stereo, mode, r
     ids[min(1, F - 1), 5] = -1
     ids[min(2, F - 1), 6, :] = 9
     skip = np.zeros((F, B), np.uint8); skip[min(2, F - 1), 11] = 1; skip[F - 1, 12] = 1; skip[0, 13] = 1
-    dd = _dev(torch, dtype)
+    dd = device_caster(torch, dtype)
     d_acc, d_gyr, d_dt = dd(acc), dd(gyr), dd(np.full(Kt, DT))
     d_ids, d_left, d_right, d_skip = dd(ids), dd(left), dd(right), dd(skip)
     d_r = d_right if stereo else None
@@ -159,7 +151,7 @@ def test_pose_window_rows_are_its_frames(dialect, n, mode, route):
     ids[min(1, F - 1), 5] = -1
     ids[min(2, F - 1), 6, :] = 9
     skip = np.zeros((F, B), np.uint8); skip[min(2, F - 1), 11] = 1; skip[F - 1, 12] = 1
-    dd = _dev(torch, dtype)
+    dd = device_caster(torch, dtype)
     d_acc, d_gyr, d_dt = dd(rq(acc)), dd(rq(gyr)), dd(np.full(Kt, DT))
     d_ids, d_pos, d_quat, d_skip = dd(ids), dd(pos), dd(quat), dd(skip)
     team = (0, 0) if route == "team" else (1, 1)

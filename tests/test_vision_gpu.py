@@ -8,6 +8,7 @@ import pytest
 
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi
+from support import r32
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -55,7 +56,6 @@ def _perturbed_inputs(n, seed=11):
     base = d[rng.integers(0, len(d), n)]
     left = base[:, 2:10] + rng.normal(0, 0.02, (n, 8))
     right = base[:, 10:18] + rng.normal(0, 0.02, (n, 8))
-    r32 = lambda a: a.astype(np.float32).astype(np.float64)
     return r32(left), r32(right)
 
 
@@ -103,7 +103,6 @@ def test_corners_to_correct_chain_on_device():
     d = np.load(os.path.join(GOLD, "vision_water.npz"))["corners"]
     rng = np.random.default_rng(3)
     base = d[rng.integers(0, len(d), B)]
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
     left, right = r32(base[:, 2:10]), r32(base[:, 10:18])
     o_pos, o_quat, _ = _oracle_refractive(left, right)
     nom, rot, P, prev = synth.initial_state(0, B, list(prm.p0_diag), 18)
@@ -172,7 +171,6 @@ def test_correct_from_stereo_corners_matches_oracle(dialect, mode, dtype, mult, 
     prm.marker_size = size
     prm.cov_form = cov_form
     rng = np.random.default_rng(7)
-    r32 = lambda a: np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
     nom, rot, P, prev = synth.initial_state(300, 300 + B, list(prm.p0_diag), 18, mixed_cov=True)
     nom, rot, P = r32(nom), r32(rot), r32(P)
     ids, _, _ = synth.marker_frame(300, 300 + B, 0, M, nom, prm)
