@@ -1,6 +1,6 @@
 """What more than one test module needs: rounding, constants, the environment-knob context manager, state and input builders, handles and
-calls, bit-equality of states.  A plain library: no tests and no pytest marks, importable without a GPU.  tests/route_cells.py (and
-through it tools/route_matrix.py) builds its cells from it.
+calls, bit-equality of states and of named outputs, the builders of the independence variants.  A plain library: no tests and no pytest
+marks, importable without a GPU.  tests/route_cells.py (and through it tools/route_matrix.py) builds its cells from it.
 
 Every builder here feeds bit-for-bit comparisons downstream: seeds, the order of the random draws, the point where values are rounded,
 dtypes and contiguity are part of each function's contract.  Where two helpers differ in one of these they are two functions, side by
@@ -53,6 +53,35 @@ def frozen(x):
 
 
 # ---- bit-equality -------------------------------------------------------------------------------------------------------------------
+def _bits(x):
+    x = np.ascontiguousarray(x)
+    return x.view(f"u{x.dtype.itemsize}")
+
+
+def same_rows(a, b, rows=None, rows_b=None):
+    """dicts name -> array with the filters along axis 0: a[name][rows] and b[name][rows_b] hold the same BITS for every name of a (NaN
+    equals the same NaN, 0.0 does not equal -0.0).  rows / rows_b: index arrays, None = all.  Prints which names differ, in how many of
+    the filters and in which (numbered as in a)."""
+    ra, rb = (slice(None) if r is None else np.asarray(r) for r in (rows, rows_b))
+    ok = True
+    for name, x in a.items():
+        x, y = np.asarray(x)[ra], np.asarray(b[name])[rb]
+        if x.shape != y.shape or x.dtype != y.dtype:
+            print(f"differs: {name} is {x.dtype} {x.shape} and {y.dtype} {y.shape}")
+            ok = False
+            continue
+        d = (_bits(x) != _bits(y)).reshape(len(x), -1)
+        if d.any():
+            ok = False
+            with np.errstate(invalid="ignore"):
+                diff = np.abs(x.astype(np.float64) - y.astype(np.float64)).reshape(len(x), -1)
+            who = np.nonzero(d.any(axis=1))[0]
+            who = who if rows is None else np.asarray(rows)[who]
+            print(f"differs: {name} in {len(who)} filters {who[:12]}, columns {np.nonzero(d.any(axis=0))[0][:12]}, "
+                  f"max |diff| {np.nanmax(diff):.3e}")
+    return ok
+
+
 def same_state(a, b, rows=None):
     """every array of a equals its partner in b bit for bit (on the filters `rows`): (nominal, rot, P, prev), with or without `applied` as
     a fifth.  Prints where they differ."""
@@ -70,6 +99,55 @@ def same_state(a, b, rows=None):
                 print(f"differs: {name} in {int(d.any(axis=1).sum())} filters, columns {np.nonzero(d.any(axis=0))[0][:12]}, "
                       f"max |diff| {diff.max():.3e}")
     return ok
+
+
+# ---- the same filters in other surroundings (tests/test_independence_*.py) ----------------------------------------------------------------
+B_IND = 193                                  # three full 64-filter tiles and a tile of one filter; prime
+
+
+def permutation(B=B_IND, power=5, shift=106):
+    """pi: position j holds filter pi[j] = (j ** power + shift) mod B.  B prime and power coprime to B - 1: a bijection.  (An affine map
+    k j + c will not do: with k != 1 it has a fixed point, with k = 1 it is a rotation, which keeps every filter beside its neighbour.)"""
+    return np.array([(pow(j, power, B) + shift) % B for j in range(B)])
+
+
+def ragged_cut(B=B_IND, at=101):
+    """two shards whose border lies inside a tile: at = 101 is lane 37 of tile 1, and the second shard ends in a tile of (B - at) % 64"""
+    return np.arange(0, at), np.arange(at, B)
+
+
+POISON_FORMS = 5                             # a b c d e of poisoned_state / with_nan
+ALONE = (0, 100, 192)                        # the filters that also run on handles of one filter: first, mid-tile, the tail tile's only one
+
+
+def poison_set(B=B_IND):
+    """(S, form): the filters to break -- id % 7 == 5, all of tile 1 (64 .. 127) except 100 (a whole wave but one lane) and B - 2 -- and
+    the form of each, cycling through all of them in the order of S"""
+    b = np.arange(B)
+    S = b[(b % 7 == 5) | ((b >= 64) & (b < 128) & (b != 100)) | (b == B - 2)]
+    return S, np.arange(len(S)) % POISON_FORMS
+
+
+def poisoned_state(nom, rot, P, S, form):
+    """copies of (nominal, rot, P) with the filters S broken, S[i] in the way form[i]: 0 (a) NaN in all three; 1 (b) position +Inf and the
+    covariance diagonal 1e30; 2 (c) the covariance -P; 4 (e) zero quaternion and zero rotation; 3 (d) leaves the state alone (with_nan
+    breaks its inputs)"""
+    nom, rot, P = np.array(nom), np.array(rot), np.array(P)
+    a, b, c, e = (S[form == k] for k in (0, 1, 2, 4))
+    nom[a], rot[a], P[a] = np.nan, np.nan, np.nan
+    nom[b, 0:3] = np.inf
+    i = np.arange(P.shape[1])
+    P[b[:, None], i, i] = 1e30
+    P[c] = -P[c]
+    nom[e, 6:10], rot[e] = 0.0, 0.0
+    return nom, rot, P
+
+
+def with_nan(x, where, axis):
+    """a copy of x, NaN at the indices `where` of `axis`"""
+    x = np.array(x)
+    x[(slice(None),) * axis + (where,)] = np.nan
+    return x
 
 
 # ---- pose-row states and inputs, fp32-representable -----------------------------------------------------------------------------------
@@ -241,8 +319,8 @@ def perturbed_setup(B, dtype, nstate, dialect, kind, M=4, seed=3, n=256, tilted=
 
 # ---- handles and calls --------------------------------------------------------------------------------------------------------------
 def to_device(a, dt=None):
-    """a (None stays None) on the device, cast to dt by numpy on the host first"""
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
+    """a (None stays None, a tensor stays the tensor it is) on the device, cast to dt by numpy on the host first"""
+    return a if a is None or torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a, dt)).cuda()
 
 
 def device_caster(torch, dtype):

@@ -6,46 +6,16 @@ For every cell (handle state x size class x entry point x call shape):
                 K = 1) and its update, every fused or resident route counts the frame kind only, a window counts its F frames
   2 frames      the records and applied flags after a window == after the same frames one by one through the single-frame entry point,
                 bit for bit (team windows against team frames, one-wave against one-wave, per-call against per-call)
-The expected route is restated here from the documented rules and the handle's own launch_info answers; the last test checks that the
-cells reach every value of both route enums."""
+The expected route is restated in tests/route_cells.py from the documented rules and the handle's own launch_info answers; the last test
+checks that the cells reach every value of both route enums."""
 import numpy as np
 import pytest
 
 from fbus_ekf import capi
-from route_cells import CFGS, KC, KINDS, NEAREST, STACKED, data_of, make, one_frame, window
+from route_cells import CFGS, KINDS, NEAREST, STACKED, data_of, frame_route, make, one_frame, shapes_of, window, window_route
 from support import same_state
 
 pytestmark = pytest.mark.gpu
-
-
-# ---- the documented rules, restated from the handle's own launch_info answers -----------------------------------------------------------------
-def frame_route(f, cfg, kind, mode, M, K):
-    fp32, tabled = cfg.dtype == 32, cfg.noise or cfg.lik
-    if tabled and not (f.launch_info(capi.INFO_NOISE_RESIDENT) and K <= 255):
-        return "per_call"
-    if kind == "pose":
-        if cfg.joseph and mode == NEAREST:
-            return "per_call"
-        if not fp32:
-            return "f64_fused" if mode == STACKED and not cfg.joseph and 1 <= K <= 255 else "per_call"
-        if tabled:
-            return "tabled_resident"
-        return "team" if f.launch_info(capi.INFO_TEAM_FRAMES) and K <= 255 else "fused"
-    if not fp32 or M == 0 or K > 255 or cfg.env.get("FBUS_NO_FRAME_MEAS") == "1":
-        return "per_call"
-    if tabled:
-        return "tabled_resident"
-    roles = 1 if (kind == "corners" and mode == NEAREST) else f.launch_info(capi.INFO_ROLES_MEAS, M)
-    return "meas_resident" if roles == 1 else "per_call"
-
-
-def window_route(f, cfg, kind, mode, M, nframes, rows):
-    r = frame_route(f, cfg, kind, mode, M, 1)
-    if r in ("per_call", "f64_fused") or (kind != "pose" and nframes == 1):
-        return "by_frame"
-    if r == "team":
-        return "team_frames" if rows else "team"
-    return "one_wave"
 
 
 def signature(route, kind, M, K):
@@ -67,19 +37,6 @@ def counts(f):
 
 def total(parts):
     return {k: sum(p[k] for p in parts) for k in KINDS}
-
-
-# (kind, mode, M, kcount, rows): every kind with and without rows, a one-frame window, M = 0 and M = 1
-WINDOWS = [("pose", STACKED, 4, KC, False), ("pose", STACKED, 4, KC, True), ("pose", NEAREST, 4, KC, True), ("pose", STACKED, 0, KC, False),
-           ("left", STACKED, 4, KC, False), ("stereo", STACKED, 4, KC, True), ("corners", NEAREST, 4, KC, False),
-           ("corners", STACKED, 4, KC, True), ("left", STACKED, 1, KC, True), ("stereo", STACKED, 0, KC, False),
-           ("stereo", STACKED, 4, (2,), True)]
-
-
-def shapes_of(cfg):
-    """a third of the shapes per handle state, every shape on the states that differ most (about a hundred cells in all)"""
-    i = CFGS.index(cfg)
-    return WINDOWS if i in (0, 1, 7, 12) else list(dict.fromkeys(WINDOWS[i % 3::3] + WINDOWS[:2]))
 
 
 @pytest.mark.parametrize("cfg", CFGS, ids=repr)
