@@ -1,5 +1,5 @@
-// ekf_group.hpp -- hypothesis groups: evidence-weighted fusion and collapse (fbus_ekf_group_fuse / fbus_ekf_group_collapse,
-// include/fbus_ekf.h).  No reference counterpart: the reference runs one filter on one thread (C++/src/filter.cpp:190-250).
+// ekf_group.hpp -- hypothesis groups: evidence-weighted fusion, collapse and IMM mixing (fbus_ekf_group_fuse / fbus_ekf_group_collapse /
+// fbus_ekf_group_mix, include/fbus_ekf.h).  No reference counterpart: the reference runs one filter on one thread (C++/src/filter.cpp:190-250).
 // Included by fbus_ekf.hip only, next to pack / unpack / snapshot.  gfx950 only.
 //
 // Mapping: ONE FILTER PER LANE, as everywhere.  Group j = filters j G .. j G + G - 1; a wave serves floor(64 / G) whole groups: lane l is
@@ -119,6 +119,58 @@ __device__ __forceinline__ void group_reduce(const double* term, int lane, int n
     wave_lds_fence();
 }
 
+// steps 1, 2 of fuse as mix takes them: this lane's weight in double -- exactly 0 for a member that is not usable and for an idle lane --
+// and bi, the group's best member (-1: no usable member, or an idle lane).  wsh: 64 doubles of LDS, free again on return.
+// (group_fuse_kernel keeps the same lines inline: calling this from it changes its instruction stream, group_delta does not.)
+template <typename GM>
+__device__ __forceinline__ double group_weight(const GM& gm, const double* __restrict__ logw, double* wsh, int G, int& bi)
+{
+    const int lane = gm.lane;
+    const double lw = gm.act ? logw[gm.b] : __builtin_nan("");
+    const bool usable = gm.act && __builtin_isfinite(lw);
+    wsh[lane] = lw;
+    wave_lds_fence();
+    double m = 0.0;
+    bi = -1;
+    for (int j = 0; j < G; ++j) {
+        const double v = wsh[gm.gbase + j];
+        if (__builtin_isfinite(v) && (bi < 0 || v > m)) { m = v; bi = j; }      // (strict: ties go to the first member)
+    }
+    if (!gm.act) bi = -1;
+    const double ew = usable ? exp(lw - m) : 0.0;
+    wave_lds_fence();
+    wsh[lane] = ew;
+    wave_lds_fence();
+    double s = 0.0;
+    for (int j = 0; j < G; ++j) s += wsh[gm.gbase + j];
+    return (usable && bi >= 0) ? ew / s : 0.0;
+}
+
+// step 3: this member's error state dl (order p v theta ba bg [g]) against the chart xs, in double for both record types
+template <typename T, int N>
+__device__ __forceinline__ void group_delta(const T* nom, const T* xs, double* dl)
+{
+    using L = Lay<N>;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        dl[i] = (double)nom[L::OFF_P3 + i] - (double)xs[L::OFF_P3 + i];
+        dl[3 + i] = (double)nom[L::OFF_V + i] - (double)xs[L::OFF_V + i];
+        dl[9 + i] = (double)nom[L::OFF_BA + i] - (double)xs[L::OFF_BA + i];
+        dl[12 + i] = (double)nom[L::OFF_BG + i] - (double)xs[L::OFF_BG + i];
+        if constexpr (N == 18) dl[15 + i] = (double)nom[L::OFF_G + i] - (double)xs[L::OFF_G + i];
+    }
+    {   // dtheta = Log(conj(q*) (x) q), in double for both record types: the inverse of inject()'s q <- normalize(q (x) dq(dtheta))
+        const double qc[4] = { (double)xs[L::OFF_Q], -(double)xs[L::OFF_Q + 1], -(double)xs[L::OFF_Q + 2], -(double)xs[L::OFF_Q + 3] };
+        const double qi[4] = { (double)nom[L::OFF_Q], (double)nom[L::OFF_Q + 1], (double)nom[L::OFF_Q + 2], (double)nom[L::OFF_Q + 3] };
+        double d[4];
+        quat_mul(qc, qi, d);
+        if (d[0] < 0.0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; d[3] = -d[3]; }
+        const double n = sqrt(d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
+        const double k = n == 0.0 ? 0.0 : 2.0 * atan2(n, d[0]) / n;
+        dl[6] = k * d[1]; dl[7] = k * d[2]; dl[8] = k * d[3];
+    }
+}
+
 // dynamic LDS of group_fuse_kernel in bytes (the launcher passes it)
 template <typename T, int N>
 __host__ __device__ constexpr size_t group_fuse_lds(int ngw)
@@ -180,24 +232,7 @@ group_fuse_kernel(const T* __restrict__ recs, size_t rec_bytes, int B, int G, co
 #pragma unroll
     for (int e = 0; e < L::NNOM; ++e) xs[e] = (e >= L::OFF_R && e < L::OFF_R + 9) ? T(0) : __shfl(nom[e], src);
     double dl[N];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        dl[i] = (double)nom[L::OFF_P3 + i] - (double)xs[L::OFF_P3 + i];
-        dl[3 + i] = (double)nom[L::OFF_V + i] - (double)xs[L::OFF_V + i];
-        dl[9 + i] = (double)nom[L::OFF_BA + i] - (double)xs[L::OFF_BA + i];
-        dl[12 + i] = (double)nom[L::OFF_BG + i] - (double)xs[L::OFF_BG + i];
-        if constexpr (N == 18) dl[15 + i] = (double)nom[L::OFF_G + i] - (double)xs[L::OFF_G + i];
-    }
-    {   // dtheta = Log(conj(q*) (x) q), in double for both record types: the inverse of inject()'s q <- normalize(q (x) dq(dtheta))
-        const double qc[4] = { (double)xs[L::OFF_Q], -(double)xs[L::OFF_Q + 1], -(double)xs[L::OFF_Q + 2], -(double)xs[L::OFF_Q + 3] };
-        const double qi[4] = { (double)nom[L::OFF_Q], (double)nom[L::OFF_Q + 1], (double)nom[L::OFF_Q + 2], (double)nom[L::OFF_Q + 3] };
-        double d[4];
-        quat_mul(qc, qi, d);
-        if (d[0] < 0.0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; d[3] = -d[3]; }
-        const double n = sqrt(d[1] * d[1] + d[2] * d[2] + d[3] * d[3]);
-        const double k = n == 0.0 ? 0.0 : 2.0 * atan2(n, d[0]) / n;
-        dl[6] = k * d[1]; dl[7] = k * d[2]; dl[8] = k * d[3];
-    }
+    group_delta<T, N>(nom, xs, dl);
 
     // ---- step 4: mu = sum w_i delta_i, the fused nominal state ----------------------------------------------------------------------
 #pragma unroll
@@ -334,6 +369,155 @@ group_collapse_kernel(T* __restrict__ recs, size_t rec_bytes, int B, int G, cons
                 if (put) __builtin_amdgcn_raw_buffer_store_b128(o, gm.rs, gm.voff + (unsigned)(c0 + k) * 1024u, 0, AUX_DEFAULT);
             }
     }
+}
+
+// dynamic LDS of group_mix_kernel in bytes: a batch of packed covariance elements of every lane, every lane's delta, the 64 weights and
+// the mixing weights W[i][lane] = the share of source member i in this lane's filter (G rows: 32 KB of the 50 KB at G = 64)
+__host__ __device__ constexpr size_t group_mix_lds(int G)
+{
+    return (size_t)((GROUP_EB + GROUP_ROWS) * GROUP_TP + 64 + G * 64) * sizeof(double);
+}
+
+// IMM mixing in place (fbus_ekf_group_mix, include/fbus_ekf.h): every lane is a source AND a target.  Lane j holds column j of the mixing
+// matrix of its group, W_ij = trans[i][j] mu_i / c_j; every lane publishes its delta_i against the chart and, batch by batch, its packed
+// covariance elements to LDS, and lane j adds its own G terms from member 0 up.  A source with W_ij == 0 is skipped, not multiplied.
+// In place and race-free by collapse's argument: the nominal chunks of the whole wave are in registers (and every delta in LDS) before
+// any nominal chunk is stored, a batch of covariance chunks of the whole wave is in LDS before that batch is stored, the batches
+// requested ahead are other chunks, and no other wave owns these filters.
+template <typename T, int N>
+__global__ void __launch_bounds__(BLOCK)
+group_mix_kernel(T* __restrict__ recs, size_t rec_bytes, int B, int G, const double* __restrict__ logw, const double* __restrict__ trans,
+                 double* __restrict__ weight, double* __restrict__ logc)
+{
+    using L = Lay<N>;
+    using RC = Rec<T, N>;
+    constexpr int CN = RC::CH_NOM, EPC = RC::EPC, NP = L::NP;
+    extern __shared__ double group_lds[];
+    const GroupMap<T, N> gm(recs, rec_bytes, B, G);
+    const int lane = gm.lane;
+    double* term = group_lds;                               // [GROUP_EB][GROUP_TP]: P_i,e of the batch
+    double* dsh = term + GROUP_EB * GROUP_TP;               // [N][GROUP_TP]: delta_i
+    double* wsh = dsh + GROUP_ROWS * GROUP_TP;              // [64]
+    double* wmix = wsh + 64;                                // [G][64]: W_ij of lane j
+
+    T nom[L::NNOM];
+    gm.template load<0, CN>(nom);
+
+    // ---- steps 1, 2: mu as in fuse, c_j and this lane's column of W, in double ----------------------------------------------------------
+    int bi;
+    const double mu = group_weight(gm, logw, wsh, G, bi);
+    const bool none = bi < 0;
+    if (gm.act && weight) weight[gm.b] = mu;
+    wave_lds_fence();
+    wsh[lane] = mu;
+    wave_lds_fence();
+    double c = 0.0;
+    for (int i = 0; i < G; ++i) {
+        const double t = trans[i * G + gm.mem] * wsh[gm.gbase + i];
+        wmix[i * 64 + lane] = t;
+        c += t;
+    }
+    const bool reach = gm.act && !none && c > 0.0;          // otherwise the target keeps its bytes
+    if (gm.act && logc) logc[gm.b] = reach ? log(c) : -__builtin_inf();
+    double wjj = 0.0;
+    for (int i = 0; i < G; ++i) {
+        const double wv = reach ? wmix[i * 64 + lane] / c : 0.0;
+        wmix[i * 64 + lane] = wv;
+        if (i == gm.mem) wjj = wv;
+    }
+    const bool put = reach && wjj != 1.0;                   // W_jj == 1: the target is its own only source
+
+    // ---- step 3: the chart x* (carried rotation included) from the best lane, every member's delta to LDS -------------------------------
+    const int src = gm.gbase + (none ? 0 : bi);
+    T xs[L::NNOM];
+#pragma unroll
+    for (int e = 0; e < L::NNOM; ++e) xs[e] = __shfl(nom[e], src);
+    {
+        double dl[N];
+        group_delta<T, N>(nom, xs, dl);
+#pragma unroll
+        for (int a = 0; a < N; ++a) dsh[a * GROUP_TP + lane] = dl[a];
+    }
+    wave_lds_fence();
+
+    // ---- step 4: m_j = sum_i W_ij delta_i in member order; x* (+) m_j, the chart's rotation (and g for N = 15) kept -----------------------
+    double mj[N];
+#pragma unroll
+    for (int a = 0; a < N; ++a) mj[a] = 0.0;
+    for (int i = 0; i < G; ++i) {
+        const double wv = wmix[i * 64 + lane];
+        if (wv != 0.0) {                                    // step 6: one branch per source -- a weightless source's lanes are masked
+#pragma unroll
+            for (int a = 0; a < N; ++a) mj[a] += wv * dsh[a * GROUP_TP + gm.gbase + i];
+        }
+    }
+    {
+        T dx[N];
+#pragma unroll
+        for (int a = 0; a < N; ++a) dx[a] = (T)mj[a];
+        inject<T, N>(xs, dx);
+#pragma unroll
+        for (int cc = 0; cc < CN; ++cc) {
+            u32x4 v;
+            T* e = reinterpret_cast<T*>(&v);
+#pragma unroll
+            for (int k = 0; k < EPC; ++k) e[k] = xs[cc * EPC + k];
+            // (the whole offset in the VGPR, soffset 0: see the hazard note at store_chunks)
+            if (put) __builtin_amdgcn_raw_buffer_store_b128(v, gm.rs, gm.voff + (unsigned)cc * 1024u, 0, AUX_DEFAULT);
+        }
+    }
+
+    // ---- step 5: P0_j = sum_i W_ij (P_i + (delta_i - m_j)(delta_i - m_j)'), a batch of packed elements at a time ------------------------
+    constexpr int CB = GROUP_EB / EPC;                      // chunks per batch
+    constexpr int NCC = (NP + EPC - 1) / EPC;               // covariance chunks that hold an element of P
+    constexpr int NB = (NCC + CB - 1) / CB;
+    constexpr int PF = 2;                                   // batches requested ahead of the one being mixed
+    T pb[NB][GROUP_EB];
+    const auto fetch = [&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        if constexpr (k < NB) {
+            constexpr int c0 = CN + k * CB, c1 = (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC;
+            gm.template load<c0, c1>(pb[k]);
+        }
+    };
+    static_for<0, PF>(fetch);
+    static_for<0, NB>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        fetch(std::integral_constant<int, k + PF>{});
+        constexpr int q0 = k * GROUP_EB;
+        constexpr int ECNT = NP - q0 < GROUP_EB ? NP - q0 : GROUP_EB;
+        constexpr int c0 = CN + k * CB, c1 = (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC;
+#pragma unroll
+        for (int e = 0; e < ECNT; ++e) term[e * GROUP_TP + lane] = (double)pb[k][e];
+        wave_lds_fence();
+        double acc[ECNT];
+#pragma unroll
+        for (int e = 0; e < ECNT; ++e) acc[e] = 0.0;
+        for (int i = 0; i < G; ++i) {
+            const double wv = wmix[i * 64 + lane];
+            if (wv == 0.0) continue;                        // (one branch per source and batch: a select per element made the compiler
+                                                            //  branch around every element's LDS read, each waiting for its own)
+            double d[N];                                    // (only the rows and columns of this batch are read)
+#pragma unroll
+            for (int a = 0; a < N; ++a) d[a] = dsh[a * GROUP_TP + gm.gbase + i] - mj[a];
+            static_for<0, ECNT>([&](auto ec) {
+                constexpr int e = decltype(ec)::value;
+                acc[e] += wv * (term[e * GROUP_TP + gm.gbase + i] + d[pk_row<N>(q0 + e)] * d[pk_col<N>(q0 + e)]);
+            });
+        }
+        wave_lds_fence();                                   // (the next batch overwrites term)
+        // rounded once to the record type; prev_id and the padding behind the last element keep the lane's own bytes
+#pragma unroll
+        for (int e = 0; e < ECNT; ++e) pb[k][e] = (T)acc[e];
+#pragma unroll
+        for (int cc = c0; cc < c1; ++cc) {
+            u32x4 v;
+            T* e = reinterpret_cast<T*>(&v);
+#pragma unroll
+            for (int kk = 0; kk < EPC; ++kk) e[kk] = pb[k][(cc - c0) * EPC + kk];
+            if (put) __builtin_amdgcn_raw_buffer_store_b128(v, gm.rs, gm.voff + (unsigned)cc * 1024u, 0, AUX_DEFAULT);
+        }
+    });
 }
 
 }  // namespace

@@ -590,6 +590,17 @@ int group_collapse_t(fbus_ekf_t h, int G, const int32_t* src)
     return FBUS_OK;
 }
 int do_group_collapse(fbus_ekf_t h, int G, const int32_t* src) { DISPATCH2(h, group_collapse_t, h, G, src); }
+template <typename T, int N>
+int group_mix_t(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc)
+{
+    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
+    h->records_warm = true;                                  // stored with the default cache policy
+    hipLaunchKernelGGL((group_mix_kernel<T, N>), dim3(grid), dim3(BLOCK), group_mix_lds(G), h->stream, (T*)h->recs, h->rec_bytes, h->B, G,
+                       logw, trans, weight, logc);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int do_group_mix(fbus_ekf_t h, int G, const double* lw, const double* tr, double* w, double* lc) { DISPATCH2(h, group_mix_t, h, G, lw, tr, w, lc); }
 
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
 int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
@@ -1386,7 +1397,7 @@ int imu_ema_any(fbus_ekf_t h, Transport t, int T, void* accel, void* gyro, int r
     });
 }
 
-// ---- hypothesis groups: fbus_ekf_group_fuse / _collapse, host and device forms ----------------------------------------------------------
+// ---- hypothesis groups: fbus_ekf_group_fuse / _collapse / _mix, host and device forms ----------------------------------------------------------
 int check_group(fbus_ekf_t h, const char* where, int G)
 {
     if (!h) return FBUS_ERR_INVALID;
@@ -1395,6 +1406,12 @@ int check_group(fbus_ekf_t h, const char* where, int G)
     if (h->B % G != 0)
         return fail(h, FBUS_ERR_INVALID, std::string(where) + ": the batch of " + std::to_string(h->B) + " is not a multiple of G = " + std::to_string(G));
     return FBUS_OK;
+}
+// does a device output of `bytes` at p overlap the records (the rule of fbus_ekf_snapshot_dev)?
+bool in_records(fbus_ekf_t h, const void* p, size_t bytes)
+{
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes, a = reinterpret_cast<uintptr_t>(p);
+    return p && a < r1 && a + bytes > r0;
 }
 int group_fuse_any(fbus_ekf_t h, Transport t, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
 {
@@ -1407,13 +1424,10 @@ int group_fuse_any(fbus_ekf_t h, Transport t, int G, const double* logw, double*
     if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
     const size_t es = esize(h), B = (size_t)h->B, NG = B / G, N = (size_t)h->N;
     if (t == DEV) {          // (staged outputs are the handle's own buffers)
-        const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes;
         const struct { const void* p; size_t bytes; } outs[5] = { { weight, B * sizeof(double) }, { best, NG * sizeof(int32_t) },
                                                                   { nominal, NG * 19 * es }, { P, NG * N * N * es }, { pdiag, NG * N * es } };
-        for (const auto& o : outs) {
-            const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
-            if (o.p && a < r1 && a + o.bytes > r0) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
-        }
+        for (const auto& o : outs)
+            if (in_records(h, o.p, o.bytes)) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
     }
     if (!weight && !best && !nominal && !P && !pdiag) return FBUS_OK;
     const void* dl;
@@ -1443,6 +1457,42 @@ int group_collapse_any(fbus_ekf_t h, Transport t, int G, const int32_t* src)
     const void* ds;
     Piece pc[1] = { in_piece(src, NG * sizeof(int32_t), &ds) };
     return run_pieces(h, t, pc, 1, [&] { return do_group_collapse(h, G, (const int32_t*)ds); });
+}
+int group_mix_any(fbus_ekf_t h, Transport t, int G, const double* logw, const double* trans, double* weight, double* logc)
+{
+    DeviceGuard guard_(h);
+    const char* where = t == DEV ? "fbus_ekf_group_mix_dev" : "fbus_ekf_group_mix";
+    int rc = check_group(h, where, G);
+    if (rc != FBUS_OK) return rc;
+    if (!trans) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans is NULL");
+    if (!logw && !h->d_lik)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
+    const size_t B = (size_t)h->B;
+    if (t == DEV) {
+        if (in_records(h, weight, B * sizeof(double)) || in_records(h, logc, B * sizeof(double)))
+            return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
+    } else {
+        if (h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+        for (int i = 0; i < G; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < G; ++j) {
+                const double v = trans[i * G + j];
+                if (!std::isfinite(v) || v < 0.0)
+                    return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans row " + std::to_string(i) + " column " + std::to_string(j) +
+                                                     " = " + std::to_string(v) + " is not a probability");
+                s += v;
+            }
+            if (std::fabs(s - 1.0) > 1e-9)
+                return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans row " + std::to_string(i) + " sums to " + std::to_string(s) + ", not to 1");
+        }
+    }
+    const void *dl, *dt;
+    void *dw, *dc;
+    Piece pc[4] = { in_piece(logw, B * sizeof(double), &dl), in_piece(trans, (size_t)G * G * sizeof(double), &dt),
+                    out_piece(weight, B * sizeof(double), &dw), out_piece(logc, B * sizeof(double), &dc) };
+    return run_pieces(h, t, pc, 4, [&] {
+        return do_group_mix(h, G, dl ? (const double*)dl : h->d_lik, (const double*)dt, (double*)dw, (double*)dc);
+    });
 }
 
 }  // namespace
@@ -2340,6 +2390,14 @@ int fbus_ekf_group_fuse(fbus_ekf_t h, int G, const double* logw, double* weight,
 }
 int fbus_ekf_group_collapse_dev(fbus_ekf_t h, int G, const int32_t* src) { return group_collapse_any(h, DEV, G, src); }
 int fbus_ekf_group_collapse(fbus_ekf_t h, int G, const int32_t* src) { return group_collapse_any(h, STAGED, G, src); }
+int fbus_ekf_group_mix_dev(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc)
+{
+    return group_mix_any(h, DEV, G, logw, trans, weight, logc);
+}
+int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc)
+{
+    return group_mix_any(h, STAGED, G, logw, trans, weight, logc);
+}
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,
                              void* nis, int32_t* dof)

@@ -163,6 +163,8 @@ def load_library():
         "fbus_ekf_group_fuse_dev": ([H, C.c_int, vp, vp, ip, vp, vp, vp], C.c_int),
         "fbus_ekf_group_collapse": ([H, C.c_int, ip], C.c_int),
         "fbus_ekf_group_collapse_dev": ([H, C.c_int, ip], C.c_int),
+        "fbus_ekf_group_mix": ([H, C.c_int, vp, vp, vp, vp], C.c_int),
+        "fbus_ekf_group_mix_dev": ([H, C.c_int, vp, vp, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

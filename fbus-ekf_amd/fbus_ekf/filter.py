@@ -16,6 +16,7 @@ import ctypes as C
 import numpy as np
 
 from . import capi
+from . import noise
 from .noise import COLUMNS
 
 
@@ -459,6 +460,19 @@ class BatchedFilter:
             raise ValueError(f"{where}: G = {G} does not divide the batch of {self.B} into groups of 2..{capi.GROUP_MAX}")
         return G, self.B // G
 
+    def _group_logw(self, logw, dev, where):
+        """logw of a group call on the device: None stays None (the handle's likelihood sums), a float64 device tensor is checked,
+        anything else is staged"""
+        import torch
+        if logw is None:
+            return None
+        if _is_dev(logw):
+            if logw.dtype != torch.float64 or not logw.is_cuda:
+                raise ValueError(f"{where}: logw must be a float64 device tensor, got {logw.dtype} on {logw.device}")
+        else:
+            logw = torch.from_numpy(np.ascontiguousarray(logw, np.float64).ravel()).to(dev)
+        return self._dev_checked(logw, self.B, "logw")
+
     def group_fuse(self, G, logw=None, full_cov=True):
         """Evidence-weighted, moment-matched fusion of every contiguous group of G filters (fbus_ekf_group_fuse_dev): returns
         (weight (B,) float64, best (B/G,) int32, nominal (B/G, 19), P (B/G, N, N) or None, pdiag (B/G, N)), torch tensors on the
@@ -469,13 +483,7 @@ class BatchedFilter:
         G, NG = self._group_count(G, "group_fuse_dev")
         dev = torch.device("cuda", self.device)
         tt = torch.float32 if self.dtype == 32 else torch.float64
-        if logw is not None:
-            if _is_dev(logw):
-                if logw.dtype != torch.float64 or not logw.is_cuda:
-                    raise ValueError(f"group_fuse: logw must be a float64 device tensor, got {logw.dtype} on {logw.device}")
-            else:
-                logw = torch.from_numpy(np.ascontiguousarray(logw, np.float64).ravel()).to(dev)
-            self._dev_checked(logw, self.B, "logw")
+        logw = self._group_logw(logw, dev, "group_fuse")
         out = (torch.empty(self.B, dtype=torch.float64, device=dev), torch.empty(NG, dtype=torch.int32, device=dev),
                torch.empty((NG, 19), dtype=tt, device=dev),
                torch.empty((NG, self.N, self.N), dtype=tt, device=dev) if full_cov else None,
@@ -503,6 +511,43 @@ class BatchedFilter:
             return self._order_out(cur)
         src = self._host(src, (NG,), np.int32)
         self._check(self._lib.fbus_ekf_group_collapse(self._h, G, self._p(src)), "group_collapse")
+
+    def group_mix(self, G, trans, logw=None):
+        """The IMM mixing step on every contiguous group of G filters, in place (fbus_ekf_group_mix_dev): every member is re-initialised
+        from the mixture of its group's members with the weights W_ij = trans[i][j] mu_i / c_j, in the chart of the best member.
+        Returns (weight (B,) float64 = mu, logc (B,) float64 = log c_j, the predicted model probabilities), torch tensors on the
+        handle's device, stream-ordered.  logw as in group_fuse.  trans: (G, G), trans[i][j] = the probability that model i is
+        followed by model j (noise.imm_transition) -- a float64 device tensor goes in as it is, uninspected; anything np.asarray takes
+        is held to the host form's rule (finite, >= 0, rows summing to 1: noise.check_transition) and then staged.  A target nothing
+        leads to (c_j = 0) and a group without a usable member keep their bytes, logc = -inf; trans = I changes nothing.  prev_id,
+        the applied flags, the likelihood sums and the noise table are not touched.  The cycle, all on the device:
+
+            logc = log prior
+            loop:
+                loglik_reset()
+                a window of frames
+                logw = logc + loglik(device=True)[0]
+                group_fuse(G, logw)                      -> the output estimate
+                weight, logc = group_mix(G, trans, logw)
+        """
+        import torch
+        G, _ = self._group_count(G, "group_mix_dev")
+        dev = torch.device("cuda", self.device)
+        if trans is None:
+            self._check(self._lib.fbus_ekf_group_mix_dev(self._h, G, None, None, None, None), "group_mix_dev")
+        if _is_dev(trans):
+            if trans.dtype != torch.float64 or not trans.is_cuda:
+                raise ValueError(f"group_mix: trans must be a float64 device tensor, got {trans.dtype} on {trans.device}")
+        else:
+            trans = torch.from_numpy(noise.check_transition(trans, G)).to(dev)
+        self._dev_checked(trans, G * G, "trans")
+        logw = self._group_logw(logw, dev, "group_mix")
+        out = (torch.empty(self.B, dtype=torch.float64, device=dev), torch.empty(self.B, dtype=torch.float64, device=dev))
+        self._keep += list(out)
+        cur = self._order_in(logw, trans, *out)
+        self._check(self._lib.fbus_ekf_group_mix_dev(self._h, G, self._p(logw), self._p(trans), *(self._p(o) for o in out)), "group_mix_dev")
+        self._order_out(cur)
+        return out
 
     def _nis_outputs(self, dev_like):
         if dev_like is not None:

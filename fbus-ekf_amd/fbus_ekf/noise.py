@@ -5,7 +5,8 @@ scale factors around a parameter set and assigns it to the filters round-robin (
 hypothesis is run by B / G filters.  noise.best is the other half: the per-hypothesis sum of the filters' innovation log-likelihood
 (BatchedFilter.loglik) and its arg max -- NIS cannot rank hypotheses (it falls as the noise grows), the evidence can.
 noise.group_weights is the numpy twin of the weights BatchedFilter.group_fuse forms on the device for contiguous groups of G filters
-(the layout grid produces when G divides B).  numpy only.
+(the layout grid produces when G divides B); noise.imm_transition builds the model-transition matrix BatchedFilter.group_mix takes and
+noise.group_mix_weights is the numpy twin of the mixing weights it forms.  numpy only.
 """
 import itertools
 
@@ -92,3 +93,55 @@ def group_weights(logw, G):
             s += v
         weight[j] = e / s
     return weight.ravel(), best
+
+
+def imm_transition(G, stay):
+    """The model-transition matrix of an IMM bank of G models that keeps its model with probability `stay` and moves to each of the
+    others with equal probability: (G, G) float64, trans[i][j] = the probability that model i is followed by model j, `stay` on the
+    diagonal and (1 - stay) / (G - 1) elsewhere (every row sums to 1)."""
+    G, stay = int(G), float(stay)
+    if G < 2 or not 0.0 <= stay <= 1.0:
+        raise ValueError(f"imm_transition: G = {G} must be >= 2 and stay = {stay} a probability")
+    trans = np.full((G, G), (1.0 - stay) / (G - 1), np.float64)
+    trans[np.arange(G), np.arange(G)] = stay
+    return trans
+
+
+def check_transition(trans, G):
+    """trans as a contiguous (G, G) float64 array, refused by the rule of the host form of fbus_ekf_group_mix: every entry finite and
+    >= 0, every row sum within 1e-9 of 1.  The message names the row."""
+    t = np.ascontiguousarray(trans, np.float64)
+    G = int(G)
+    if t.shape != (G, G):
+        raise ValueError(f"trans: expected ({G}, {G}), got {t.shape}")
+    for i, row in enumerate(t):
+        if not np.isfinite(row).all() or (row < 0).any():
+            raise ValueError(f"trans: row {i} has an entry that is not finite or is negative")
+        s = 0.0
+        for v in row:
+            s += v
+        if abs(s - 1.0) > 1e-9:
+            raise ValueError(f"trans: row {i} sums to {s!r}, not to 1")
+    return t
+
+
+def group_mix_weights(logw, trans, G):
+    """The mixing weights of contiguous groups of G filters (steps 1-2 of fbus_ekf_group_mix, include/fbus_ekf.h): mu = group_weights(logw),
+    c_j = sum_i trans[i][j] mu_i summed in member order, W_ij = trans[i][j] mu_i / c_j -- the weight of source i in target j.  A target
+    with c_j == 0 (every group without a usable member among them) has logc = -inf and a zero column of W.
+    Returns (weight (B,) float64, logc (B,) float64, W (B / G, G, G) float64 indexed [group, i, j])."""
+    G = int(G)
+    trans = check_transition(trans, G)
+    weight, _ = group_weights(logw, G)
+    mu = weight.reshape(-1, G)
+    logc = np.full(mu.shape, -np.inf, np.float64)
+    W = np.zeros((mu.shape[0], G, G), np.float64)
+    for g, row in enumerate(mu):
+        for j in range(G):
+            c = 0.0
+            for i in range(G):
+                c += trans[i, j] * row[i]
+            if c > 0.0:
+                logc[g, j] = np.log(c)
+                W[g, :, j] = trans[:, j] * row / c
+    return weight, logc.ravel(), W

@@ -189,6 +189,12 @@ public:
     void group_fuse_dev(int G, const double* logw, double* weight, int32_t* best, Real* nominal, Real* P, Real* pdiag) const
     { check(fbus_ekf_group_fuse_dev(h_, G, logw, weight, best, nominal, P, pdiag), "group_fuse_dev"); }
     void group_collapse_dev(int G, const int32_t* src) { check(fbus_ekf_group_collapse_dev(h_, G, src), "group_collapse_dev"); }
+    // group_mix_dev: the IMM mixing step in place -- every member re-initialised from the mixture of its group's members under the
+    // model-transition matrix trans (G x G row-major, trans[i][j] = the probability that model i is followed by model j; uninspected)
+    // -> weight (batch(): mu), logc (batch(): log of the predicted model probability; + the next stretch's ll = the next logw); each
+    // output may be null.  The cycle: logw = logc + ll, group_fuse_dev (the output estimate), group_mix_dev, loglik_reset, frames.
+    void group_mix_dev(int G, const double* logw, const double* trans, double* weight, double* logc)
+    { check(fbus_ekf_group_mix_dev(h_, G, logw, trans, weight, logc), "group_mix_dev"); }
 
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --

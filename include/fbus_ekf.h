@@ -109,7 +109,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      (struct unchanged); added under 8 without a bump: fbus_ekf_set_noise[_dev], fbus_ekf_get_noise (per-filter noise; no
  *      existing meaning changed -- callers detect the feature by the symbol); likewise fbus_ekf_loglik_enable / _reset / _get /
  *      _get_dev (per-filter innovation log-likelihood sums; off by default, nothing routed differently until switched on) and
- *      fbus_ekf_group_fuse[_dev], fbus_ekf_group_collapse[_dev] (hypothesis groups; new kernels, nothing existing changed)
+ *      fbus_ekf_group_fuse[_dev], fbus_ekf_group_collapse[_dev], fbus_ekf_group_mix[_dev] (hypothesis groups; new kernels, nothing
+ *      existing changed)
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -592,8 +593,8 @@ int fbus_ekf_loglik_reset(fbus_ekf_t h);
 int fbus_ekf_loglik_get(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
 int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
 
-/* ---- hypothesis groups: evidence-weighted fusion and collapse (NO reference counterpart) ---------------------------------------
- * The reference runs one filter on one thread (C++/src/filter.cpp:190-250) and has no bank of hypotheses; these two calls are what a
+/* ---- hypothesis groups: evidence-weighted fusion, collapse and IMM mixing (NO reference counterpart) ---------------------------
+ * The reference runs one filter on one thread (C++/src/filter.cpp:190-250) and has no bank of hypotheses; these three calls are what a
  * multiple-model bank does with the evidence above.  Group j holds the G consecutive filters j G .. j G + G - 1 (the layout a noise
  * grid of G hypotheses has when G divides B), 2 <= G <= FBUS_GROUP_MAX, B % G == 0, any G in that range (a 3 x 3 grid is G = 9).
  * Groups are per handle.
@@ -627,15 +628,51 @@ int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* ap
  *   group's bytes alone; the device form inspects nothing and the kernel never forms an address from such a value.  NOT copied: the
  *   applied flags, the likelihood sums, the noise table and the carried IMU-EMA sample.
  *
+ * fbus_ekf_group_mix: the mixing step of the interacting-multiple-model (IMM) estimator, in place: between two stretches of
+ *   measurements every member of a group is re-initialised from a mixture of all members, weighted by the model probabilities and a
+ *   model-transition matrix.  collapse is its degenerate case (every column of the mixing matrix one-hot on one source), fuse its
+ *   rank-one case (every target gets the same mixture).
+ *   logw     [B] double, log model probabilities up to a per-group constant; NULL = the handle's likelihood sums, by the rule and with
+ *            the error of fuse
+ *   trans    [G][G] double, row-major: trans[i][j] = Pi_ij, the probability that model i is followed by model j; one matrix for all
+ *            groups of the call (a device pointer in the _dev form, a host pointer in the host form)
+ *   weight   [B] double, may be NULL: mu_i, steps 1-2 of fuse
+ *   logc     [B] double, may be NULL: log c_j, the predicted model probability -- the caller adds the next stretch's `ll` to it to get
+ *            the next logw
+ *   Members i (sources) and j (targets) of one group, in member order throughout:
+ *   1. mu_i as in steps 1-2 of fuse: usable iff logw_i is finite, exactly 0 otherwise.  No usable member: no record of the group
+ *      changes, weight = 0 and logc = -inf for all its members.
+ *   2. c_j = sum_i Pi_ij mu_i and W_ij = Pi_ij mu_i / c_j, in double.  c_j == 0 (in the device form, which inspects nothing: anything
+ *      but c_j > 0): target j keeps its bytes and logc_j = -inf.
+ *   3. The chart is the record of the best member, x* (fuse's `best`); delta_i exactly as in step 3 of fuse, in double with atan2;
+ *      m_j = sum_i W_ij delta_i.
+ *   4. Target j's new nominal state is x* with m_j injected by the update's own injection (MeasureUpdate.m:92-98), as in step 4 of
+ *      fuse.  Its carried rotation is the chart member's, bit for bit: mixing is an injection into x*, and the measurement update leaves
+ *      the carried rotation alone.  A target whose own record was NaN is thereby wholly re-seeded.  For N = 15, g is the chart's.
+ *   5. P0_j = sum_i W_ij (P_i + (delta_i - m_j)(delta_i - m_j)'), stored packed (symmetric by construction) and rounded once to the
+ *      record type.  No transport between tangent spaces, as in step 5 of fuse.
+ *   6. A source with W_ij exactly 0 is skipped, not multiplied by 0 (mu_i = 0 and Pi_ij = 0 alike: a NaN record behind it cannot
+ *      reach target j).  A target with W_jj == 1 exactly keeps its bytes: Pi = I changes nothing, bit for bit.
+ *   7. Written in place: the nominal state, the carried rotation and the packed covariance of every rewritten target.  Each member keeps
+ *      its own prev_id.  The applied flags, the likelihood sums, the noise table and the carried IMU-EMA sample are not touched.
+ *   8. Every sum runs in member order: the results do not depend on the batch size or on the group's place in it, and two runs are
+ *      bit-identical.
+ *   The cycle this enables, all on the device:  logc = log prior;  loop { loglik_reset; a window of frames; logw = logc + ll;
+ *   group_fuse(G, logw) -> the output estimate;  group_mix(G, trans, logw) -> weight, logc }.
+ *
  * The _dev forms take device pointers, are stream-ordered on the handle's stream and may be captured in a graph; the host forms stage
  * their arrays and wait.  All checks are made before anything is launched: a NULL handle is FBUS_ERR_INVALID; G out of range or
- * B % G != 0, an output that overlaps the records (the rule of fbus_ekf_snapshot_dev), src == NULL, and in the host form of collapse an
- * entry >= G are FBUS_ERR_INVALID with a fbus_ekf_last_error text.  Added under ABI 8 without a bump: detect the feature by symbol. */
+ * B % G != 0, an output that overlaps the records (the rule of fbus_ekf_snapshot_dev), src == NULL, trans == NULL, in the host form of
+ * collapse an entry >= G, and in the host form of mix a trans entry that is not finite or is negative or a row sum further than 1e-9
+ * from 1 (the text names the row) are FBUS_ERR_INVALID with a fbus_ekf_last_error text; the _dev form of mix inspects nothing.
+ * Added under ABI 8 without a bump: detect the feature by symbol. */
 #define FBUS_GROUP_MAX 64
 int fbus_ekf_group_fuse_dev(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag);
 int fbus_ekf_group_fuse(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag);
 int fbus_ekf_group_collapse_dev(fbus_ekf_t h, int G, const int32_t* src);
 int fbus_ekf_group_collapse(fbus_ekf_t h, int G, const int32_t* src);
+int fbus_ekf_group_mix_dev(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc);
+int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Cost of the hypothesis-group kernels beside fbus_ekf_snapshot_dev on the same handle: B = 65 536 filters, N = 18, fp32 and fp64 records,
-G = 4, 9 (a 3 x 3 grid: 65 536 is no multiple of 9, so that case runs 65 529 filters) and 64.  Four launches -- snapshot_dev (nominal +
-pdiag + applied), group_fuse_dev with the full P, group_fuse_dev with pdiag only, group_collapse_dev (src = best) -- ALTERNATED in one
-process and timed with device events on the handle's stream; the records are the same before every launch (collapse runs last in each
-round and the state is restored from a device copy behind it, outside the timed span).  The yardstick is the record read itself:
-bytes per filter x B, printed with each case.
+G = 4, 9 (a 3 x 3 grid: 65 536 is no multiple of 9, so that case runs 65 529 filters) and 64.  Five launches -- snapshot_dev (nominal +
+pdiag + applied), group_fuse_dev with the full P, group_fuse_dev with pdiag only, group_mix_dev (imm_transition(G, 0.9)),
+group_collapse_dev (src = best) -- ALTERNATED in one process and timed with device events on the handle's stream; the records are the
+same before every launch (behind mix and behind collapse, which write them, the state is restored from a device copy, outside the timed
+span).  The yardstick is the record read itself: bytes per filter x B, printed with each case; for mix it is collapse, which like it
+reads and writes every record.
 Prints one JSON line per (dtype, G): median, min and max microseconds per launch.
   python tools/time_group.py [--batch 65536] [--reps 40] [--warmup 5]"""
 import argparse
@@ -27,7 +28,7 @@ def main():
     ap.add_argument("--groups", type=int, nargs="+", default=[4, 9, 64])
     args = ap.parse_args()
     import torch
-    from fbus_ekf import BatchedFilter, capi, synth
+    from fbus_ekf import BatchedFilter, capi, noise, synth
     assert torch.cuda.is_available(), "time_group.py measures on a GPU"
     dev = torch.device("cuda:0")
     p = lambda t: None if t is None else C.c_void_p(t.data_ptr())
@@ -45,7 +46,8 @@ def main():
             n_d, r_d, P_d = up(nom), up(rot), up(P)
             pv_d = torch.from_numpy(np.ascontiguousarray(prev, np.int32)).to(dev)
             logw = torch.from_numpy(np.random.default_rng(G).uniform(-4.0, 0.0, B)).to(dev)
-            weight = torch.empty(B, dtype=torch.float64, device=dev)
+            trans = torch.from_numpy(noise.imm_transition(G, 0.9)).to(dev)
+            weight, logc = (torch.empty(B, dtype=torch.float64, device=dev) for _ in range(2))
             best = torch.empty(NG, dtype=torch.int32, device=dev)
             f_nom, f_P, f_pd = (torch.empty(s, dtype=tt, device=dev) for s in ((NG, 19), (NG, N, N), (NG, N)))
             s_nom, s_pd = torch.empty((B, 19), dtype=tt, device=dev), torch.empty((B, N), dtype=tt, device=dev)
@@ -59,6 +61,7 @@ def main():
                     "snapshot": lambda: lib.fbus_ekf_snapshot_dev(h, p(s_nom), p(s_pd), p(s_app)),
                     "fuse_full": lambda: lib.fbus_ekf_group_fuse_dev(h, G, p(logw), p(weight), p(best), p(f_nom), p(f_P), p(f_pd)),
                     "fuse_pdiag": lambda: lib.fbus_ekf_group_fuse_dev(h, G, p(logw), p(weight), p(best), p(f_nom), None, p(f_pd)),
+                    "mix": lambda: lib.fbus_ekf_group_mix_dev(h, G, p(logw), p(trans), p(weight), p(logc)),
                     "collapse": lambda: lib.fbus_ekf_group_collapse_dev(h, G, p(best)),
                 }
                 times = {k: [] for k in launches}
@@ -71,8 +74,9 @@ def main():
                         e1.synchronize()
                         if rep >= args.warmup:
                             times[k].append(e0.elapsed_time(e1) * 1e3)
-                    assert restore() == 0
-                    flt.sync()
+                        if k in ("mix", "collapse"):
+                            assert restore() == 0
+                            flt.sync()
                 _, bpf, total = flt.records()
             print(json.dumps({"dtype": dtype, "G": G, "B": B, "record_MB": round(bpf * B / 1e6, 1),
                               "us": {k: {"median": round(float(np.median(v)), 2), "min": round(min(v), 2), "max": round(max(v), 2)}
