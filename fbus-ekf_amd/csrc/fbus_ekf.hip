@@ -13,6 +13,7 @@
 #include "ekf_kernels.hpp"
 #include "ekf_launch.hpp"
 #include "ekf_group.hpp"
+#include "ekf_depth.hpp"
 #include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
@@ -165,6 +166,10 @@ struct fbus_ekf {
     // without a noise table d_noise then holds fbus_params' own row (lik_fill), and noise_on stays false: predict keeps its untabled kernels
     double* d_lik = nullptr;
     bool lik_on = false;
+    // the depth sensor (fbus_ekf_set_depth_sensor): handed to correct_depth_kernel by value at every launch, so a captured graph keeps
+    // the values it was captured with.  depth_set: no correct_depth* form runs before the setter has been called
+    DepthSensor depth{};
+    bool depth_set = false;
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
@@ -601,6 +606,21 @@ int group_mix_t(fbus_ekf_t h, int G, const double* logw, const double* trans, do
     return FBUS_OK;
 }
 int do_group_mix(fbus_ekf_t h, int G, const double* lw, const double* tr, double* w, double* lc) { DISPATCH2(h, group_mix_t, h, G, lw, tr, w, lc); }
+// ---- the depth update (ekf_depth.hpp): one launcher for every form; one wave per tile whatever the batch, the team setting, the noise
+// table or the likelihood switch.  The gate table is the handle's (+inf without one), the likelihood accumulator null while the sums are off
+template <typename T, int N>
+int launch_depth_t(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
+    launch_depth_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, var, var_per_filter ? 1 : 0, (const unsigned char*)skip, h->d_applied,
+                         h->depth, h->d_gate, (T*)nis, (int*)dof, h->lik_on ? h->d_lik : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_depth(fbus_ekf_t h, const void* z, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DISPATCH2(h, launch_depth_t, h, z, var, per, skip, nis, dof);
+}
 
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
 int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
@@ -1492,6 +1512,38 @@ int group_mix_any(fbus_ekf_t h, Transport t, int G, const double* logw, const do
                     out_piece(weight, B * sizeof(double), &dw), out_piece(logc, B * sizeof(double), &dc) };
     return run_pieces(h, t, pc, 4, [&] {
         return do_group_mix(h, G, dl ? (const double*)dl : h->d_lik, (const double*)dt, (double*)dw, (double*)dc);
+    });
+}
+
+// ---- the depth update: fbus_ekf_correct_depth / _dev / _async / _nis / _nis_dev ----------------------------------------------------------------
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int check_depth(fbus_ekf_t h, const char* where, const void* z, const double* var, int var_per_filter)
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (!h->depth_set) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": fbus_ekf_set_depth_sensor has not been called");
+    if (!z || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": z and var must not be NULL");
+    if (var_per_filter != 0 && var_per_filter != 1)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
+    return FBUS_OK;
+}
+// nis: an _nis form (its outputs may still be null)
+int depth_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
+              void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const char* where = t == ASYNC ? "fbus_ekf_correct_depth_async"
+                                   : nis ? (t == DEV ? "fbus_ekf_correct_depth_nis_dev" : "fbus_ekf_correct_depth_nis")
+                                         : (t == DEV ? "fbus_ekf_correct_depth_dev" : "fbus_ekf_correct_depth");
+    const int rc = check_depth(h, where, z, var, var_per_filter);
+    if (rc != FBUS_OK) return rc;
+    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    const size_t B = (size_t)h->B;
+    const void *dz, *dv, *ds;
+    void *dn, *dd;
+    Piece pc[5] = { in_piece(z, B * esize(h), &dz), in_piece(var, (var_per_filter ? B : 1) * sizeof(double), &dv), in_piece(skip, B, &ds),
+                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
+    return run_pieces(h, t, pc, 5, [&] {
+        return launch_depth(h, dz, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
     });
 }
 
@@ -2397,6 +2449,47 @@ int fbus_ekf_group_mix_dev(fbus_ekf_t h, int G, const double* logw, const double
 int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc)
 {
     return group_mix_any(h, STAGED, G, logw, trans, weight, logc);
+}
+
+int fbus_ekf_set_depth_sensor(fbus_ekf_t h, const double axis[3], double offset, const double lever[3])
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_depth_sensor: not between graph_begin and graph_end");
+    if (!axis) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_depth_sensor: axis must not be NULL");
+    const double n = std::sqrt(axis[0] * axis[0] + axis[1] * axis[1] + axis[2] * axis[2]);
+    if (!std::isfinite(n) || !(n > 0.0)) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_depth_sensor: axis must be finite and not zero");
+    if (!std::isfinite(offset)) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_depth_sensor: offset must be finite");
+    if (lever && !(std::isfinite(lever[0]) && std::isfinite(lever[1]) && std::isfinite(lever[2])))
+        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_depth_sensor: lever must be finite");
+    for (int i = 0; i < 3; ++i) {
+        h->depth.axis[i] = axis[i] / n;
+        h->depth.lever[i] = lever ? lever[i] : 0.0;
+    }
+    h->depth.offset = offset;
+    h->depth_set = true;
+    return FBUS_OK;
+}
+int fbus_ekf_correct_depth(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return depth_any(h, STAGED, false, z, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_depth_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return depth_any(h, DEV, false, z, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_depth_async(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return depth_any(h, ASYNC, false, z, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_depth_nis(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
+                               int32_t* dof)
+{
+    return depth_any(h, STAGED, true, z, var, var_per_filter, skip, nis, dof);
+}
+int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
+                                   int32_t* dof)
+{
+    return depth_any(h, DEV, true, z, var, var_per_filter, skip, nis, dof);
 }
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,

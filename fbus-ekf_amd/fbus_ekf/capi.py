@@ -165,6 +165,12 @@ def load_library():
         "fbus_ekf_group_collapse_dev": ([H, C.c_int, ip], C.c_int),
         "fbus_ekf_group_mix": ([H, C.c_int, vp, vp, vp, vp], C.c_int),
         "fbus_ekf_group_mix_dev": ([H, C.c_int, vp, vp, vp, vp], C.c_int),
+        "fbus_ekf_set_depth_sensor": ([H, C.POINTER(C.c_double), C.c_double, C.POINTER(C.c_double)], C.c_int),
+        "fbus_ekf_correct_depth": ([H, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_depth_dev": ([H, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_depth_async": ([H, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_depth_nis": ([H, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_depth_nis_dev": ([H, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

@@ -38,6 +38,7 @@ class BatchedFilter:
             self._h = C.c_void_p()
             raise capi.FbusError(rc, "fbus_ekf_create", self._lib.fbus_status_string(rc).decode())
         self._keep = []          # device arrays that must outlive asynchronous launches
+        self._async_inputs = []  # host inputs of correct_depth_async (pinned ones are DMA'd in place): until async_inputs_consumed() / sync()
         # The handle starts on its own NON-BLOCKING stream: device arrays handed to predict/correct/frame must be
         # complete before the call and results are complete after sync() (or order the streams with
         # wait_stream()/signal_stream(), or share the caller's stream with set_stream()).
@@ -123,6 +124,7 @@ class BatchedFilter:
     def sync(self):
         self._check(self._lib.fbus_ekf_sync(self._h), "sync")
         self._keep.clear()
+        self._async_inputs.clear()
 
     def _order_in(self, *arrays):
         """own stream + order_streams: wait for the caller's current stream; returns it for _order_out (else None)"""
@@ -304,6 +306,7 @@ class BatchedFilter:
     def async_inputs_consumed(self):
         """every H2D copy of the _async calls so far is done: pinned input arrays may be rewritten"""
         self._check(self._lib.fbus_ekf_async_inputs_consumed(self._h), "async_inputs_consumed")
+        self._async_inputs.clear()
 
     def async_stats(self):
         a, b, c = C.c_int64(), C.c_int64(), C.c_int64()
@@ -548,6 +551,72 @@ class BatchedFilter:
         self._check(self._lib.fbus_ekf_group_mix_dev(self._h, G, self._p(logw), self._p(trans), *(self._p(o) for o in out)), "group_mix_dev")
         self._order_out(cur)
         return out
+
+    # ---- depth (pressure) sensor update (include/fbus_ekf.h; no reference counterpart) ---------------------------------------
+    def set_depth_sensor(self, axis, offset=0.0, lever=None):
+        """The handle's depth sensor (fbus_ekf_set_depth_sensor): axis = the world-frame direction along which the reading grows
+        (normalised by the library; zero or non-finite is refused), offset = the reading at the world origin, lever = the sensor's
+        position in the IMU frame (None: 0).  A captured graph keeps the values it was captured with.  No correct_depth* form runs
+        before this has been called."""
+        ax = (C.c_double * 3)(*np.asarray(axis, np.float64).reshape(3))
+        lv = None if lever is None else (C.c_double * 3)(*np.asarray(lever, np.float64).reshape(3))
+        self._check(self._lib.fbus_ekf_set_depth_sensor(self._h, ax, float(offset), lv), "fbus_ekf_set_depth_sensor")
+
+    def _depth(self, z, var, skip, nis=False, transport=None):
+        """One depth update through fbus_ekf_correct_depth[_nis]<transport>, on _update's device / host / async branch.  var: one
+        variance or B of them, always float64."""
+        B = self.B
+        cur, out = None, ()
+        if transport is None and _is_dev(z):
+            import torch
+            transport = "_dev"
+            self._dev_checked(z, B, "z")
+            if not _is_dev(var):
+                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(z.device)
+            if var.dtype != torch.float64 or var.numel() not in (1, B):
+                raise ValueError(f"correct_depth: var must be float64 with 1 or {B} elements, got {var.dtype} x {var.numel()}")
+            self._dev_checked(var, var.numel(), "var")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            if nis:
+                out = self._nis_outputs(z)
+                self._keep += list(out)
+            cur = self._order_in(z, var, skip)
+            per = 1 if (var.numel() == B and B > 1) else 0
+        else:
+            conv = self._host_any if transport else self._host
+            transport = transport or ""
+            z = conv(z, (B,))
+            var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
+            if var.size not in (1, B):
+                raise ValueError(f"correct_depth: var must have 1 or {B} elements, got {var.size}")
+            per = 1 if (var.size == B and B > 1) else 0
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            if transport == "_async":       # pinned inputs are transferred in place: they live until async_inputs_consumed() / sync()
+                self._async_inputs += [z, var, skip]
+            if nis:
+                out = self._nis_outputs(None)
+        name = "correct_depth" + ("_nis" if nis else "") + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(z), self._p(var), per, self._p(skip), *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if nis else None
+
+    def correct_depth(self, z, var, skip=None):
+        """The depth (pressure) sensor update, one scalar row per filter: h = axis . (p + R lever) + offset, dx = P H' (z - h) / S,
+        P <- P - P H' H P / S (set_depth_sensor first).  z: (B,) readings in the handle's dtype; var: the reading's variance, one
+        float64 or (B,) of them; skip: (B,) uint8.  A filter that is skipped, whose z is not finite or whose var is not a finite
+        number > 0 is left untouched; the gate table's thr[1] (set_gate) rejects as in the *_nis updates.  Meant for the sensor's own
+        rate, between camera frames:  loop { predict_n(imu since the last reading); correct_depth(z, var) }."""
+        self._depth(z, var, skip)
+
+    def correct_depth_nis(self, z, var, skip=None):
+        """correct_depth() that also returns (nis, dof) per filter: nis = (z - h)^2 / S, dof = 1 (0 and 0 for an untouched filter)."""
+        return self._depth(z, var, skip, nis=True)
+
+    def correct_depth_async(self, z, var, skip=None):
+        """correct_depth() on host arrays without the wait (fbus_ekf_correct_depth_async)."""
+        self._depth(z, var, skip, transport="_async")
 
     def _nis_outputs(self, dev_like):
         if dev_like is not None:

@@ -11,7 +11,7 @@ import numpy as np
 
 BASE_SEED = 0xFB05EC0F
 RNG_BLOCK = 1024
-_S_STATE, _S_IMU, _S_MARK = 1 << 40, 2 << 40, 3 << 40
+_S_STATE, _S_IMU, _S_MARK, _S_DEPTH = 1 << 40, 2 << 40, 3 << 40, 4 << 40
 
 ACC_STD = np.array([0.66, 0.18, 0.53])
 GYR_STD = np.array([0.022, 0.014, 0.008])
@@ -168,6 +168,20 @@ def marker_frame(lo, hi, frame, M, nominal0, params, seed=BASE_SEED, noise=1e-3)
     quat = hq + noise * z[..., 3:]
     quat /= np.linalg.norm(quat, axis=-1, keepdims=True)
     return mids[slot].astype(np.int32), pos, quat
+
+
+def depth(lo, hi, step, nominal_true, rot_true=None, axis=(0.0, 0.0, 1.0), offset=0.0, lever=None, noise=0.01, seed=BASE_SEED):
+    """z (n,) float64: the depth (pressure) sensor's reading number `step` of filters [lo, hi) (fbus_ekf_correct_depth),
+    z = axis . (p_true + R_true lever) + offset + N(0, noise^2), axis normalised as the library normalises it.  nominal_true (n, 19)
+    carries p_true; rot_true (n, 9) the rotation (None: the one of nominal_true's quaternion).  Keyed like the other streams: any
+    shard reproduces its slice of the unsharded stream."""
+    a = np.asarray(axis, float)
+    a = a / np.linalg.norm(a)
+    lv = np.zeros(3) if lever is None else np.asarray(lever, float)
+    nominal_true = np.asarray(nominal_true, float)
+    R = q2R(nominal_true[:, 6:10]) if rot_true is None else np.asarray(rot_true, float).reshape(-1, 3, 3)
+    e = _draw(lo, hi, _S_DEPTH, step, seed, lambda r: r.normal(size=(RNG_BLOCK,)))
+    return (nominal_true[:, 0:3] + R @ lv) @ a + offset + noise * e
 
 
 def port_project(params, Xcam, right=False, iters=40):

@@ -196,6 +196,27 @@ public:
     void group_mix_dev(int G, const double* logw, const double* trans, double* weight, double* logc)
     { check(fbus_ekf_group_mix_dev(h_, G, logw, trans, weight, logc), "group_mix_dev"); }
 
+    // ---- the depth (pressure) sensor update (fbus_ekf.h; the reference names the sensor, common.hpp:16, and has no update for it).
+    // One scalar row per filter, h = axis . (p + R lever) + offset; at the sensor's own rate, between camera frames:
+    //   loop { predict_n(imu since the last reading); correct_depth(z, var); }
+    // set_depth_sensor first (axis: world frame, normalised by the library; lever: IMU frame, null = 0).  z: batch() readings; var: ONE
+    // variance or (per_filter) batch() of them, always double; a skipped filter, a non-finite z and a var that is not finite and > 0
+    // leave the filter untouched; thr[1] of set_gate's table gates every form.  nis / dof: batch() each, either may be null.
+    void set_depth_sensor(const double axis[3], double offset = 0.0, const double* lever = nullptr)
+    { check(fbus_ekf_set_depth_sensor(h_, axis, offset, lever), "fbus_ekf_set_depth_sensor"); }
+    void correct_depth(const Real* z, double var, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_depth(h_, z, &var, 0, skip), "correct_depth"); }
+    void correct_depth(const Real* z, const double* var, bool per_filter, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_depth(h_, z, var, per_filter ? 1 : 0, skip), "correct_depth"); }
+    void correct_depth_dev(const Real* z, const double* var, bool per_filter, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_depth_dev(h_, z, var, per_filter ? 1 : 0, skip), "correct_depth_dev"); }
+    void correct_depth_async(const Real* z, const double* var, bool per_filter, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_depth_async(h_, z, var, per_filter ? 1 : 0, skip), "correct_depth_async"); }
+    void correct_depth_nis(const Real* z, const double* var, bool per_filter, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_depth_nis(h_, z, var, per_filter ? 1 : 0, skip, nis, dof), "correct_depth_nis"); }
+    void correct_depth_nis_dev(const Real* z, const double* var, bool per_filter, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_depth_nis_dev(h_, z, var, per_filter ? 1 : 0, skip, nis, dof), "correct_depth_nis_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

@@ -674,6 +674,61 @@ int fbus_ekf_group_collapse(fbus_ekf_t h, int G, const int32_t* src);
 int fbus_ekf_group_mix_dev(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc);
 int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc);
 
+/* ---- depth (pressure) sensor update (NO reference counterpart) ---------------------------------------------------------------
+ * The reference names three sensors -- `namespace FBUSEKF // Underwater Vision IMU Depth EKF` (C++/include/common.hpp:16) -- and
+ * implements two: it has no depth update to follow, so the model is stated here.  predict is the IMU, correct* are vision and need
+ * a marker in view; this is the one absolute measurement a vehicle has between sightings: one scalar row per filter.
+ *
+ * The sensor, per handle, set once:
+ *   fbus_ekf_set_depth_sensor(h, axis, offset, lever)
+ *     axis    world-frame direction along which the reading grows; normalised by the host in double.  A zero or non-finite axis is
+ *             FBUS_ERR_INVALID with the reason in fbus_ekf_last_error (the previous sensor, or none, stays).
+ *     offset  the reading at the world origin (finite)
+ *     lever   the sensor's position in the IMU frame; NULL = 0
+ *   The three go to the kernel BY VALUE as doubles: a captured graph keeps the values it was captured with, whatever is set later.
+ *   Refused between graph_begin and graph_end.  Until it has been called every correct_depth* form returns FBUS_ERR_INVALID with a
+ *   fbus_ekf_last_error text that names fbus_ekf_set_depth_sensor: there is no silent default axis.
+ *
+ * The row.  R = the record's CARRIED rotation (the possibly stale, not re-orthonormalised one the pose rows use), error convention
+ * of the injection q <- q (x) dq(dtheta) (MeasureUpdate.m:92-98), error-state order p v theta ba bg [g]:
+ *     h(x)  = axis . (p + R lever) + offset
+ *     H_p   = axis'                      (columns 0..2)
+ *     H_th  = (lever x (R' axis))'       (columns 6..8)           every other column 0
+ *     res   = z - h(x)         S = H P H' + var         u = P H'  (reads the p and theta columns of P only)
+ *     dx    = u res / S  -> the update's own injection;   P <- P - u u' / S
+ * For one row the reference's literal (I - K H) P, its Joseph form and P - u u' / S are the same matrix: the kernel has the one
+ * symmetric form for both settings of fbus_params::cov_form, and does not read the dialect.  The carried rotation and prev_id are
+ * not written (MeasureUpdate writes neither).
+ *
+ *   z              [B] readings in the handle's dtype
+ *   var            the reading's variance, ALWAYS double (as the noise table): 1 value (var_per_filter = 0) or [B] (var_per_filter = 1);
+ *                  filter b with var[b] runs bit for bit what a handle with the scalar var[b] runs
+ *   skip           [B] bytes, nonzero = leave the filter alone; may be NULL
+ *   nis, dof       (_nis forms) [B] in the handle's dtype / int32; each may be NULL
+ * A filter is LEFT UNTOUCHED -- record bytes unchanged, applied = 0, nis = 0, dof = 0, likelihood sums unchanged -- when it is
+ * skipped, when z[b] is not finite, or when its var is not a finite number > 0: a per-lane decision, a bad input of one filter
+ * never reaches another.  Otherwise nis = res^2 / S, dof = 1, and the gate is exactly nis > thr[1] of the handle's gate table
+ * (fbus_ekf_set_gate; +inf without one or with a shorter one), decided before the first store, in EVERY form: a rejected filter keeps
+ * its record, applied = 0, nis and dof are still written.  While fbus_ekf_loglik_enable is on, an applied update adds
+ * -1/2 (nis + ln S + ln 2 pi) to ll, 1 to rows and 1 to applied; a rejected one adds 1 to rejected alone.  The innovation, h, S,
+ * 1 / S, nis and ll are formed in double for both record types; u and the rank-1 pass run in the record type.
+ * fbus_ekf_get_applied reports the flags of the last update, as after correct*.
+ * One kernel, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, a noise table and the
+ * likelihood switch do not change the route, and the plain, _nis and likelihood-on calls are the same code object -- records and
+ * applied are bit-equal between all five forms.
+ * The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text), sensor not set,
+ * NULL z / var, var_per_filter not 0 or 1 -- the last three with the entry point's name in fbus_ekf_last_error.
+ * _dev: device pointers, stream-ordered, capturable.  _async: host pointers through the pinned ring (the rules of
+ * fbus_ekf_predict_async).  Added under ABI 8 without a bump: detect the feature by symbol. */
+int fbus_ekf_set_depth_sensor(fbus_ekf_t h, const double axis[3], double offset, const double lever[3] /* may be NULL */);
+int fbus_ekf_correct_depth(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip);
+int fbus_ekf_correct_depth_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip);
+int fbus_ekf_correct_depth_async(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip);
+int fbus_ekf_correct_depth_nis(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
+                               void* nis, int32_t* dof);
+int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
+                                   void* nis, int32_t* dof);
+
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
  * matlab/quaternion_*.m, vector_to_crossmat.m, axisangle_to_quaternion.m and C++/include/matrix_math.hpp:26-99
