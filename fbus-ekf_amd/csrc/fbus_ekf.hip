@@ -14,6 +14,7 @@
 #include "ekf_launch.hpp"
 #include "ekf_group.hpp"
 #include "ekf_depth.hpp"
+#include "ekf_screen.hpp"
 #include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
@@ -173,8 +174,8 @@ struct fbus_ekf {
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
-    void* stage[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
-    size_t stage_cap[6] = { 0, 0, 0, 0, 0, 0 };
+    void* stage[7] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };      // (seven arrays: fbus_ekf_screen_markers)
+    size_t stage_cap[7] = { 0, 0, 0, 0, 0, 0, 0 };
     // asynchronous host-pointer entry points (fbus_ekf_predict_async / _correct_async): a ring of pinned staging slots + a copy stream
     struct AsyncSlot { void* host = nullptr; void* dev = nullptr; size_t cap = 0; hipEvent_t copied = nullptr, done = nullptr; bool busy = false; };
     static constexpr int ASYNC_SLOTS = 8;
@@ -1547,6 +1548,76 @@ int depth_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const double* 
     });
 }
 
+// ---- per-marker screening (ekf_screen.hpp): fbus_ekf_screen_markers / _dev ----------------------------------------------------------------------
+// One launcher for both forms and one route: one wave per tile whatever the batch, the team setting, the policy batch or the likelihood
+// switch.  Read-only: the records, the applied flags, the likelihood sums, the noise table and records_warm stay as they are.
+struct ScreenDst { int32_t* ids; void* nis; int32_t* dof; int32_t* kept; };
+template <typename T, int N, int D>
+int launch_screen_t(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry, const uint8_t* skip,
+                    const ScreenDst& o)
+{
+    const ScreenOut<T> out{ (int*)o.ids, (T*)o.nis, (int*)o.dof, (int*)o.kept, h->d_gate };
+    const double* noise = h->noise_on ? h->d_noise : nullptr;
+    const unsigned char* sk = (const unsigned char*)skip;
+    if (kind == FBUS_SCREEN_POSE) {
+        launch_screen_pose_k<T, N, D>(h->stream, (const T*)h->recs, h->B, M, (const int*)ids, (const T*)a, (const T*)b, noise, sk, make_dc<T>(h), out);
+    } else {
+        const bool sq = route_key(h).square_port;
+        const auto go = [&](auto kind_c, double r) {
+            launch_screen_meas_k<T, N, decltype(kind_c)::value>(h->stream, (const T*)h->recs, h->B, M, (const int*)ids, (const T*)a, (const T*)b,
+                                                                geometry, sq, h->prm.marker_size, r, noise, sk, h->d_id2slot, make_mc(h),
+                                                                make_vc<double>(h), make_vc<T>(h), out);
+        };
+        if (kind == FBUS_SCREEN_CORNERS) go(std::integral_constant<int, SCREEN_CORNERS>{}, h->prm.r_pos);
+        else if (b) go(std::integral_constant<int, SCREEN_PIX_STEREO>{}, h->prm.r_pix);
+        else go(std::integral_constant<int, SCREEN_PIX_LEFT>{}, h->prm.r_pix);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_screen(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry, const uint8_t* skip,
+                  const ScreenDst& o)
+{
+    DISPATCH(h, launch_screen_t, h, kind, M, ids, a, b, geometry, skip, o);
+}
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int screen_any(fbus_ekf_t h, Transport t, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry, const uint8_t* skip,
+               int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    const std::string where = t == DEV ? "fbus_ekf_screen_markers_dev" : "fbus_ekf_screen_markers";
+    if (kind != FBUS_SCREEN_POSE && kind != FBUS_SCREEN_PIXELS && kind != FBUS_SCREEN_CORNERS)
+        return fail(h, FBUS_ERR_INVALID, where + ": kind = " + std::to_string(kind) + " is none of FBUS_SCREEN_POSE / _PIXELS / _CORNERS");
+    if (M < 1 || M > FBUS_MAX_VISIBLE)
+        return fail(h, FBUS_ERR_INVALID, where + ": M = " + std::to_string(M) + " outside 1.." + std::to_string(FBUS_MAX_VISIBLE));
+    if (!ids || !a) return fail(h, FBUS_ERR_INVALID, where + ": ids and a must not be NULL");
+    const bool c3d = kind == FBUS_SCREEN_CORNERS && geometry == FBUS_VIS_CORNERS3D;
+    if (kind == FBUS_SCREEN_CORNERS && !geometry_ok(geometry)) return fail(h, FBUS_ERR_UNSUPPORTED, where + ": unknown geometry");
+    if ((kind == FBUS_SCREEN_POSE || (kind == FBUS_SCREEN_CORNERS && !c3d)) && !b)
+        return fail(h, FBUS_ERR_INVALID, where + ": b must not be NULL for this kind");
+    if (kind != FBUS_SCREEN_POSE && t == DEV && !points_aligned(a, b))
+        return fail(h, FBUS_ERR_INVALID, where + ": a / b must be 16-byte aligned device pointers");
+    if (kind == FBUS_SCREEN_PIXELS && !(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, where + ": r_pix must be positive");
+    const int max_dof = kind == FBUS_SCREEN_PIXELS ? (b ? 16 : 8) : kind == FBUS_SCREEN_CORNERS ? 12 : h->prm.dialect == FBUS_DIALECT_CPP ? 7 : 3;
+    const int rc = check_gate_dof(h, max_dof, where.c_str());
+    if (rc != FBUS_OK) return rc;
+    if (t == DEV) return launch_screen(h, kind, M, ids, a, b, geometry, skip, ScreenDst{ ids_out, nis, dof, kept });
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
+    // staged: the ids go in, are screened in place and come back into ids_out
+    const size_t es = esize(h), B = (size_t)h->B, BM = B * M;
+    const size_t wa = kind == FBUS_SCREEN_POSE ? 3 : (c3d ? 12 : 8), wb = kind == FBUS_SCREEN_POSE ? 4 : 8;
+    const void *di, *da, *db, *ds;
+    void *dn, *dd, *dk;
+    Piece pc[7] = { Piece{ ids, ids_out, BM * sizeof(int32_t), &di, false }, in_piece(a, BM * wa * es, &da),
+                    in_piece(b, c3d ? 0 : BM * wb * es, &db), in_piece(skip, B, &ds), out_piece(nis, BM * es, &dn),
+                    out_piece(dof, BM * sizeof(int32_t), &dd), out_piece(kept, B * sizeof(int32_t), &dk) };
+    return run_pieces(h, t, pc, 7, [&] {
+        int32_t* io = ids_out ? const_cast<int32_t*>((const int32_t*)di) : nullptr;
+        return launch_screen(h, kind, M, (const int32_t*)di, da, db, geometry, (const uint8_t*)ds, ScreenDst{ io, dn, (int32_t*)dd, (int32_t*)dk });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -1751,7 +1822,7 @@ int fbus_ekf_destroy(fbus_ekf_t h)
     (void)hipStreamSynchronize(h->stream);
     for (auto& p : h->ev_pool) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto g : h->graphs) if (g) (void)hipGraphExecDestroy(g);
-    for (int i = 0; i < 6; ++i) if (h->stage[i]) (void)hipFree(h->stage[i]);
+    for (void* st : h->stage) if (st) (void)hipFree(st);
     if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
     for (auto& a : h->aring) {
         if (a.host) (void)hipHostFree(a.host);
@@ -2490,6 +2561,16 @@ int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* va
                                    int32_t* dof)
 {
     return depth_any(h, DEV, true, z, var, var_per_filter, skip, nis, dof);
+}
+int fbus_ekf_screen_markers(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry, const uint8_t* skip,
+                            int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept)
+{
+    return screen_any(h, STAGED, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept);
+}
+int fbus_ekf_screen_markers_dev(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry, const uint8_t* skip,
+                                int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept)
+{
+    return screen_any(h, DEV, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept);
 }
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,

@@ -640,6 +640,52 @@ class BatchedFilter:
         return self._update("correct_corners", ids, self._image_arrays(left, right, capi.MEAS_CORNERS, geometry), (geometry, mode), skip,
                             nis=True)
 
+    # ---- per-marker chi-square screening (include/fbus_ekf.h: fbus_ekf_screen_markers) ----------------------------------
+    def screen_markers(self, kind, ids, a, b=None, geometry=capi.VIS_REFRACTIVE, skip=None, inplace=False):
+        """Judges every marker slot of every filter on its own against the prior: nis_m = r_m' (H_m P H_m' + R_m)^-1 r_m of the rows
+        the kind's stacked update would fold for slot m alone, kept iff nis_m <= thr[dof_m] of the gate table (set_gate; no table:
+        only a NaN is dropped).  kind: capi.SCREEN_POSE (a, b = pos, quat), SCREEN_PIXELS (left, right or None) or SCREEN_CORNERS
+        (left, right under `geometry`).  Returns (ids_out, nis, dof, kept): ids with -1 in the dropped slots -- hand it to the update
+        in place of ids --, nis and dof (B, M), kept (B,) = the slots of the map left per filter; numpy arrays for host inputs, device
+        tensors for device inputs.  inplace: ids_out is ids itself.  Read-only: no record, flag or likelihood sum changes."""
+        B = self.B
+        if kind == capi.SCREEN_POSE:
+            arrays = self._pose_arrays(a, b)
+        elif kind in (capi.SCREEN_PIXELS, capi.SCREEN_CORNERS):
+            arrays = self._image_arrays(a, b, capi.MEAS_CORNERS if kind == capi.SCREEN_CORNERS else capi.MEAS_PIXELS, geometry)
+        else:
+            raise ValueError(f"screen_markers: kind {kind} is none of SCREEN_POSE / SCREEN_PIXELS / SCREEN_CORNERS")
+        cur = None
+        if _is_dev(ids):
+            import torch
+            transport, M = "_dev", ids.numel() // B
+            self._rows_checked(B, M, ids, arrays, skip)
+            if ids.dtype != torch.int32:
+                raise ValueError(f"screen_markers: ids must be int32, got {ids.dtype}")
+            arrs = [x for x, _, _, _ in arrays]
+            dt = torch.float32 if self.dtype == 32 else torch.float64
+            out = (ids if inplace else torch.empty((B, M), dtype=torch.int32, device=ids.device),
+                   torch.empty((B, M), dtype=dt, device=ids.device), torch.empty((B, M), dtype=torch.int32, device=ids.device),
+                   torch.empty(B, dtype=torch.int32, device=ids.device))
+            self._keep += list(out)
+            cur = self._order_in(ids, *arrs, skip)
+        else:
+            transport = ""
+            if inplace and not (isinstance(ids, np.ndarray) and ids.dtype == np.int32 and ids.flags.c_contiguous):
+                raise ValueError("screen_markers: inplace needs a contiguous int32 array")
+            ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
+            M = ids.shape[1]
+            arrs = [None if (x is None and optional) else self._host(x, (B, M, w)) for x, w, _, optional in arrays]
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            out = (ids if inplace else np.empty((B, M), np.int32), np.empty((B, M), self.np_dtype), np.empty((B, M), np.int32),
+                   np.empty(B, np.int32))
+        name = "screen_markers" + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, int(kind), M, self._p(ids), *[self._p(x) for x in arrs], int(geometry),
+                                                    self._p(skip), *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out
+
     def applied(self):
         out = np.empty(self.B, np.uint8)
         self._check(self._lib.fbus_ekf_get_applied(self._h, self._p(out)), "get_applied")

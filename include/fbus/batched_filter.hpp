@@ -217,6 +217,17 @@ public:
     void correct_depth_nis_dev(const Real* z, const double* var, bool per_filter, const uint8_t* skip, Real* nis, int32_t* dof)
     { check(fbus_ekf_correct_depth_nis_dev(h_, z, var, per_filter ? 1 : 0, skip, nis, dof), "correct_depth_nis_dev"); }
 
+    // ---- per-marker chi-square screening (fbus_ekf.h; in the place of VISION::RejectInvalidMarker, vision.cpp:825-853): every marker slot
+    // judged alone against the prior, nis_m <= thr[dof_m] of set_gate's table or its id becomes -1 in ids_out.  kind: FBUS_SCREEN_POSE
+    // (a, b = pos, quat), FBUS_SCREEN_PIXELS (left, right or null), FBUS_SCREEN_CORNERS (left, right under geometry).  ids_out (may be ids),
+    // nis, dof: batch() x M; kept: batch(); each may be null.  Read-only; hand ids_out to the update in place of ids.
+    void screen_markers(int kind, int M, const int32_t* ids, const Real* a, const Real* b, int32_t* ids_out, Real* nis = nullptr,
+                        int32_t* dof = nullptr, int32_t* kept = nullptr, int geometry = FBUS_VIS_REFRACTIVE, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_screen_markers(h_, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept), "screen_markers"); }
+    void screen_markers_dev(int kind, int M, const int32_t* ids, const Real* a, const Real* b, int32_t* ids_out, Real* nis = nullptr,
+                            int32_t* dof = nullptr, int32_t* kept = nullptr, int geometry = FBUS_VIS_REFRACTIVE, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_screen_markers_dev(h_, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept), "screen_markers_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

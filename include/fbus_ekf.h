@@ -729,6 +729,64 @@ int fbus_ekf_correct_depth_nis(fbus_ekf_t h, const void* z, const double* var, i
 int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
                                    void* nis, int32_t* dof);
 
+/* ---- per-marker chi-square screening of a frame's marker slots ----------------------------------------------------------------
+ * The reference drops single detections in front of the update (VISION::RejectInvalidMarker, C++/src/vision.cpp:825-853, called once
+ * per image at :73: a marker whose apparent motion exceeds markerMoveVelThres loses isComputePose, the rest of the frame goes on to
+ * SetDetectionResult).  The gate of the _nis forms judges the WHOLE stacked frame of a filter; this call judges every marker slot on
+ * its own -- the individual-compatibility test -- and writes a screened copy of ids with -1 in the rejected slots.  -1 means
+ * "absent" in every update, so the existing updates take that copy unchanged, and their whole-frame gate remains the joint test of
+ * the survivors.  Nothing but the four outputs is written.
+ *
+ *   kind           FBUS_SCREEN_POSE / FBUS_SCREEN_PIXELS / FBUS_SCREEN_CORNERS: the update whose rows are judged
+ *   ids            [B][M] int32, M in 1..FBUS_MAX_VISIBLE
+ *   a, b           the two measurement arrays of the kind's update, with that update's shapes and alignment rules --
+ *                  POSE: pos [B][M][3], quat [B][M][4];  PIXELS: left, right [B][M][8] each, right == NULL: the left camera only;
+ *                  CORNERS: left, right as fbus_ekf_correct_corners takes them under `geometry`
+ *   geometry       CORNERS only (FBUS_VIS_*); ignored for the other two kinds
+ *   skip           [B] bytes, nonzero = the filter is not screened; may be NULL
+ *   ids_out        [B][M] int32; may be the same pointer as ids (in place); any other overlap is the caller's error
+ *   nis, dof       [B][M] in the handle's dtype / int32
+ *   kept           [B] int32
+ *   Every output may be NULL, in which case it is not written.
+ *
+ * For filter b and slot m:
+ * 1. The slot is JUDGED iff the filter is not skipped and the slot is one the kind's stacked update would fold: its id is in the
+ *    marker map and, for pixels, at least one of its projections has non-zero weight (lies in the port's view).  An unjudged slot
+ *    gets nis = 0, dof = 0 and ids_out = ids: -1 and unknown ids pass through as they are.
+ * 2. nis_m and dof_m are exactly what the kind's _nis entry point defines for a stacked frame that holds slot m alone, evaluated at
+ *    the current record: pixels 2 per weighted projection (at most 8 per marker for the left camera, 16 for stereo); corners 12; pose
+ *    3 in the Matlab dialect (all 7 rows in S, the quaternion residual zeroed) and 7 in the C++ dialect.  Formed in double for both
+ *    record types from the 6 x 6 quantities Lam_m, b_m (the fold's information matrix and vector) and P_JJ (the p / theta block):
+ *        nis_m = w sum res^2 - b_m' (P_JJ^-1 + Lam_m)^-1 b_m  =  r_m' (H_m P H_m' + R_m)^-1 r_m
+ * 3. R comes from the filter's own row when a noise table is set (r_pix, r_pos, r_quat of fbus_ekf_set_noise), otherwise from
+ *    fbus_params.
+ * 4. The slot is KEPT iff nis_m <= thr[dof_m], thr = the handle's gate table (fbus_ekf_set_gate); without a table, or past its end
+ *    at a replay, thr is +inf.  The decision is made on the double, before the cast: a NaN nis_m (a non-finite detection) is
+ *    dropped even without a table.  A record whose p, q, R or P_JJ holds a non-finite value makes EVERY slot of the filter whose id
+ *    is in the map judged with nis = NaN, hence dropped; no other filter is touched.  A dropped slot gets ids_out = -1; its nis and
+ *    dof are still reported.
+ *    kept[b] = the number of slots of filter b whose ids_out is an id of the marker map (what a stacked update of the screened ids
+ *    folds); 0 for a skipped filter.
+ * 5. With a gate table of n entries, a call whose largest possible per-marker dof (8 x cameras for pixels, 12 for corners, 3 / 7
+ *    for pose) has no entry fails with FBUS_ERR_INVALID before anything is launched, as the _nis forms do.
+ * 6. Nothing else is written: the records stay byte-identical, and so do the applied flags, the likelihood sums, the noise table,
+ *    prev_id and the carried EMA sample.  The nearest-mode rules (the 10 m limit, the hysteresis, switch_thres) are NOT applied: the
+ *    screen is mode-agnostic, a nearest-mode update afterwards chooses among the survivors.
+ * 7. The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text); then kind, M
+ *    (1..FBUS_MAX_VISIBLE), NULL ids / a, an unknown geometry (CORNERS; FBUS_ERR_UNSUPPORTED), a NULL b where the kind needs it (POSE;
+ *    CORNERS unless FBUS_VIS_CORNERS3D), alignment (_dev, PIXELS / CORNERS: 16 bytes), r_pix <= 0 (PIXELS), the table size -- each
+ *    with the entry point's name in fbus_ekf_last_error.
+ * 8. _dev: device pointers, stream-ordered, capturable; a captured call reads the gate table current at its replay (the _nis_dev
+ *    rule).  The host form stages, launches, waits and copies back; it is refused between graph_begin and graph_end.
+ * One kernel family, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch and the likelihood switch
+ * do not change the route.  Not available inside the frame windows (a window's later frames would have to be screened at states
+ * that do not exist yet) and without an _async form.  Added under ABI 8 without a bump: detect the feature by symbol. */
+enum { FBUS_SCREEN_POSE = 0, FBUS_SCREEN_PIXELS = 1, FBUS_SCREEN_CORNERS = 2 };
+int fbus_ekf_screen_markers_dev(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry,
+                                const uint8_t* skip, int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept);
+int fbus_ekf_screen_markers(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry,
+                            const uint8_t* skip, int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept);
+
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
  * matlab/quaternion_*.m, vector_to_crossmat.m, axisangle_to_quaternion.m and C++/include/matrix_math.hpp:26-99
