@@ -14,6 +14,7 @@
 #include "ekf_launch.hpp"
 #include "ekf_group.hpp"
 #include "ekf_depth.hpp"
+#include "ekf_velocity.hpp"
 #include "ekf_screen.hpp"
 #include "ekf_route.hpp"
 
@@ -171,6 +172,10 @@ struct fbus_ekf {
     // the values it was captured with.  depth_set: no correct_depth* form runs before the setter has been called
     DepthSensor depth{};
     bool depth_set = false;
+    // the velocity sensor (fbus_ekf_set_velocity_sensor), by value at every launch as the depth sensor is; velocity_set: no
+    // correct_velocity* form runs before the setter has been called
+    VelocitySensor velocity{};
+    bool velocity_set = false;
     void* d_ema_carry = nullptr;        // B x 6, previous EMA-filtered IMU sample
     bool ema_has_carry = false;
     // staging for the host-pointer entry points (grown on demand)
@@ -621,6 +626,21 @@ int launch_depth_t(fbus_ekf_t h, const void* z, const double* var, int var_per_f
 int launch_depth(fbus_ekf_t h, const void* z, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
 {
     DISPATCH2(h, launch_depth_t, h, z, var, per, skip, nis, dof);
+}
+// ---- the velocity update (ekf_velocity.hpp): one launcher for every form, one route, as the depth update's
+template <typename T, int N>
+int launch_velocity_t(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
+                      int32_t* dof)
+{
+    h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
+    launch_velocity_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, (const T*)gyro, var, var_per_filter ? 1 : 0, (const unsigned char*)skip,
+                            h->d_applied, h->velocity, h->d_gate, (T*)nis, (int*)dof, h->lik_on ? h->d_lik : nullptr);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_velocity(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DISPATCH2(h, launch_velocity_t, h, z, gyro, var, per, skip, nis, dof);
 }
 
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
@@ -1545,6 +1565,39 @@ int depth_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const double* 
                     out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
     return run_pieces(h, t, pc, 5, [&] {
         return launch_depth(h, dz, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
+    });
+}
+
+// ---- the velocity update: fbus_ekf_correct_velocity / _dev / _async / _nis / _nis_dev ----------------------------------------------------------
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int check_velocity(fbus_ekf_t h, const char* where, const void* z, const double* var, int var_per_filter)
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (!h->velocity_set) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": fbus_ekf_set_velocity_sensor has not been called");
+    if (!z || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": z and var must not be NULL");
+    if (var_per_filter != 0 && var_per_filter != 1)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
+    return FBUS_OK;
+}
+// nis: an _nis form (its outputs may still be null)
+int velocity_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const void* gyro, const double* var, int var_per_filter,
+                 const uint8_t* skip, void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const char* where = t == ASYNC ? "fbus_ekf_correct_velocity_async"
+                                   : nis ? (t == DEV ? "fbus_ekf_correct_velocity_nis_dev" : "fbus_ekf_correct_velocity_nis")
+                                         : (t == DEV ? "fbus_ekf_correct_velocity_dev" : "fbus_ekf_correct_velocity");
+    const int rc = check_velocity(h, where, z, var, var_per_filter);
+    if (rc != FBUS_OK) return rc;
+    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    const size_t B = (size_t)h->B;
+    const void *dz, *dg, *dv, *ds;
+    void *dn, *dd;
+    Piece pc[6] = { in_piece(z, B * 3 * esize(h), &dz), in_piece(gyro, B * 3 * esize(h), &dg),
+                    in_piece(var, (var_per_filter ? B : 1) * 3 * sizeof(double), &dv), in_piece(skip, B, &ds),
+                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
+    return run_pieces(h, t, pc, 6, [&] {
+        return launch_velocity(h, dz, dg, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
     });
 }
 
@@ -2571,6 +2624,51 @@ int fbus_ekf_screen_markers_dev(fbus_ekf_t h, int kind, int M, const int32_t* id
                                 int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept)
 {
     return screen_any(h, DEV, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept);
+}
+
+int fbus_ekf_set_velocity_sensor(fbus_ekf_t h, const double mount[9], const double lever[3])
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (h->capturing) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_velocity_sensor: not between graph_begin and graph_end");
+    VelocitySensor vs{};
+    for (int i = 0; i < 9; ++i) vs.C[i] = mount ? mount[i] : (i % 4 == 0 ? 1.0 : 0.0);
+    for (int i = 0; i < 9; ++i)
+        if (!std::isfinite(vs.C[i])) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_velocity_sensor: mount must be finite");
+    double dev = 0.0;                               // max |C C' - I|
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            const double cct = vs.C[3 * i] * vs.C[3 * j] + vs.C[3 * i + 1] * vs.C[3 * j + 1] + vs.C[3 * i + 2] * vs.C[3 * j + 2];
+            dev = std::max(dev, std::fabs(cct - (i == j ? 1.0 : 0.0)));
+        }
+    if (!(dev <= 1e-6)) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_velocity_sensor: mount must be a rotation (max |C C' - I| <= 1e-6)");
+    if (lever && !(std::isfinite(lever[0]) && std::isfinite(lever[1]) && std::isfinite(lever[2])))
+        return fail(h, FBUS_ERR_INVALID, "fbus_ekf_set_velocity_sensor: lever must be finite");
+    for (int i = 0; i < 3; ++i) vs.lever[i] = lever ? lever[i] : 0.0;
+    h->velocity = vs;
+    h->velocity_set = true;
+    return FBUS_OK;
+}
+int fbus_ekf_correct_velocity(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return velocity_any(h, STAGED, false, z, gyro, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_velocity_dev(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return velocity_any(h, DEV, false, z, gyro, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_velocity_async(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return velocity_any(h, ASYNC, false, z, gyro, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_velocity_nis(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip,
+                                  void* nis, int32_t* dof)
+{
+    return velocity_any(h, STAGED, true, z, gyro, var, var_per_filter, skip, nis, dof);
+}
+int fbus_ekf_correct_velocity_nis_dev(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
+                                      const uint8_t* skip, void* nis, int32_t* dof)
+{
+    return velocity_any(h, DEV, true, z, gyro, var, var_per_filter, skip, nis, dof);
 }
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,

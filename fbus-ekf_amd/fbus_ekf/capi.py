@@ -174,6 +174,12 @@ def load_library():
         "fbus_ekf_correct_depth_nis_dev": ([H, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_screen_markers": ([H, C.c_int, C.c_int, ip, vp, vp, C.c_int, u8p, ip, vp, ip, ip], C.c_int),
         "fbus_ekf_screen_markers_dev": ([H, C.c_int, C.c_int, ip, vp, vp, C.c_int, u8p, ip, vp, ip, ip], C.c_int),
+        "fbus_ekf_set_velocity_sensor": ([H, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
+        "fbus_ekf_correct_velocity": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_velocity_dev": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_velocity_async": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_velocity_nis": ([H, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_velocity_nis_dev": ([H, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

@@ -38,7 +38,7 @@ class BatchedFilter:
             self._h = C.c_void_p()
             raise capi.FbusError(rc, "fbus_ekf_create", self._lib.fbus_status_string(rc).decode())
         self._keep = []          # device arrays that must outlive asynchronous launches
-        self._async_inputs = []  # host inputs of correct_depth_async (pinned ones are DMA'd in place): until async_inputs_consumed() / sync()
+        self._async_inputs = []  # host inputs of correct_depth_async / correct_velocity_async (pinned ones are DMA'd in place): until async_inputs_consumed() / sync()
         # The handle starts on its own NON-BLOCKING stream: device arrays handed to predict/correct/frame must be
         # complete before the call and results are complete after sync() (or order the streams with
         # wait_stream()/signal_stream(), or share the caller's stream with set_stream()).
@@ -617,6 +617,78 @@ class BatchedFilter:
     def correct_depth_async(self, z, var, skip=None):
         """correct_depth() on host arrays without the wait (fbus_ekf_correct_depth_async)."""
         self._depth(z, var, skip, transport="_async")
+
+    # ---- body-velocity (DVL, zero-velocity) update (include/fbus_ekf.h; no reference counterpart) ------------------------------------
+    def set_velocity_sensor(self, mount=None, lever=None):
+        """The handle's velocity sensor (fbus_ekf_set_velocity_sensor): mount = the rotation C from the IMU frame to the instrument frame
+        (3 x 3, row-major; None: the identity; refused unless max |C C' - I| <= 1e-6), lever = the instrument's position in the IMU
+        frame (None: 0).  A captured graph keeps the values it was captured with.  No correct_velocity* form runs before this has
+        been called."""
+        mt = None if mount is None else (C.c_double * 9)(*np.asarray(mount, np.float64).reshape(9))
+        lv = None if lever is None else (C.c_double * 3)(*np.asarray(lever, np.float64).reshape(3))
+        self._check(self._lib.fbus_ekf_set_velocity_sensor(self._h, mt, lv), "fbus_ekf_set_velocity_sensor")
+
+    def _velocity(self, z, gyro, var, skip, nis=False, transport=None):
+        """One velocity update through fbus_ekf_correct_velocity[_nis]<transport>, on _depth's device / host / async branch.  var: three
+        variances or B x 3 of them, always float64."""
+        B = self.B
+        cur, out = None, ()
+        if transport is None and _is_dev(z):
+            import torch
+            transport = "_dev"
+            self._dev_checked(z, 3 * B, "z")
+            if gyro is not None:
+                self._dev_checked(gyro, 3 * B, "gyro")
+            if not _is_dev(var):
+                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(z.device)
+            if var.dtype != torch.float64 or var.numel() not in (3, 3 * B):
+                raise ValueError(f"correct_velocity: var must be float64 with 3 or {B} x 3 elements, got {var.dtype} x {var.numel()}")
+            self._dev_checked(var, var.numel(), "var")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            if nis:
+                out = self._nis_outputs(z)
+                self._keep += list(out)
+            cur = self._order_in(z, gyro, var, skip)
+            per = 1 if (var.numel() == 3 * B and B > 1) else 0
+        else:
+            conv = self._host_any if transport else self._host
+            transport = transport or ""
+            z = conv(z, (B, 3))
+            gyro = None if gyro is None else conv(gyro, (B, 3))
+            var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
+            if var.size not in (3, 3 * B):
+                raise ValueError(f"correct_velocity: var must have 3 or {B} x 3 elements, got {var.size}")
+            per = 1 if (var.size == 3 * B and B > 1) else 0
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            if transport == "_async":       # pinned inputs are transferred in place: they live until async_inputs_consumed() / sync()
+                self._async_inputs += [z, gyro, var, skip]
+            if nis:
+                out = self._nis_outputs(None)
+        name = "correct_velocity" + ("_nis" if nis else "") + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(z), self._p(gyro), self._p(var), per, self._p(skip),
+                                                    *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if nis else None
+
+    def correct_velocity(self, z, var, gyro=None, skip=None):
+        """The body-velocity update (a Doppler velocity log; with z = 0 a zero-velocity update), three rows per filter:
+        h = C (R' v + (gyro - bg) x lever), dx = P H' S^-1 (z - h), P <- P - P H' S^-1 H P (set_velocity_sensor first).  z: (B, 3)
+        in the handle's dtype, the velocity in the instrument frame; var: the three variances, float64, (3,) or (B, 3); gyro: (B, 3),
+        the raw rate sample predict takes (None: the lever term is dropped and the gyro bias is not observed); skip: (B,) uint8.  A
+        filter that is skipped, has a non-finite z or gyro component or a variance that is not a finite number > 0 is left untouched;
+        the gate table's thr[3] (set_gate) rejects as in the *_nis updates.  Meant for the instrument's own rate, between camera
+        frames:  loop { predict_n(imu since the last reading); correct_velocity(z, var, gyro) }."""
+        self._velocity(z, gyro, var, skip)
+
+    def correct_velocity_nis(self, z, var, gyro=None, skip=None):
+        """correct_velocity() that also returns (nis, dof) per filter: nis = res' S^-1 res, dof = 3 (0 and 0 for an untouched filter)."""
+        return self._velocity(z, gyro, var, skip, nis=True)
+
+    def correct_velocity_async(self, z, var, gyro=None, skip=None):
+        """correct_velocity() on host arrays without the wait (fbus_ekf_correct_velocity_async)."""
+        self._velocity(z, gyro, var, skip, transport="_async")
 
     def _nis_outputs(self, dev_like):
         if dev_like is not None:

@@ -11,7 +11,7 @@ import numpy as np
 
 BASE_SEED = 0xFB05EC0F
 RNG_BLOCK = 1024
-_S_STATE, _S_IMU, _S_MARK, _S_DEPTH = 1 << 40, 2 << 40, 3 << 40, 4 << 40
+_S_STATE, _S_IMU, _S_MARK, _S_DEPTH, _S_VEL = 1 << 40, 2 << 40, 3 << 40, 4 << 40, 5 << 40
 
 ACC_STD = np.array([0.66, 0.18, 0.53])
 GYR_STD = np.array([0.022, 0.014, 0.008])
@@ -182,6 +182,23 @@ def depth(lo, hi, step, nominal_true, rot_true=None, axis=(0.0, 0.0, 1.0), offse
     R = q2R(nominal_true[:, 6:10]) if rot_true is None else np.asarray(rot_true, float).reshape(-1, 3, 3)
     e = _draw(lo, hi, _S_DEPTH, step, seed, lambda r: r.normal(size=(RNG_BLOCK,)))
     return (nominal_true[:, 0:3] + R @ lv) @ a + offset + noise * e
+
+
+def velocity(lo, hi, step, nominal_true, rot_true=None, gyro=None, mount=None, lever=None, noise=0.01, seed=BASE_SEED):
+    """z (n, 3) float64: the velocity log's reading number `step` of filters [lo, hi) (fbus_ekf_correct_velocity),
+    z = C (R_true' v_true + (gyro - bg_true) x lever) + noise N(0, I).  nominal_true (n, 19) carries v_true and bg_true; rot_true (n, 9)
+    the rotation (None: the one of nominal_true's quaternion); gyro (n, 3) the raw rate sample (None: no lever term); mount the
+    rotation C IMU -> instrument (None: identity); lever the instrument's position in the IMU frame (None: 0).  Keyed like the other
+    streams: any shard reproduces its slice of the unsharded stream."""
+    Cm = np.eye(3) if mount is None else np.asarray(mount, float).reshape(3, 3)
+    lv = np.zeros(3) if lever is None else np.asarray(lever, float)
+    nominal_true = np.asarray(nominal_true, float)
+    R = q2R(nominal_true[:, 6:10]) if rot_true is None else np.asarray(rot_true, float).reshape(-1, 3, 3)
+    y = np.einsum("bji,bj->bi", R, nominal_true[:, 3:6])
+    if gyro is not None:
+        y = y + np.cross(np.asarray(gyro, float) - nominal_true[:, 13:16], lv)
+    e = _draw(lo, hi, _S_VEL, step, seed, lambda r: r.normal(size=(RNG_BLOCK, 3)))
+    return y @ Cm.T + noise * e
 
 
 def port_project(params, Xcam, right=False, iters=40):

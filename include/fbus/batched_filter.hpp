@@ -228,6 +228,28 @@ public:
                             int32_t* dof = nullptr, int32_t* kept = nullptr, int geometry = FBUS_VIS_REFRACTIVE, const uint8_t* skip = nullptr)
     { check(fbus_ekf_screen_markers_dev(h_, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept), "screen_markers_dev"); }
 
+    // ---- the body-velocity (DVL) update (fbus_ekf.h; no reference counterpart).  Three rows per filter,
+    // h = C (R' v + (gyro - bg) x lever); at the instrument's own rate, between camera frames:
+    //   loop { predict_n(imu since the last reading); correct_velocity(z, gyro, var); }
+    // With z = 0 it is the zero-velocity update of a vehicle sitting on the bottom.  set_velocity_sensor first (mount: the rotation IMU
+    // frame -> instrument frame, row-major, null = identity; lever: IMU frame, null = 0).  z, gyro: batch() x 3 (gyro may be null: no lever
+    // term, the gyro bias is not observed); var: THREE variances or (per_filter) batch() x 3 of them, always double; a skipped filter, a
+    // non-finite z or gyro component and a var that is not finite and > 0 leave the filter untouched; thr[3] of set_gate's table gates
+    // every form.  nis / dof: batch() each, either may be null.
+    void set_velocity_sensor(const double* mount = nullptr, const double* lever = nullptr)
+    { check(fbus_ekf_set_velocity_sensor(h_, mount, lever), "fbus_ekf_set_velocity_sensor"); }
+    void correct_velocity(const Real* z, const Real* gyro, const double* var, bool per_filter = false, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_velocity(h_, z, gyro, var, per_filter ? 1 : 0, skip), "correct_velocity"); }
+    void correct_velocity_dev(const Real* z, const Real* gyro, const double* var, bool per_filter = false, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_velocity_dev(h_, z, gyro, var, per_filter ? 1 : 0, skip), "correct_velocity_dev"); }
+    void correct_velocity_async(const Real* z, const Real* gyro, const double* var, bool per_filter = false, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_velocity_async(h_, z, gyro, var, per_filter ? 1 : 0, skip), "correct_velocity_async"); }
+    void correct_velocity_nis(const Real* z, const Real* gyro, const double* var, bool per_filter, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_velocity_nis(h_, z, gyro, var, per_filter ? 1 : 0, skip, nis, dof), "correct_velocity_nis"); }
+    void correct_velocity_nis_dev(const Real* z, const Real* gyro, const double* var, bool per_filter, const uint8_t* skip, Real* nis,
+                                  int32_t* dof)
+    { check(fbus_ekf_correct_velocity_nis_dev(h_, z, gyro, var, per_filter ? 1 : 0, skip, nis, dof), "correct_velocity_nis_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

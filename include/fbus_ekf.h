@@ -110,7 +110,9 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      existing meaning changed -- callers detect the feature by the symbol); likewise fbus_ekf_loglik_enable / _reset / _get /
  *      _get_dev (per-filter innovation log-likelihood sums; off by default, nothing routed differently until switched on) and
  *      fbus_ekf_group_fuse[_dev], fbus_ekf_group_collapse[_dev], fbus_ekf_group_mix[_dev] (hypothesis groups; new kernels, nothing
- *      existing changed)
+ *      existing changed);
+ *      fbus_ekf_set_velocity_sensor, fbus_ekf_correct_velocity[_dev|_async|_nis|_nis_dev] (body-velocity update): added under 8
+ *      without a bump
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -728,6 +730,73 @@ int fbus_ekf_correct_depth_nis(fbus_ekf_t h, const void* z, const double* var, i
                                void* nis, int32_t* dof);
 int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
                                    void* nis, int32_t* dof);
+
+/* ---- body-velocity (DVL) update (NO reference counterpart) -----------------------------------------------------------------------
+ * The reference has no velocity update, so the model is stated here, as it is for depth.  Between marker sightings the depth row
+ * holds one axis of position and nothing measures velocity: the horizontal axes of p, all of v and the accelerometer bias free-run on
+ * the integrated accelerometer.  A Doppler velocity log measures the velocity of the vehicle over ground in the instrument's own
+ * frame; a zero-velocity update (ZUPT) of a vehicle sitting on the bottom is the same measurement with z = 0.
+ *
+ * The sensor, per handle, set once:
+ *   fbus_ekf_set_velocity_sensor(h, mount, lever)
+ *     mount   const double[9], row-major: the rotation C from the IMU frame to the instrument frame; NULL = identity.  Refused
+ *             (FBUS_ERR_INVALID, text in fbus_ekf_last_error, previous sensor kept) when an entry is not finite or
+ *             max |C C' - I| > 1e-6.
+ *     lever   const double[3], the instrument's position in the IMU frame; NULL = 0.  Must be finite.
+ *   Both go to the kernel BY VALUE as doubles: a captured graph keeps what it was captured with.  Refused between graph_begin and
+ *   graph_end.  Until it has been called every correct_velocity* form returns FBUS_ERR_INVALID with a fbus_ekf_last_error text that
+ *   names fbus_ekf_set_velocity_sensor: there is no silent default.
+ *
+ * The rows.  R = the record's CARRIED rotation, the one the pose rows and the depth row use; error convention of the injection
+ * q <- q (x) dq(dtheta) (MeasureUpdate.m:92-98); error-state order p v theta ba bg [g]; w = gyro - bg:
+ *     h(x)  = C (R' v + w x lever)                      3 rows
+ *     H_v   = C R'            (columns 3..5)
+ *     H_th  = C [R' v]x       (columns 6..8)
+ *     H_bg  = C [lever]x      (columns 12..14)          every other column 0
+ *     res = z - h     S = H P H' + diag(var)     U = P H' (N x 3)
+ *     dx = U S^-1 res -> the update's own injection      P <- P - U S^-1 U'
+ * Processing the three rows one after another AT THE ONE linearisation point gives the same dx, P, nis and log det S as the joint
+ * solve: u = P h_k, s_k = h_k . u + var_k, r_k = res_k - h_k . dx, dx += u r_k / s_k, P -= u u' / s_k; nis = sum r_k^2 / s_k and
+ * ln det S = sum ln s_k.  Either form may be the kernel's; the s_k are the squares of the Cholesky pivots of S, so "pivot" below
+ * means the same number in both forms.
+ *
+ *   z              [B][3] in the handle's dtype
+ *   gyro           [B][3] in the handle's dtype, the raw rate sample that predict takes; may be NULL: the w x lever term is then
+ *                  dropped from h and H_bg = 0 -- the columns 12..14 are then EXACTLY untouched by H
+ *   var            ALWAYS double, as for depth: 3 values (var_per_filter = 0) or [B][3] (var_per_filter = 1); filter b under
+ *                  var[b][:] runs bit for bit what a handle under those three scalars runs
+ *   skip           [B] bytes, nonzero = leave the filter alone; may be NULL
+ *   nis, dof       (_nis forms) [B] in the handle's dtype / int32; each may be NULL
+ * A filter is LEFT UNTOUCHED -- record bytes unchanged, applied = 0, nis = 0, dof = 0, likelihood sums unchanged -- when it is
+ * skipped, when a component of z is not finite, when a component of gyro is not finite (only when gyro is given), or when one of
+ * its three variances is not a finite number > 0.
+ * Otherwise dof = 3, and the update is APPLIED IFF all three pivots are > 0 and nis <= thr[3] of the handle's gate table
+ * (fbus_ekf_set_gate; +inf without one or with a shorter one); both comparisons are false for a NaN.  The decision is made before
+ * the first store, in every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (possibly NaN) and
+ * dof = 3; while fbus_ekf_loglik_enable is on it adds 1 to rejected alone.  An applied lane adds -1/2 (nis + ln det S + 3 ln 2 pi)
+ * to ll, 3 to rows and 1 to applied.
+ * h, res, S, the pivots, nis and ll are formed in double for both record types; H is rounded once to the record type.  U and the
+ * covariance pass run in double for BOTH record types, and an fp32 record's covariance elements are rounded once, when they are stored:
+ * an update that takes the velocity variance from a loose prior down to the instrument's subtracts numbers that agree in their leading
+ * digits, and in fp32 arithmetic the posterior would keep only eps32 x prior / posterior of its own size.  dx is formed in the record type.  The carried rotation and prev_id are not written; cov_form and the dialect are not
+ * read; for N = 15, g is left alone.  fbus_ekf_get_applied reports the flags of the last update, as after correct*.
+ * One kernel, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, a noise table and the
+ * likelihood switch do not change the route, and the plain, _nis and likelihood-on calls are the same code object -- records and
+ * applied are bit-equal between all five forms.  Not available inside the frame windows.
+ * The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text), sensor not set,
+ * NULL z / var, var_per_filter not 0 or 1 -- the last three with the entry point's name in fbus_ekf_last_error.
+ * _dev: device pointers, stream-ordered, capturable.  _async: host pointers through the pinned ring (the rules of
+ * fbus_ekf_predict_async).  Added under ABI 8 without a bump: detect the feature by symbol. */
+int fbus_ekf_set_velocity_sensor(fbus_ekf_t h, const double mount[9] /* may be NULL */, const double lever[3] /* may be NULL */);
+int fbus_ekf_correct_velocity(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip);
+int fbus_ekf_correct_velocity_dev(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
+                                  const uint8_t* skip);
+int fbus_ekf_correct_velocity_async(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
+                                    const uint8_t* skip);
+int fbus_ekf_correct_velocity_nis(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
+                                  const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_velocity_nis_dev(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
+                                      const uint8_t* skip, void* nis, int32_t* dof);
 
 /* ---- per-marker chi-square screening of a frame's marker slots ----------------------------------------------------------------
  * The reference drops single detections in front of the update (VISION::RejectInvalidMarker, C++/src/vision.cpp:825-853, called once
