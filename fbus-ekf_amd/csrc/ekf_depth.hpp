@@ -6,6 +6,10 @@
 //     h(x) = axis . (p + R lever) + offset      H_p = axis'      H_theta = (lever x (R' axis))'
 //     res = z - h      S = H P H' + var      u = P H'      dx = u res / S -> inject()      P <- P - u u' / S
 // For one row (I - K H) P, its Joseph form and P - u u' / S are the same matrix: one symmetric form for both cov_form settings.
+// fp32 records do this arithmetic -- u, S, the gain, the rank-1 term -- in DOUBLE and round every covariance element once, as
+// correct_velocity_kernel does: the update takes the variance along its row from the prior's to the sensor's, and P - u u' / S in fp32 keeps
+// eps32 x prior / posterior of it (a position prior of 1 m beside var = 1e-4: 2e-3 of the posterior variance, 2e-1 at 10 m).
+// fp64 records do it in the record type.
 //
 // Mapping: one filter per lane, one wave per 64-filter tile, one buffer descriptor per tile -- at every batch size.
 // A stream, as predict_kernel (K = 1) is: z, var and skip are requested first, then every record chunk in use order (nominal state,
@@ -25,6 +29,11 @@ namespace {
 
 // the sensor, by value (fbus_ekf_set_depth_sensor): unit axis, reading at the world origin, lever arm in the IMU frame
 struct DepthSensor { double axis[3], offset, lever[3]; };
+
+// one 16-byte chunk of registers made opaque where it stands (an empty asm): what was computed from it earlier is not kept alive for a
+// later use of it, and a pass over it is finished where it is written (correct_velocity_kernel uses it too)
+__device__ __forceinline__ void pin_chunk(float* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3])); }
+__device__ __forceinline__ void pin_chunk(double* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1])); }
 
 template <typename T, int N>
 struct DepthCut {
@@ -113,12 +122,14 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
                      (T)(ds.lever[1] * Rta[2] - ds.lever[2] * Rta[1]), (T)(ds.lever[2] * Rta[0] - ds.lever[0] * Rta[2]),
                      (T)(ds.lever[0] * Rta[1] - ds.lever[1] * Rta[0]) };
 #define PS(i, j) P[pidx<N>((i), (j))]
-    T u[N];
+    // A: the type of the arithmetic -- double for both record types (see the head of the file).  fp32: N doubles beside the covariance
+    using A = typename std::conditional<sizeof(T) == 4, double, T>::type;
+    A u[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
-        T acc = PS(i, jcol(0)) * H[0];
+        A acc = (A)PS(i, jcol(0)) * (A)H[0];
 #pragma unroll
-        for (int k = 1; k < 6; ++k) acc += PS(i, jcol(k)) * H[k];
+        for (int k = 1; k < 6; ++k) acc += (A)PS(i, jcol(k)) * (A)H[k];
         u[i] = acc;
     }
 #undef PS
@@ -135,12 +146,23 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
         return;
     }
     const double is = 1.0 / S;
-    const T g = (T)(res * is), dk = (T)is;
+    const A g = (A)(res * is);
+    const T dk = (T)is;
     {
         T dx[N];
 #pragma unroll
-        for (int i = 0; i < N; ++i) dx[i] = u[i] * g;
+        for (int i = 0; i < N; ++i) dx[i] = (T)(u[i] * g);
         inject<T, N>(nom, dx);
+    }
+    if constexpr (sizeof(T) == 4) {
+        // y = u / sqrt(S): the rank-1 term is y y', symmetric to the bit
+        const double rsq = sqrt(is);
+#pragma unroll
+        for (int i = 0; i < N; ++i) u[i] *= rsq;
+        // The chunks that hold P(:, J) are made opaque in front of the pass: the compiler otherwise keeps the columns it widened for u
+        // alive for it, two registers each beside the covariance they were converted from (364 registers for N = 18; 281 with it).  The
+        // EARLY chunks only -- they have landed; an asm that names a late chunk would wait for it in front of the first store.
+        static_for<0, C_J - CN>([&](auto cc) { pin_chunk(P + EPC * decltype(cc)::value); });
     }
     // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
     store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
@@ -154,7 +176,11 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
             for (int k = 0; k < EPC; ++k) {
                 constexpr int e0 = (c - CN) * EPC;
                 const int e = e0 + k;
-                if (e < L::NP) P[e] -= (u[pk_row<N>(e)] * dk) * u[pk_col<N>(e)];
+                if constexpr (sizeof(T) == 4) {
+                    if (e < L::NP) P[e] = (T)((double)P[e] - u[pk_row<N>(e)] * u[pk_col<N>(e)]);
+                } else {
+                    if (e < L::NP) P[e] -= (u[pk_row<N>(e)] * dk) * u[pk_col<N>(e)];
+                }
             }
             store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
             __builtin_amdgcn_sched_barrier(0);

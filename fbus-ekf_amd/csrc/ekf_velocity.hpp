@@ -26,6 +26,7 @@
 // order.  A lane that is skipped, has a non-finite z or gyro or a var that is not a finite number > 0, or is not applied, stores nothing
 // to its record.  No early exit in front of the loads (correct_depth_kernel's reason).
 #pragma once
+#include "ekf_depth.hpp"        // pin_chunk
 #include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
 #include "ekf_kernels.hpp"
 
@@ -37,10 +38,8 @@ struct VelocitySensor { double C[9], lever[3]; };
 
 __host__ __device__ constexpr int vcol(int k) { return k < 6 ? k + 3 : k + 6; }          // V-position -> state column
 
-// A pass whose result only the applied branch uses is sunk behind the gate by the compiler, and its u vector with it: the chunk is made
-// opaque where the pass leaves it, so every row is finished where it stands
-__device__ __forceinline__ void pin_chunk(float* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3])); }
-__device__ __forceinline__ void pin_chunk(double* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1])); }
+// pin_chunk (ekf_depth.hpp) here: a pass whose result only the applied branch uses is sunk behind the gate by the compiler, and its u
+// vector with it; the chunk is made opaque where the pass leaves it, so every row is finished where it stands.
 
 template <typename T, int N>
 struct VelocityCut {

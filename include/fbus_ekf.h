@@ -713,7 +713,10 @@ int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* tr
  * (fbus_ekf_set_gate; +inf without one or with a shorter one), decided before the first store, in EVERY form: a rejected filter keeps
  * its record, applied = 0, nis and dof are still written.  While fbus_ekf_loglik_enable is on, an applied update adds
  * -1/2 (nis + ln S + ln 2 pi) to ll, 1 to rows and 1 to applied; a rejected one adds 1 to rejected alone.  The innovation, h, S,
- * 1 / S, nis and ll are formed in double for both record types; u and the rank-1 pass run in the record type.
+ * 1 / S, nis and ll are formed in double for both record types -- and so are u = P H', the gain and the covariance pass: with fp32
+ * records every covariance element is P - u u' / S in double, rounded ONCE to the record (as in fbus_ekf_correct_velocity), because
+ * the update of a grown prior subtracts nearly equal numbers along its row (a 1 m prior beside var = 1e-4 leaves the fp32 pass 2e-3
+ * of the posterior variance, the double pass the rounding of the record, 1e-4).  fp64 records do the pass in the record type.
  * fbus_ekf_get_applied reports the flags of the last update, as after correct*.
  * One kernel, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, a noise table and the
  * likelihood switch do not change the route, and the plain, _nis and likelihood-on calls are the same code object -- records and
