@@ -15,6 +15,7 @@
 #include "ekf_group.hpp"
 #include "ekf_depth.hpp"
 #include "ekf_velocity.hpp"
+#include "ekf_rows.hpp"
 #include "ekf_screen.hpp"
 #include "ekf_route.hpp"
 
@@ -641,6 +642,29 @@ int launch_velocity_t(fbus_ekf_t h, const void* z, const void* gyro, const doubl
 int launch_velocity(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
 {
     DISPATCH2(h, launch_velocity_t, h, z, gyro, var, per, skip, nis, dof);
+}
+// ---- the general row update (ekf_rows.hpp): one launcher for every form, one route, as the velocity update's; m picks the instantiation
+template <typename T, int N>
+int launch_rows_t(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
+                  int32_t* dof)
+{
+    h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
+    const auto go = [&](auto mc) {
+        launch_rows_k<T, N, decltype(mc)::value>(h->stream, (T*)h->recs, h->B, (const T*)res, (const T*)H, var, var_per_filter ? 1 : 0,
+                                                 (const unsigned char*)skip, h->d_applied, h->d_gate, (T*)nis, (int*)dof,
+                                                 h->lik_on ? h->d_lik : nullptr);
+    };
+    switch (m) {
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    default: go(std::integral_constant<int, 3>{}); break;
+    }
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_rows(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
+{
+    DISPATCH2(h, launch_rows_t, h, m, res, H, var, per, skip, nis, dof);
 }
 
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
@@ -1598,6 +1622,39 @@ int velocity_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const void*
                     out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
     return run_pieces(h, t, pc, 6, [&] {
         return launch_velocity(h, dz, dg, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
+    });
+}
+
+// ---- the general row update: fbus_ekf_correct_rows / _dev / _nis / _nis_dev -------------------------------------------------------------------
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int check_rows(fbus_ekf_t h, const char* where, int m, const void* res, const void* H, const double* var, int var_per_filter)
+{
+    if (!h) return FBUS_ERR_INVALID;
+    if (m < 1 || m > FBUS_ROWS_MAX)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": m = " + std::to_string(m) + " outside 1.." + std::to_string(FBUS_ROWS_MAX));
+    if (!res || !H || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": res, H and var must not be NULL");
+    if (var_per_filter != 0 && var_per_filter != 1)
+        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
+    return check_gate_dof(h, m, where);           // every form is gated: the table must reach dof m
+}
+// nis: an _nis form (its outputs may still be null)
+int rows_any(fbus_ekf_t h, Transport t, bool nis, int m, const void* res, const void* H, const double* var, int var_per_filter,
+             const uint8_t* skip, void* out_nis, int32_t* out_dof)
+{
+    DeviceGuard guard_(h);
+    const char* where = nis ? (t == DEV ? "fbus_ekf_correct_rows_nis_dev" : "fbus_ekf_correct_rows_nis")
+                            : (t == DEV ? "fbus_ekf_correct_rows_dev" : "fbus_ekf_correct_rows");
+    const int rc = check_rows(h, where, m, res, H, var, var_per_filter);
+    if (rc != FBUS_OK) return rc;
+    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    const size_t B = (size_t)h->B, M = (size_t)m;
+    const void *dr, *dH, *dv, *ds;
+    void *dn, *dd;
+    Piece pc[6] = { in_piece(res, B * M * esize(h), &dr), in_piece(H, B * M * (size_t)h->N * esize(h), &dH),
+                    in_piece(var, (var_per_filter ? B : 1) * M * sizeof(double), &dv), in_piece(skip, B, &ds),
+                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
+    return run_pieces(h, t, pc, 6, [&] {
+        return launch_rows(h, m, dr, dH, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
     });
 }
 
@@ -2669,6 +2726,24 @@ int fbus_ekf_correct_velocity_nis_dev(fbus_ekf_t h, const void* z, const void* g
                                       const uint8_t* skip, void* nis, int32_t* dof)
 {
     return velocity_any(h, DEV, true, z, gyro, var, var_per_filter, skip, nis, dof);
+}
+int fbus_ekf_correct_rows(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return rows_any(h, STAGED, false, m, res, H, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_rows_dev(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip)
+{
+    return rows_any(h, DEV, false, m, res, H, var, var_per_filter, skip, nullptr, nullptr);
+}
+int fbus_ekf_correct_rows_nis(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip,
+                              void* nis, int32_t* dof)
+{
+    return rows_any(h, STAGED, true, m, res, H, var, var_per_filter, skip, nis, dof);
+}
+int fbus_ekf_correct_rows_nis_dev(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter,
+                                  const uint8_t* skip, void* nis, int32_t* dof)
+{
+    return rows_any(h, DEV, true, m, res, H, var, var_per_filter, skip, nis, dof);
 }
 
 int fbus_ekf_correct_nis_dev(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int mode, const uint8_t* skip,

@@ -28,6 +28,7 @@ GATE_MAX_DOF = 256                 # FBUS_GATE_MAX_DOF: a full gate table has 25
 NOISE_COLS = 7                     # FBUS_NOISE_COLS: q_v q_theta q_ba q_bg r_pos r_quat r_pix (fbus_ekf_set_noise)
 SCREEN_POSE, SCREEN_PIXELS, SCREEN_CORNERS = 0, 1, 2   # fbus_ekf_screen_markers: the update whose rows are judged per marker slot
 GROUP_MAX = 64                     # FBUS_GROUP_MAX: the largest hypothesis group (fbus_ekf_group_fuse / _collapse)
+ROWS_MAX = 3                       # FBUS_ROWS_MAX: the most rows of one fbus_ekf_correct_rows call
 
 
 class FbusError(RuntimeError):
@@ -180,6 +181,10 @@ def load_library():
         "fbus_ekf_correct_velocity_async": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
         "fbus_ekf_correct_velocity_nis": ([H, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_correct_velocity_nis_dev": ([H, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_rows": ([H, C.c_int, vp, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_rows_dev": ([H, C.c_int, vp, vp, vp, C.c_int, u8p], C.c_int),
+        "fbus_ekf_correct_rows_nis": ([H, C.c_int, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
+        "fbus_ekf_correct_rows_nis_dev": ([H, C.c_int, vp, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_init_gravity_bias": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_init_gravity_bias_dev": ([H, C.c_int, vp, vp], C.c_int),
         "fbus_ekf_pose_init": ([H, C.c_int, ip, vp, vp, C.c_int, u8p], C.c_int),

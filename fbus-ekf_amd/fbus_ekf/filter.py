@@ -192,6 +192,22 @@ class BatchedFilter:
         self._check(rc, "get_state")
         return nominal, rot, P, prev
 
+    def get_state_dev(self, cov=False):
+        """The state as torch tensors on the handle's device, stream-ordered, without a trip to the host (fbus_ekf_get_state_dev):
+        (nominal (B, 19), rot (B, 9)) -- the linearisation point of correct_rows, rot being the CARRIED rotation -- and, with
+        cov=True, (nominal, rot, P (B, N, N), prev_id (B,))."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        tt = torch.float32 if self.dtype == 32 else torch.float64
+        out = [torch.empty((self.B, 19), dtype=tt, device=dev), torch.empty((self.B, 9), dtype=tt, device=dev)]
+        if cov:
+            out += [torch.empty((self.B, self.N, self.N), dtype=tt, device=dev), torch.empty(self.B, dtype=torch.int32, device=dev)]
+        self._keep.extend(out)
+        cur = self._order_in(*out)
+        self._check(self._lib.fbus_ekf_get_state_dev(self._h, *(self._p(o) for o in out), *([] if cov else [None, None])), "get_state_dev")
+        self._order_out(cur)
+        return tuple(out)
+
     def reset_cov(self):
         self._check(self._lib.fbus_ekf_reset_cov(self._h), "reset_cov")
 
@@ -689,6 +705,69 @@ class BatchedFilter:
     def correct_velocity_async(self, z, var, gyro=None, skip=None):
         """correct_velocity() on host arrays without the wait (fbus_ekf_correct_velocity_async)."""
         self._velocity(z, gyro, var, skip, transport="_async")
+
+    # ---- the general linearised measurement update (include/fbus_ekf.h; no reference counterpart) ------------------------------------
+    def _rows(self, res, H, var, skip, nis=False):
+        """One row update through fbus_ekf_correct_rows[_nis][_dev], on _velocity's device / host branch.  m is read off res.shape[1];
+        var: m variances or B x m of them, always float64."""
+        B, N = self.B, self.N
+        if getattr(res, "ndim", 0) != 2 or res.shape[0] != B:
+            raise ValueError(f"correct_rows: res must be ({B}, m), got {tuple(getattr(res, 'shape', ()))}")
+        m = int(res.shape[1])
+        cur, out = None, ()
+        if _is_dev(res):
+            import torch
+            transport = "_dev"
+            dt = torch.float32 if self.dtype == 32 else torch.float64
+            if not _is_dev(H) or res.dtype != dt or H.dtype != dt:
+                raise ValueError(f"correct_rows: res and H must both be {dt} device tensors")
+            self._dev_checked(res, m * B, "res")
+            self._dev_checked(H, m * N * B, "H")
+            if not _is_dev(var):
+                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(res.device)
+            if var.dtype != torch.float64 or var.numel() not in (m, m * B):
+                raise ValueError(f"correct_rows: var must be float64 with {m} or {B} x {m} elements, got {var.dtype} x {var.numel()}")
+            self._dev_checked(var, var.numel(), "var")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            if nis:
+                out = self._nis_outputs(res)
+                self._keep += list(out)
+            cur = self._order_in(res, H, var, skip)
+            per = 1 if (var.numel() == m * B and B > 1) else 0
+        else:
+            transport = ""
+            res = self._host(res, (B, m))
+            H = self._host(H.numpy() if _is_dev(H) else H, (B, m, N))
+            var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
+            if var.size not in (m, m * B):
+                raise ValueError(f"correct_rows: var must have {m} or {B} x {m} elements, got {var.size}")
+            per = 1 if (var.size == m * B and B > 1) else 0
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            if nis:
+                out = self._nis_outputs(None)
+        name = "correct_rows" + ("_nis" if nis else "") + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, m, self._p(res), self._p(H), self._p(var), per, self._p(skip),
+                                                    *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if nis else None
+
+    def correct_rows(self, res, H, var, skip=None):
+        """The general linearised measurement update, m = res.shape[1] rows per filter (1..capi.ROWS_MAX): the caller hands over the
+        innovation res = z - h(x), (B, m), and the Jacobian rows H, (B, m, N), columns in the error-state order p v theta ba bg [g]
+        under the injection's convention R_true ~ R (I + [dtheta]x), both in the handle's dtype; the library does
+        S = H P H' + diag(var), dx = P H' S^-1 res -> its own injection, P <- P - P H' S^-1 H P, the NIS, the gate (thr[m] of
+        set_gate) and the likelihood sums.  var: the m variances, float64, (m,) or (B, m); skip: (B,) uint8.  torch device tensors
+        take the stream-ordered, capturable device form, numpy arrays are staged.  A filter that is skipped, has a non-finite
+        residual or entry of H or a variance that is not a finite number > 0 is left untouched.  fbus_ekf.rows has ready-made
+        sensors:  loop { predict_n(...); nominal, rot = get_state_dev()[:2]; res, H = rows.position_fix(nominal, rot, z);
+        correct_rows(res, H, var) }."""
+        self._rows(res, H, var, skip)
+
+    def correct_rows_nis(self, res, H, var, skip=None):
+        """correct_rows() that also returns (nis, dof) per filter: nis = res' S^-1 res, dof = m (0 and 0 for an untouched filter)."""
+        return self._rows(res, H, var, skip, nis=True)
 
     def _nis_outputs(self, dev_like):
         if dev_like is not None:

@@ -250,6 +250,21 @@ public:
                                   int32_t* dof)
     { check(fbus_ekf_correct_velocity_nis_dev(h_, z, gyro, var, per_filter ? 1 : 0, skip, nis, dof), "correct_velocity_nis_dev"); }
 
+    // ---- the general linearised measurement update (fbus_ekf.h; no reference counterpart): m = 1..FBUS_ROWS_MAX rows per filter,
+    // res [B][m] = z - h(x) and H [B][m][N] (columns p v theta ba bg [g], R_true ~ R (I + [dtheta]x)) formed by the caller at the state
+    // of get_state_dev; the library does the gain, the injection, the covariance, the NIS, the gate and the likelihood sums.
+    //   loop { predict_n(...); get_state_dev(nominal, rot, nullptr, nullptr); <rows of the sensor on the device>; correct_rows_dev(...); }
+    // No _async form: res and H are functions of the device-resident state.
+    void correct_rows(int m, const Real* res, const Real* H, const double* var, bool per_filter = false, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_rows(h_, m, res, H, var, per_filter ? 1 : 0, skip), "correct_rows"); }
+    void correct_rows_dev(int m, const Real* res, const Real* H, const double* var, bool per_filter = false, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_correct_rows_dev(h_, m, res, H, var, per_filter ? 1 : 0, skip), "correct_rows_dev"); }
+    void correct_rows_nis(int m, const Real* res, const Real* H, const double* var, bool per_filter, const uint8_t* skip, Real* nis, int32_t* dof)
+    { check(fbus_ekf_correct_rows_nis(h_, m, res, H, var, per_filter ? 1 : 0, skip, nis, dof), "correct_rows_nis"); }
+    void correct_rows_nis_dev(int m, const Real* res, const Real* H, const double* var, bool per_filter, const uint8_t* skip, Real* nis,
+                              int32_t* dof)
+    { check(fbus_ekf_correct_rows_nis_dev(h_, m, res, H, var, per_filter ? 1 : 0, skip, nis, dof), "correct_rows_nis_dev"); }
+
     // (round 5) one camera frame with the north star's update in ONE launch (device pointers): K predicts, then correct_pixels
     // (kind = FBUS_MEAS_PIXELS; right may be null = left camera) or correct_corners (FBUS_MEAS_CORNERS with its geometry / mode) --
     // filter.cpp:232-235 with the reprojection rows in place of the pose rows

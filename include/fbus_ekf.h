@@ -112,7 +112,9 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      fbus_ekf_group_fuse[_dev], fbus_ekf_group_collapse[_dev], fbus_ekf_group_mix[_dev] (hypothesis groups; new kernels, nothing
  *      existing changed);
  *      fbus_ekf_set_velocity_sensor, fbus_ekf_correct_velocity[_dev|_async|_nis|_nis_dev] (body-velocity update): added under 8
- *      without a bump
+ *      without a bump;
+ *      fbus_ekf_correct_rows[_dev|_nis|_nis_dev] (the general linearised measurement update: residual and Jacobian rows from the
+ *      caller): added under 8 without a bump
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -800,6 +802,72 @@ int fbus_ekf_correct_velocity_nis(fbus_ekf_t h, const void* z, const void* gyro,
                                   const uint8_t* skip, void* nis, int32_t* dof);
 int fbus_ekf_correct_velocity_nis_dev(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter,
                                       const uint8_t* skip, void* nis, int32_t* dof);
+
+/* ---- the general linearised measurement update (NO reference counterpart) ------------------------------------------------------
+ * Depth and body velocity are built in; a compass, an acoustic position fix, a range to a beacon and whatever else a vehicle carries
+ * are not, and do not need to be: the caller forms the innovation and the Jacobian rows of its sensor, the library does the gain, the
+ * injection, the covariance, the NIS, the gate and the likelihood on the packed records.  (fbus_ekf.rows in the Python package has
+ * three such sensors ready made: position_fix, direction, range_to.)
+ *
+ *   m              1..FBUS_ROWS_MAX rows per filter, the same for every filter of the call
+ *   res            [B][m] in the handle's dtype: the innovation z - h(x) at the current record, formed by the caller
+ *   H              [B][m][N] in the handle's dtype, N the handle's nstate (18 or 15); columns in the error-state order
+ *                  p v theta ba bg [g]; row k is d h_k / d dx under the injection's convention q <- q (x) dq(dtheta)
+ *                  (MeasureUpdate.m:92-98), i.e. R_true ~ R (I + [dtheta]x)
+ *                  res and H need only the natural alignment of the element type
+ *   var            ALWAYS double, as for depth and velocity: m values (var_per_filter = 0) or [B][m] (var_per_filter = 1); filter b
+ *                  under var[b][:] runs bit for bit what a handle under those m scalars runs
+ *   skip           [B] bytes, nonzero = leave the filter alone; may be NULL
+ *   nis, dof       (_nis forms) [B] in the handle's dtype / int32; each may be NULL
+ *
+ * The linearisation point is the caller's business: fbus_ekf_get_state_dev(h, nominal, rot, NULL, NULL) gives the nominal state and
+ * the CARRIED rotation -- the possibly stale, not re-orthonormalised one that every built-in update (pose, depth, velocity)
+ * linearises with.  A caller may form h and H with that rotation or with the rotation of the quaternion; the kernel reads neither
+ * R, the dialect nor fbus_params::cov_form.
+ *
+ *     S = H P H' + diag(var)      U = P H' (N x m)      dx = U S^-1 res -> the update's own injection      P <- P - U S^-1 U'
+ * The m rows may be processed one after another at the one linearisation point, with the orthogonalised rows of
+ * fbus_ekf_correct_velocity above: the pivots s_k are the squares of the Cholesky pivots of S, nis = sum r_k^2 / s_k
+ * = res' S^-1 res and ln det S = sum ln s_k, exactly as defined there.
+ *
+ * A filter is LEFT UNTOUCHED -- record bytes unchanged, applied = 0, nis = 0, dof = 0, likelihood sums unchanged -- when it is
+ * skipped, when one of its m residuals is not finite, when one of its m variances is not a finite number > 0, or when one of its
+ * m N entries of H is not finite: a per-lane decision, a bad input of one filter never reaches another.
+ * Otherwise dof = m, and the update is APPLIED IFF all m pivots are > 0 and nis <= thr[m] of the handle's gate table
+ * (fbus_ekf_set_gate; +inf without one); both comparisons are false for a NaN.  The decision is made before the first store, in
+ * every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (possibly NaN) and dof = m; while
+ * fbus_ekf_loglik_enable is on it adds 1 to rejected alone.  An applied lane adds -1/2 (nis + ln det S + m ln 2 pi) to ll, m to rows
+ * and 1 to applied.  A gate table of n <= m entries has no thr[m]: EVERY form then fails with FBUS_ERR_INVALID before anything is
+ * launched (the rule of the _nis updates).
+ * An all-zero row of H is legal: its pivot is var_k, it adds res_k^2 / var_k to nis and moves nothing.
+ * Not written: the carried rotation and prev_id; for N = 15, g is left alone.  fbus_ekf_get_applied reports the flags of the last
+ * update, as after correct*.
+ * Precision, as fbus_ekf_correct_velocity: S, the pivots, the orthogonalised residuals, nis and ll are formed in double for both
+ * record types; H is used as given, in the record type.  U and the covariance pass run in double for BOTH record types, and an
+ * fp32 record's covariance elements are rounded once, when they are stored; dx is formed in the record type.  (fp64 records take
+ * the sequential rows in the record type, which is double.)
+ * One kernel family, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, a noise table and the
+ * likelihood switch do not change the route, and the plain, _nis and likelihood-on calls are the same code object -- records and
+ * applied are bit-equal between all four forms.  Not available inside the frame windows.
+ * The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text), m outside
+ * 1..FBUS_ROWS_MAX, NULL res / H / var, var_per_filter not 0 or 1, a gate table that does not reach thr[m] -- the last four with
+ * the entry point's name in fbus_ekf_last_error.
+ * _dev: device pointers, stream-ordered, capturable.  The host forms stage their arrays, launch and wait; they are refused between
+ * graph_begin and graph_end.  There is NO _async form: res and H are functions of the device-resident state, so a host array of
+ * them implies the very round trip (state to the host, rows back) that the async forms exist to avoid -- a caller with that need
+ * forms its rows on the device and calls _dev.
+ * Why FBUS_ROWS_MAX is 3: for fp32 records the joint form keeps m N doubles beside the covariance, and the velocity kernel's budget
+ * at m = 3 is 442 of the 512 registers; pose-sized stacks are what fbus_ekf_correct* is for.  A sensor with more rows calls twice
+ * and relinearises in between, which is ordinary sequential EKF practice.
+ * Added under ABI 8 without a bump: detect the feature by symbol. */
+#define FBUS_ROWS_MAX 3
+int fbus_ekf_correct_rows(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip);
+int fbus_ekf_correct_rows_dev(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter,
+                              const uint8_t* skip);
+int fbus_ekf_correct_rows_nis(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter,
+                              const uint8_t* skip, void* nis, int32_t* dof);
+int fbus_ekf_correct_rows_nis_dev(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter,
+                                  const uint8_t* skip, void* nis, int32_t* dof);
 
 /* ---- per-marker chi-square screening of a frame's marker slots ----------------------------------------------------------------
  * The reference drops single detections in front of the update (VISION::RejectInvalidMarker, C++/src/vision.cpp:825-853, called once
