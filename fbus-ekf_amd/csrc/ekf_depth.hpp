@@ -18,9 +18,10 @@
 // operations retire in issue order and the waits in front of each use are the compiler's counted s_waitcnt vmcnt(n), n = the operations
 // issued behind the chunk -- forms u, S, the gate and dx, stores the injected nominal state, and then gives every covariance chunk its
 // rank-1 term and stores it, in storage order: the chunks past C_J are still arriving while the first ones go out.
-// The gate is decided before the first store; a lane that is skipped, has a non-finite z or a var that is not a finite number > 0, or is
-// rejected, leaves before it and stores nothing to its record.  No early exit in front of the loads (the compiler would sink loads into
-// the live branch, behind the stream; correct_kernel's reason).
+// The gate -- S > 0 and nis <= thr[1], both false for a NaN: the rule of correct_velocity_kernel and correct_rows_kernel with one pivot --
+// is decided before the first store; a lane that is skipped, has a non-finite z or a var that is not a finite number > 0, or is not
+// applied (a record of NaN and one with a negated covariance among them), leaves before it and stores nothing to its record.  No early
+// exit in front of the loads (the compiler would sink loads into the live branch, behind the stream; correct_kernel's reason).
 #pragma once
 #include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
 #include "ekf_kernels.hpp"
@@ -140,7 +141,7 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
     const double nisv = res * res / S;
     if (nis) nis[b] = (T)nisv;
     if (dof) dof[b] = 1;
-    if (nisv > gate) {
+    if (!(S > 0.0 && nisv <= gate)) {                   // (both comparisons are false for a NaN)
         applied[b] = 0;
         if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, S, 1);
         return;

@@ -142,7 +142,11 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
         // why).  P stays as loaded until its one pass; the rows are orthogonalised instead:
         //   w_k = P h_k - sum_{j<k} y_j (y_j . h_k),  s_k = h_k . w_k + var_k,  y_k = w_k / sqrt(s_k),  q_k = r_k / sqrt(s_k),
         //   r_k = res_k - sum_{j<k} (h_k . y_j) q_j:      P+ = P - sum y_k y_k',  dx = sum y_k q_k,  nis = sum q_k^2
+        // The roots are taken of |s_k| and the sign of s_k goes with the products (sgn_j y_j (y_j . h_k), sgn_k q_k^2), as
+        // correct_velocity_kernel does and says why: a lane with a pivot < 0 is not applied and reports nis = sum r_k^2 / s_k like the
+        // fp64 form; with every pivot > 0 the bits are those of the plain form.
         double Y[M][N], q[M];
+        bool neg[M];
         T dx[N];
         // P is made opaque in front of every row but the first and in front of the pass: the compiler otherwise keeps the elements it
         // widened for one row alive for the next, two registers each beside the covariance they were converted from
@@ -185,6 +189,7 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
                 double c = 0.0;
 #pragma unroll
                 for (int m = 0; m < N; ++m) c += (double)Hk[m] * Y[j][m];
+                c = neg[j] ? -c : c;
 #pragma unroll
                 for (int i = 0; i < N; ++i) Y[k][i] -= Y[j][i] * c;
                 r -= c * q[j];
@@ -192,14 +197,20 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
             double hph = 0.0;
 #pragma unroll
             for (int m = 0; m < N; ++m) hph += (double)Hk[m] * Y[k][m];
-            const double s = hph + varv[k], rsq = 1.0 / sqrt(s);
+            const double s = hph + varv[k], rsq = 1.0 / sqrt(fabs(s));
             pivots = pivots && s > 0.0;
+            neg[k] = s < 0.0;
             q[k] = r * rsq;
             // the row is finished HERE: arithmetic is not tied to its place by order_fence(), and without this the compiler sinks every
             // row's sums behind the requests of all the rows of H and of the nominal state (seen in the ISA: 15 global loads and the
             // nominal chunks in front of the first row, 54 + 28 registers carried through all of it)
             asm volatile("" : "+v"(q[k]));
-            nisv += q[k] * q[k];
+            // nisv += sgn_k q_k^2, written out in the order the plain sum q_0^2 + q_1^2 + q_2^2 contracts to (ll keeps its last bit):
+            // q_0^2 is fused into the rounded q_1^2, every later term is fused into the sum
+            auto sq = [&](int j) __attribute__((always_inline)) { return neg[j] ? -q[j] : q[j]; };
+            if constexpr (k == 0 && M == 1) nisv = sq(0) * q[0];
+            if constexpr (k == 1) nisv = fma(sq(0), q[0], sq(1) * q[1]);
+            if constexpr (k >= 2) nisv = fma(sq(k), q[k], nisv);
             detS *= s;
 #pragma unroll
             for (int i = 0; i < N; ++i) {

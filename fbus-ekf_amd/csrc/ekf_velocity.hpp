@@ -158,7 +158,12 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
         // are orthogonalised instead: w_k = P h_k - sum_{j<k} w_j (w_j . h_k) / s_j is the sequential form's u_k, from the ORIGINAL P.
         // Kept as y_k = w_k / sqrt(s_k):  P+ = P - sum y_k y_k',  dx = sum y_k r_k / sqrt(s_k),  r_k = res_k - sum_{j<k} (h_k . y_j) r_j / sqrt(s_j).
         // 3 N doubles beside the fp32 covariance: 256 + 186 registers for N = 18, no scratch.
-        double Y[3][N], q[3];                            // q[k] = r_k / sqrt(s_k)
+        // A pivot that is not > 0 (a record whose covariance is not positive definite) ends in "not applied", and its lane still reports
+        // nis = sum r_k^2 / s_k as the fp64 form and the header have it: the roots are taken of |s_k| and the sign of s_k goes with the
+        // products -- w_j (w_j . h_k) / s_j = sgn_j y_j (y_j . h_k), r_k^2 / s_k = sgn_k q_k^2.  With every pivot > 0 each sign is a
+        // select that keeps its operand: the same bits as without them.
+        double Y[3][N], q[3];                            // q[k] = r_k / sqrt(|s_k|)
+        bool neg[3];
         T dx[N];
         // P is made opaque in front of the pass: the compiler otherwise keeps the elements it widened for the rows alive for it, two
         // registers each beside the covariance they were converted from (188 B of scratch; 0 B with it)
@@ -183,6 +188,7 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
                 double c = 0.0;
 #pragma unroll
                 for (int m = 0; m < 9; ++m) c += (double)Hk[m] * Y[j][vcol(m)];
+                c = neg[j] ? -c : c;
 #pragma unroll
                 for (int i = 0; i < N; ++i) Y[k][i] -= Y[j][i] * c;
                 r -= c * q[j];
@@ -190,10 +196,15 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
             double hph = 0.0;
 #pragma unroll
             for (int m = 0; m < 9; ++m) hph += (double)Hk[m] * Y[k][vcol(m)];
-            const double s = hph + varv[k], rs = 1.0 / sqrt(s);
+            const double s = hph + varv[k], rs = 1.0 / sqrt(fabs(s));
             pivots = pivots && s > 0.0;
+            neg[k] = s < 0.0;
             q[k] = r * rs;
-            nisv += q[k] * q[k];
+            // nisv += sgn_k q_k^2, written out in the order the plain sum q_0^2 + q_1^2 + q_2^2 contracts to (ll keeps its last bit):
+            // q_0^2 is fused into the rounded q_1^2, every later term is fused into the sum
+            auto sq = [&](int j) __attribute__((always_inline)) { return neg[j] ? -q[j] : q[j]; };
+            if constexpr (k == 1) nisv = fma(sq(0), q[0], sq(1) * q[1]);
+            if constexpr (k >= 2) nisv = fma(sq(k), q[k], nisv);
             detS *= s;
 #pragma unroll
             for (int i = 0; i < N; ++i) {

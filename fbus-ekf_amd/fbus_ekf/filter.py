@@ -622,7 +622,8 @@ class BatchedFilter:
         """The depth (pressure) sensor update, one scalar row per filter: h = axis . (p + R lever) + offset, dx = P H' (z - h) / S,
         P <- P - P H' H P / S (set_depth_sensor first).  z: (B,) readings in the handle's dtype; var: the reading's variance, one
         float64 or (B,) of them; skip: (B,) uint8.  A filter that is skipped, whose z is not finite or whose var is not a finite
-        number > 0 is left untouched; the gate table's thr[1] (set_gate) rejects as in the *_nis updates.  Meant for the sensor's own
+        number > 0 is left untouched; otherwise the update is applied iff S > 0 and nis <= thr[1] of the gate table (set_gate), both
+        false for a NaN, as correct_velocity and correct_rows decide: a record of NaN or with S <= 0 is not applied.  Meant for the sensor's own
         rate, between camera frames:  loop { predict_n(imu since the last reading); correct_depth(z, var) }."""
         self._depth(z, var, skip)
 

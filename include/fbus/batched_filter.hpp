@@ -201,7 +201,8 @@ public:
     //   loop { predict_n(imu since the last reading); correct_depth(z, var); }
     // set_depth_sensor first (axis: world frame, normalised by the library; lever: IMU frame, null = 0).  z: batch() readings; var: ONE
     // variance or (per_filter) batch() of them, always double; a skipped filter, a non-finite z and a var that is not finite and > 0
-    // leave the filter untouched; thr[1] of set_gate's table gates every form.  nis / dof: batch() each, either may be null.
+    // leave the filter untouched; otherwise the update is applied iff S > 0 and nis <= thr[1] of set_gate's table (both false for a
+    // NaN), in every form.  nis / dof: batch() each, either may be null.
     void set_depth_sensor(const double axis[3], double offset = 0.0, const double* lever = nullptr)
     { check(fbus_ekf_set_depth_sensor(h_, axis, offset, lever), "fbus_ekf_set_depth_sensor"); }
     void correct_depth(const Real* z, double var, const uint8_t* skip = nullptr)

@@ -711,10 +711,12 @@ int fbus_ekf_group_mix(fbus_ekf_t h, int G, const double* logw, const double* tr
  *   nis, dof       (_nis forms) [B] in the handle's dtype / int32; each may be NULL
  * A filter is LEFT UNTOUCHED -- record bytes unchanged, applied = 0, nis = 0, dof = 0, likelihood sums unchanged -- when it is
  * skipped, when z[b] is not finite, or when its var is not a finite number > 0: a per-lane decision, a bad input of one filter
- * never reaches another.  Otherwise nis = res^2 / S, dof = 1, and the gate is exactly nis > thr[1] of the handle's gate table
- * (fbus_ekf_set_gate; +inf without one or with a shorter one), decided before the first store, in EVERY form: a rejected filter keeps
- * its record, applied = 0, nis and dof are still written.  While fbus_ekf_loglik_enable is on, an applied update adds
- * -1/2 (nis + ln S + ln 2 pi) to ll, 1 to rows and 1 to applied; a rejected one adds 1 to rejected alone.  The innovation, h, S,
+ * never reaches another.  Otherwise nis = res^2 / S, dof = 1, and the update is APPLIED IFF S > 0 and nis <= thr[1] of the handle's
+ * gate table (fbus_ekf_set_gate; +inf without one or with a shorter one); both comparisons are false for a NaN -- the rule of
+ * fbus_ekf_correct_velocity and fbus_ekf_correct_rows below, S being the one pivot: a record of NaN (nis is NaN) and a record whose
+ * covariance makes S <= 0 are not applied.  The decision is made before the first store, in EVERY form.  A lane that is not applied
+ * keeps its record and reports applied = 0, its nis (possibly NaN) and dof = 1.  While fbus_ekf_loglik_enable is on, an applied update
+ * adds -1/2 (nis + ln S + ln 2 pi) to ll, 1 to rows and 1 to applied; one that is not applied adds 1 to rejected alone.  The innovation, h, S,
  * 1 / S, nis and ll are formed in double for both record types -- and so are u = P H', the gain and the covariance pass: with fp32
  * records every covariance element is P - u u' / S in double, rounded ONCE to the record (as in fbus_ekf_correct_velocity), because
  * the update of a grown prior subtracts nearly equal numbers along its row (a 1 m prior beside var = 1e-4 leaves the fp32 pass 2e-3
@@ -777,7 +779,8 @@ int fbus_ekf_correct_depth_nis_dev(fbus_ekf_t h, const void* z, const double* va
  * its three variances is not a finite number > 0.
  * Otherwise dof = 3, and the update is APPLIED IFF all three pivots are > 0 and nis <= thr[3] of the handle's gate table
  * (fbus_ekf_set_gate; +inf without one or with a shorter one); both comparisons are false for a NaN.  The decision is made before
- * the first store, in every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (possibly NaN) and
+ * the first store, in every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (res' S^-1 res also
+ * where a pivot is negative, for both record types; NaN for a record of NaN) and
  * dof = 3; while fbus_ekf_loglik_enable is on it adds 1 to rejected alone.  An applied lane adds -1/2 (nis + ln det S + 3 ln 2 pi)
  * to ll, 3 to rows and 1 to applied.
  * h, res, S, the pivots, nis and ll are formed in double for both record types; H is rounded once to the record type.  U and the
@@ -835,7 +838,8 @@ int fbus_ekf_correct_velocity_nis_dev(fbus_ekf_t h, const void* z, const void* g
  * m N entries of H is not finite: a per-lane decision, a bad input of one filter never reaches another.
  * Otherwise dof = m, and the update is APPLIED IFF all m pivots are > 0 and nis <= thr[m] of the handle's gate table
  * (fbus_ekf_set_gate; +inf without one); both comparisons are false for a NaN.  The decision is made before the first store, in
- * every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (possibly NaN) and dof = m; while
+ * every form.  A lane that is not applied keeps its record and reports applied = 0, its nis (as for the velocity update: finite where
+ * a pivot is negative, NaN for a record of NaN) and dof = m; while
  * fbus_ekf_loglik_enable is on it adds 1 to rejected alone.  An applied lane adds -1/2 (nis + ln det S + m ln 2 pi) to ll, m to rows
  * and 1 to applied.  A gate table of n <= m entries has no thr[m]: EVERY form then fails with FBUS_ERR_INVALID before anything is
  * launched (the rule of the _nis updates).

@@ -36,15 +36,18 @@ def usable(z, var, skip=False):
 def correct_depth(s, n, z, var, axis, offset=0.0, lever=None, thr1=np.inf, skip=False, joseph=False):
     """One depth update of state s (modified in place when applied).  axis: as handed to fbus_ekf_set_depth_sensor (normalised here).
     Returns (applied, nis, dof, S): a skipped filter, a non-finite z and a var that is not a finite number > 0 leave the state alone with
-    (False, 0.0, 0, nan); nis > thr1 leaves it alone with (False, nis, 1, S)."""
+    (False, 0.0, 0, nan); the update is applied iff S > 0 and nis <= thr1 (both comparisons false for a NaN: the rule of
+    velocity_ref.correct_velocity and rows_ref.correct_rows with S the one pivot), anything else leaves it alone with
+    (False, nis, 1, S)."""
     if not usable(z, var, skip):
         return False, 0.0, 0, float("nan")
     a, lv = unit(axis), lever_of(lever)
     H = H_row(s, n, a, lv)
     res = float(z) - h(s, a, offset, lv)
     S = (H @ s.P @ H.T).item() + float(var)
-    nis = res * res / S
-    if nis > thr1:
+    with np.errstate(all="ignore"):
+        nis = res * res / S
+    if not (S > 0.0 and nis <= thr1):
         return False, nis, 1, S
     K = s.P @ H.T / S                                   # (n, 1)
     dx = (K * res).ravel()

@@ -355,11 +355,29 @@ def test_a_clean_lane_among_broken_records_keeps_its_bits():
     nom, rot, P = poisoned_state(st0[0], st0[1], st0[2], S, form)
     zz = z.copy()
     zz[S[form == 3]] = np.nan                                        # form (d): the input is broken, not the record
-    out = _run([nom.astype(np.float32), rot.astype(np.float32), P.astype(np.float32), st0[3]], zz, var, skip)
+    # form (c): the suite's variances (2.5e-5 .. 4e-4) straddle the prior's H P H' (0.85e-4 .. 1.4e-4), and a negated covariance under
+    # var = 4e-4 leaves S > 0: a lane the rule applies.  Under the smallest of the three every negated covariance gives S < 0.
+    vv = var.copy()
+    vv[S[form == 2]] = 2.5e-5
+    broken = [nom.astype(np.float32), rot.astype(np.float32), P.astype(np.float32), st0[3]]
+    with BatchedFilter(B, capi.default_params(1), device=0, dtype=32, nstate=18) as f:
+        f.set_state(*broken)
+        before = dict(zip(NAMES, f.get_state()))                     # the records as they were before the update
+    out = _run(broken, zz, vv, skip)
     clean = np.setdiff1d(np.arange(B), S)
     assert 100 in clean and len(np.intersect1d(clean, np.arange(64, 128))) == 1          # a whole wave but one lane
     assert same_rows(v0, out, clean, clean)
-    assert (out["applied"][S[form == 3]] == 0).all()
+    # A record of NaN (a: nis is NaN), one with a negated covariance (c: S = H P H' + var < 0) and a broken reading (d) are not applied.
+    # An infinite position with variances of 1e30 (b) and a zero rotation (e) leave S finite and positive: the header's rule -- S > 0 and
+    # nis <= thr[1] -- decides those, lane by lane.  Whatever is not applied keeps its bytes.
+    usable = (skip == 0) & np.isfinite(zz) & np.isfinite(vv) & (vv > 0)
+    for k in (0, 2, 3):
+        assert (out["applied"][S[form == k]] == 0).all(), k
+    ac = S[(form == 0) | (form == 2)]
+    assert (out["dof"][ac] == usable[ac]).all() and np.isnan(out["nis"][S[form == 0]][usable[S[form == 0]]]).all()
+    kept = S[out["applied"][S] == 0]
+    assert len(kept) >= len(S) * 3 // 5
+    assert same_rows(before, {k: out[k] for k in NAMES}, kept, kept)
 
 
 # ---- refusals -----------------------------------------------------------------------------------------------------------------------------------
