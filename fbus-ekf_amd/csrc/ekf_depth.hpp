@@ -23,18 +23,12 @@
 // applied (a record of NaN and one with a negated covariance among them), leaves before it and stores nothing to its record.  No early
 // exit in front of the loads (the compiler would sink loads into the live branch, behind the stream; correct_kernel's reason).
 #pragma once
-#include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
-#include "ekf_kernels.hpp"
+#include "ekf_sensor.hpp"       // the exits and the gate rule, store_nominal, the two covariance passes, pin_chunk, launch_tile_k
 
 namespace {
 
 // the sensor, by value (fbus_ekf_set_depth_sensor): unit axis, reading at the world origin, lever arm in the IMU frame
 struct DepthSensor { double axis[3], offset, lever[3]; };
-
-// one 16-byte chunk of registers made opaque where it stands (an empty asm): what was computed from it earlier is not kept alive for a
-// later use of it, and a pass over it is finished where it is written (correct_velocity_kernel uses it too)
-__device__ __forceinline__ void pin_chunk(float* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1]), "+v"(p[2]), "+v"(p[3])); }
-__device__ __forceinline__ void pin_chunk(double* p) { asm volatile("" : "+v"(p[0]), "+v"(p[1])); }
 
 template <typename T, int N>
 struct DepthCut {
@@ -96,16 +90,10 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
     double varv = vin;
     unsigned skv = skip ? (unsigned)skin : 0u;
     asm volatile("" : "+v"(zv), "+v"(varv), "+v"(skv));
-    // untouched lanes: no store to the record, no likelihood term.  (x > 0 is false for a NaN)
+    const SensorOut<T> o{ applied, nis, dof, lik, B, b };
+    // untouched lanes  (x > 0 is false for a NaN)
     const bool usable = in && skv == 0u && isfinite((double)zv) && isfinite(varv) && varv > 0.0;
-    if (!usable) {
-        if (in) {
-            applied[b] = 0;
-            if (nis) nis[b] = T(0);
-            if (dof) dof[b] = 0;
-        }
-        return;
-    }
+    if (!usable) return leave_untouched(o, in);
 
     // h, the innovation and the row in double (a handful of scalars per filter); the row is rounded once to the record type
     const T* R = nom + L::OFF_R;
@@ -124,7 +112,7 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
                      (T)(ds.lever[0] * Rta[1] - ds.lever[1] * Rta[0]) };
 #define PS(i, j) P[pidx<N>((i), (j))]
     // A: the type of the arithmetic -- double for both record types (see the head of the file).  fp32: N doubles beside the covariance
-    using A = typename std::conditional<sizeof(T) == 4, double, T>::type;
+    using A = SensorArith<T>;
     A u[N];
 #pragma unroll
     for (int i = 0; i < N; ++i) {
@@ -138,21 +126,16 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
 #pragma unroll
     for (int k = 0; k < 6; ++k) hph += (double)H[k] * (double)u[jcol(k)];
     const double S = hph + varv;
-    const double nisv = res * res / S;
-    if (nis) nis[b] = (T)nisv;
-    if (dof) dof[b] = 1;
-    if (!(S > 0.0 && nisv <= gate)) {                   // (both comparisons are false for a NaN)
-        applied[b] = 0;
-        if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, S, 1);
-        return;
-    }
+    const RowSums g{ res * res / S, S, S > 0.0 };       // nis, det S and the one pivot
+    report(o, g, 1);
+    if (gate_shut(g, gate)) return leave_rejected(o, g, 1);
     const double is = 1.0 / S;
-    const A g = (A)(res * is);
+    const A gn = (A)(res * is);
     const T dk = (T)is;
     {
         T dx[N];
 #pragma unroll
-        for (int i = 0; i < N; ++i) dx[i] = (T)(u[i] * g);
+        for (int i = 0; i < N; ++i) dx[i] = (T)(u[i] * gn);
         inject<T, N>(nom, dx);
     }
     if constexpr (sizeof(T) == 4) {
@@ -165,40 +148,11 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
         // EARLY chunks only -- they have landed; an asm that names a late chunk would wait for it in front of the first store.
         static_for<0, C_J - CN>([&](auto cc) { pin_chunk(P + EPC * decltype(cc)::value); });
     }
-    // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
-    store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
-    store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, my_lane(), nom + L::NPQR);
-    __builtin_amdgcn_sched_barrier(0);
-    // chunk c: its elements' rank-1 terms, then its store (prev_id and the padding behind it go back as they came)
-    auto pass = [&](auto c0c, auto c1c) __attribute__((always_inline)) {
-        static_for<decltype(c0c)::value, decltype(c1c)::value>([&](auto cc) {
-            constexpr int c = decltype(cc)::value;
-#pragma unroll
-            for (int k = 0; k < EPC; ++k) {
-                constexpr int e0 = (c - CN) * EPC;
-                const int e = e0 + k;
-                if constexpr (sizeof(T) == 4) {
-                    if (e < L::NP) P[e] = (T)((double)P[e] - u[pk_row<N>(e)] * u[pk_col<N>(e)]);
-                } else {
-                    if (e < L::NP) P[e] -= (u[pk_row<N>(e)] * dk) * u[pk_col<N>(e)];
-                }
-            }
-            store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-    };
-    pass(std::integral_constant<int, CN>{}, std::integral_constant<int, RC::NCH>{});
-    applied[b] = 1;
-    if (lik) lik_add(LikOut{ lik, B }, b, true, nisv, 0.0, S, 1);
-}
-
-// grid: one wave per tile
-template <typename T, int N>
-void launch_depth_k(hipStream_t st, T* recs, int B, const T* z, const double* var, int var_stride, const unsigned char* skip,
-                    unsigned char* applied, const DepthSensor& ds, const double* thr, T* nis, int* dof, double* lik)
-{
-    hipLaunchKernelGGL((correct_depth_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, recs, B, z, var, var_stride, skip,
-                       applied, ds, thr, nis, dof, lik);
+    store_nominal<T, N>(rs, nom);
+    // every covariance chunk takes its rank-1 term and goes out, in storage order
+    if constexpr (sizeof(T) == 4) joint_pass<T, N, 1>(rs, P, &u);
+    else rank1_pass<T, N, true>(rs, P, u, dk);
+    leave_applied(o, g, 1);
 }
 
 }  // namespace

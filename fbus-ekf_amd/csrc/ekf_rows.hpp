@@ -43,9 +43,7 @@
 // pivots > 0 and nis <= thr[M] -- is decided behind the last row's s and r, before the first store; then the injected nominal state goes
 // out and the covariance chunks follow in storage order.  No early exit in front of the record loads (correct_depth_kernel's reason).
 #pragma once
-#include "ekf_depth.hpp"        // pin_chunk
-#include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
-#include "ekf_kernels.hpp"
+#include "ekf_sensor.hpp"       // the exits and the gate rule, store_nominal, the two row steps and covariance passes, launch_tile_k
 
 namespace {
 
@@ -61,7 +59,7 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
-    constexpr int EPC = RC::EPC, CN = RC::CH_NOM;
+    constexpr int CN = RC::CH_NOM;
     static_assert(M >= 1 && M <= 3, "FBUS_ROWS_MAX");
     // The waits are the compiler's counted vmcnt.  The largest count of the fp32 forms is the wait for the 2 M + 1 input loads behind the
     // record loads (at most NCH: 57 for N = 18, M = 3); a row of H waits behind at most the one row requested after it (N).  The fp64 records have
@@ -115,56 +113,36 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
     };
     request(std::integral_constant<int, 0>{});
     order_fence();
-    // untouched lanes: no store to the record, no likelihood term.  (x > 0 is false for a NaN)
+    const SensorOut<T> o{ applied, nis, dof, lik, B, b };
+    // untouched lanes  (x > 0 is false for a NaN)
     bool usable = in && skv == 0u;
 #pragma unroll
     for (int i = 0; i < M; ++i) usable = usable && isfinite((double)rv[i]) && isfinite(varv[i]) && varv[i] > 0.0;
-    if (!usable) {
-        if (in) {
-            applied[b] = 0;
-            if (nis) nis[b] = T(0);
-            if (dof) dof[b] = 0;
-        }
-        return;
-    }
+    if (!usable) return leave_untouched(o, in);
 
-#define PS(i, j) P[pidx<N>((i), (j))]
-    double nisv = 0.0, detS = 1.0;
-    bool pivots = true, hfin = true;
-    // a lane with a non-finite entry of H is untouched too; it is known once the last row is in
-    auto untouched = [&]() __attribute__((always_inline)) {
-        applied[b] = 0;
-        if (nis) nis[b] = T(0);
-        if (dof) dof[b] = 0;
-    };
-    if constexpr (sizeof(T) == 4) {
-        // fp32 records: THE JOINT FORM, its arithmetic in double, every covariance element rounded once (correct_velocity_kernel says
-        // why).  P stays as loaded until its one pass; the rows are orthogonalised instead:
-        //   w_k = P h_k - sum_{j<k} y_j (y_j . h_k),  s_k = h_k . w_k + var_k,  y_k = w_k / sqrt(s_k),  q_k = r_k / sqrt(s_k),
-        //   r_k = res_k - sum_{j<k} (h_k . y_j) q_j:      P+ = P - sum y_k y_k',  dx = sum y_k q_k,  nis = sum q_k^2
-        // The roots are taken of |s_k| and the sign of s_k goes with the products (sgn_j y_j (y_j . h_k), sgn_k q_k^2), as
-        // correct_velocity_kernel does and says why: a lane with a pivot < 0 is not applied and reports nis = sum r_k^2 / s_k like the
-        // fp64 form; with every pivot > 0 the bits are those of the plain form.
-        double Y[M][N], q[M];
-        bool neg[M];
-        T dx[N];
-        // P is made opaque in front of every row but the first and in front of the pass: the compiler otherwise keeps the elements it
-        // widened for one row alive for the next, two registers each beside the covariance they were converted from
-        auto fresh = [&]() __attribute__((always_inline)) {
-            static_for<0, (L::NP + 3) / 4>([&](auto cc) { pin_chunk(P + 4 * decltype(cc)::value); });
-        };
-        static_for<0, M>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            __builtin_amdgcn_sched_barrier(0);
+    // The two forms of the rows (the head of the file; the steps and their reasons: ekf_sensor.hpp).  fp32: P stays as loaded until its
+    // one pass, M N doubles y_k beside it; fp64: every row but the last updates P in registers, the last row's pass stores
+    constexpr bool joint = sizeof(T) == 4;
+    double Y[M][N], q[M];                                // fp32: y_k, q_k and the signs of s_k
+    bool neg[M];
+    T u[N], dk = T(0), dx[N];                            // fp64: the u and 1 / s of the row at hand; both: dx
+    RowSums g;
+    bool hfin = true;
+    static_for<0, M>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
+        __builtin_amdgcn_sched_barrier(0);
+        if constexpr (joint) {
             if constexpr (k + 1 < M) {
                 request(std::integral_constant<int, k + 1>{});
                 order_fence();
             }
             if constexpr (k == M - 1) request_nom();       // behind this row's N^2 multiply-adds
-            if constexpr (k > 0) fresh();
-            const T* Hk = Hr[k];
+            if constexpr (k > 0) fresh<T, N>(P);           // in front of every row but the first
+        }
+        const T* Hk = Hr[k];
 #pragma unroll
-            for (int j = 0; j < N; ++j) hfin = hfin && isfinite(Hk[j]);
+        for (int j = 0; j < N; ++j) hfin = hfin && isfinite(Hk[j]);
+        if constexpr (joint) {
             // w = P h_k, element by packed element in storage order: each is widened ONCE and goes to the two sums it belongs to (one on
             // the diagonal).  A scheduling barrier per chunk: the scheduler otherwise widens the whole covariance ahead of the sums, two
             // registers an element (fp32 N = 18, M = 3 by output row: 1172 B of scratch)
@@ -183,165 +161,46 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
                 }
                 __builtin_amdgcn_sched_barrier(0);
             });
-            double r = (double)rv[k];
-#pragma unroll
-            for (int j = 0; j < k; ++j) {
-                double c = 0.0;
-#pragma unroll
-                for (int m = 0; m < N; ++m) c += (double)Hk[m] * Y[j][m];
-                c = neg[j] ? -c : c;
-#pragma unroll
-                for (int i = 0; i < N; ++i) Y[k][i] -= Y[j][i] * c;
-                r -= c * q[j];
-            }
-            double hph = 0.0;
-#pragma unroll
-            for (int m = 0; m < N; ++m) hph += (double)Hk[m] * Y[k][m];
-            const double s = hph + varv[k], rsq = 1.0 / sqrt(fabs(s));
-            pivots = pivots && s > 0.0;
-            neg[k] = s < 0.0;
-            q[k] = r * rsq;
-            // the row is finished HERE: arithmetic is not tied to its place by order_fence(), and without this the compiler sinks every
-            // row's sums behind the requests of all the rows of H and of the nominal state (seen in the ISA: 15 global loads and the
-            // nominal chunks in front of the first row, 54 + 28 registers carried through all of it)
-            asm volatile("" : "+v"(q[k]));
-            // nisv += sgn_k q_k^2, written out in the order the plain sum q_0^2 + q_1^2 + q_2^2 contracts to (ll keeps its last bit):
-            // q_0^2 is fused into the rounded q_1^2, every later term is fused into the sum
-            auto sq = [&](int j) __attribute__((always_inline)) { return neg[j] ? -q[j] : q[j]; };
-            if constexpr (k == 0 && M == 1) nisv = sq(0) * q[0];
-            if constexpr (k == 1) nisv = fma(sq(0), q[0], sq(1) * q[1]);
-            if constexpr (k >= 2) nisv = fma(sq(k), q[k], nisv);
-            detS *= s;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                Y[k][i] *= rsq;
-                dx[i] = k > 0 ? dx[i] + (T)(Y[k][i] * q[k]) : (T)(Y[k][i] * q[k]);
-            }
-        });
-        if (!hfin) {
-            untouched();
-            return;
-        }
-        if (nis) nis[b] = (T)nisv;
-        if (dof) dof[b] = M;
-        if (!(pivots && nisv <= gate)) {                // (both comparisons are false for a NaN)
-            applied[b] = 0;
-            if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, detS, M);
-            return;
-        }
-        inject<T, N>(nom, dx);
-        // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
-        store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
-        store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, my_lane(), nom + L::NPQR);
-        __builtin_amdgcn_sched_barrier(0);
-        fresh();
-        // chunk c: its elements' M terms, one rounding, its store (prev_id and the padding behind it go back as they came)
-        static_for<CN, RC::NCH>([&](auto cc) {
-            constexpr int c = decltype(cc)::value;
-#pragma unroll
-            for (int k = 0; k < EPC; ++k) {
-                constexpr int e0 = (c - CN) * EPC;
-                const int e = e0 + k;
-                if (e < L::NP) {
-                    double a = (double)P[e];
-#pragma unroll
-                    for (int m = 0; m < M; ++m) a -= Y[m][pk_row<N>(e)] * Y[m][pk_col<N>(e)];
-                    P[e] = (T)a;
-                }
-            }
-            store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
-            __builtin_amdgcn_sched_barrier(0);
-        });
-    } else {
-        // fp64 records: the sequential rows, in the record type
-        T u[N], dx[N], dk = T(0);
-        // chunk c of the covariance takes the rank-1 term of the row at hand; the last row's pass stores each chunk behind its arithmetic
-        // (prev_id and the padding behind it go back as they came).  The scheduling barriers keep one row's work, and one chunk's, together
-        auto pass = [&](auto store) __attribute__((always_inline)) {
-            static_for<CN, RC::NCH>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-#pragma unroll
-                for (int k = 0; k < EPC; ++k) {
-                    constexpr int e0 = (c - CN) * EPC;
-                    const int e = e0 + k;
-                    if (e < L::NP) P[e] -= (u[pk_row<N>(e)] * dk) * u[pk_col<N>(e)];
-                }
-                if constexpr (decltype(store)::value) store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
-                else pin_chunk(P + (c - CN) * EPC);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        };
-        static_for<0, M>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            __builtin_amdgcn_sched_barrier(0);
-            const T* Hk = Hr[k];
-#pragma unroll
-            for (int j = 0; j < N; ++j) hfin = hfin && isfinite(Hk[j]);
+            // finished behind q[k]: without it the compiler sinks every row's sums behind the requests of all the rows of H and of the
+            // nominal state (seen in the ISA: 15 global loads and the nominal chunks in front of the first row, 54 + 28 registers carried
+            // through all of it)
+            joint_row<k, DenseCols<N>, true>(Y, q, neg, dx, g, Hk, (double)rv[k], varv[k]);
+        } else {
             static_for<0, N>([&](auto ic) {
                 constexpr int i = decltype(ic)::value;
-                T acc = PS(i, 0) * Hk[0];
+                T acc = P[pidx<N>(i, 0)] * Hk[0];
 #pragma unroll
-                for (int j = 1; j < N; ++j) acc += PS(i, j) * Hk[j];
+                for (int j = 1; j < N; ++j) acc += P[pidx<N>(i, j)] * Hk[j];
                 u[i] = acc;
             });
-            double hph = 0.0, hdx = 0.0;
-#pragma unroll
-            for (int j = 0; j < N; ++j) {
-                hph += (double)Hk[j] * (double)u[j];
-                if (k > 0) hdx += (double)Hk[j] * (double)dx[j];
-            }
-            const double s = hph + varv[k], r = (double)rv[k] - hdx;
-            double is = 1.0 / s;
-            // The row of H is done with, and the next request takes its registers: row k + 1 (it travels behind this row's rank-1 pass),
-            // or the nominal state.  One row, N values, is alive at a time beside a covariance of 342 registers.  The row's sums are
-            // finished here, in front of the request (see the fp32 rows)
-            asm volatile("" : "+v"(is));
-            if constexpr (k + 1 < M) {
-                request(std::integral_constant<int, k + 1>{});
-                order_fence();
-            } else {
-                request_nom();
-            }
-            pivots = pivots && s > 0.0;
-            nisv += r * r * is;
-            detS *= s;
-            const T g = (T)(r * is);
-            dk = (T)is;
-#pragma unroll
-            for (int i = 0; i < N; ++i) dx[i] = k > 0 ? dx[i] + u[i] * g : u[i] * g;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (k + 1 < M) pass(std::false_type{});
-        });
-        if (!hfin) {
-            untouched();
-            return;
+            seq_row<k, DenseCols<N>>(u, dx, dk, g, Hk, (double)rv[k], varv[k], [&](double& is) __attribute__((always_inline)) {
+                // The row of H is done with, and the next request takes its registers: row k + 1 (it travels behind this row's rank-1
+                // pass), or the nominal state.  One row, N values, is alive at a time beside a covariance of 342 registers.  The row's
+                // sums are finished here, in front of the request (see the fp32 rows)
+                asm volatile("" : "+v"(is));
+                if constexpr (k + 1 < M) {
+                    request(std::integral_constant<int, k + 1>{});
+                    order_fence();
+                } else {
+                    request_nom();
+                }
+            });
+            if constexpr (k + 1 < M) rank1_pass<T, N, false>(rs, P, u, dk);
         }
-        if (nis) nis[b] = (T)nisv;
-        if (dof) dof[b] = M;
-        if (!(pivots && nisv <= gate)) {                    // (both comparisons are false for a NaN)
-            applied[b] = 0;
-            if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, detS, M);
-            return;
-        }
-        inject<T, N>(nom, dx);
-        // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
-        store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
-        store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, my_lane(), nom + L::NPQR);
-        __builtin_amdgcn_sched_barrier(0);
-        pass(std::true_type{});
+    });
+    // a lane with a non-finite entry of H is untouched too; it is known once the last row is in
+    if (!hfin) return leave_untouched(o);
+    report(o, g, M);
+    if (gate_shut(g, gate)) return leave_rejected(o, g, M);
+    inject<T, N>(nom, dx);
+    store_nominal<T, N>(rs, nom);
+    if constexpr (joint) {
+        fresh<T, N>(P);
+        joint_pass<T, N, M>(rs, P, Y);
+    } else {
+        rank1_pass<T, N, true>(rs, P, u, dk);
     }
-#undef PS
-    applied[b] = 1;
-    if (lik) lik_add(LikOut{ lik, B }, b, true, nisv, 0.0, detS, M);
-}
-
-// grid: one wave per tile
-template <typename T, int N, int M>
-void launch_rows_k(hipStream_t st, T* recs, int B, const T* res, const T* H, const double* var, int var_stride, const unsigned char* skip,
-                   unsigned char* applied, const double* thr, T* nis, int* dof, double* lik)
-{
-    hipLaunchKernelGGL((correct_rows_kernel<T, N, M>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, recs, B, res, H, var, var_stride,
-                       skip, applied, thr, nis, dof, lik);
+    leave_applied(o, g, M);
 }
 
 }  // namespace

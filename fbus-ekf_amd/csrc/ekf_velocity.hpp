@@ -26,9 +26,7 @@
 // order.  A lane that is skipped, has a non-finite z or gyro or a var that is not a finite number > 0, or is not applied, stores nothing
 // to its record.  No early exit in front of the loads (correct_depth_kernel's reason).
 #pragma once
-#include "ekf_depth.hpp"        // pin_chunk
-#include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
-#include "ekf_kernels.hpp"
+#include "ekf_sensor.hpp"       // the exits and the gate rule, store_nominal, the two row steps and covariance passes, launch_tile_k
 
 namespace {
 
@@ -37,9 +35,11 @@ namespace {
 struct VelocitySensor { double C[9], lever[3]; };
 
 __host__ __device__ constexpr int vcol(int k) { return k < 6 ? k + 3 : k + 6; }          // V-position -> state column
-
-// pin_chunk (ekf_depth.hpp) here: a pass whose result only the applied branch uses is sunk behind the gate by the compiler, and its u
-// vector with it; the chunk is made opaque where the pass leaves it, so every row is finished where it stands.
+// the column set of a row of H (ekf_sensor.hpp): its 9 entries on V
+struct VCols {
+    static constexpr int n = 9;
+    static constexpr int col(int k) { return vcol(k); }
+};
 
 template <typename T, int N>
 struct VelocityCut {
@@ -69,7 +69,7 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
-    constexpr int EPC = RC::EPC, CN = RC::CH_NOM;
+    constexpr int CN = RC::CH_NOM;
     // The waits are the compiler's counted vmcnt.  The largest count of the fp32 forms is the wait for the ten input loads behind the NCH
     // record loads (60 for N = 18); the fp64 records have 100 / 77 chunks, there a larger count is clamped to 63: early, never late.
     static_assert(sizeof(T) == 8 || RC::NCH + 10 <= 63, "fp32: every counted wait of the stream must fit the 6-bit vmcnt field");
@@ -104,21 +104,15 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
     unsigned skv = skip ? (unsigned)skin : 0u;
     asm volatile("" : "+v"(zv[0]), "+v"(zv[1]), "+v"(zv[2]), "+v"(gv[0]), "+v"(gv[1]), "+v"(gv[2]));
     asm volatile("" : "+v"(varv[0]), "+v"(varv[1]), "+v"(varv[2]), "+v"(skv));
-    // untouched lanes: no store to the record, no likelihood term.  (x > 0 is false for a NaN)
+    const SensorOut<T> o{ applied, nis, dof, lik, B, b };
+    // untouched lanes  (x > 0 is false for a NaN)
     bool usable = in && skv == 0u;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
         usable = usable && isfinite((double)zv[i]) && isfinite(varv[i]) && varv[i] > 0.0;
         if (gyro) usable = usable && isfinite((double)gv[i]);
     }
-    if (!usable) {
-        if (in) {
-            applied[b] = 0;
-            if (nis) nis[b] = T(0);
-            if (dof) dof[b] = 0;
-        }
-        return;
-    }
+    if (!usable) return leave_untouched(o, in);
 
     // h and the innovation in double; without gyro the lever does not enter (H_bg = C [0]x = 0)
     const T* R = nom + L::OFF_R;
@@ -147,177 +141,49 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
         Hk[7] = (T)(c2 * lv[0] - c0 * lv[2]);
         Hk[8] = (T)(c0 * lv[1] - c1 * lv[0]);
     };
-#define PS(i, j) P[pidx<N>((i), (j))]
-    double nisv = 0.0, detS = 1.0;
-    bool pivots = true;
-    if constexpr (sizeof(T) == 4) {
-        // fp32 records: THE JOINT FORM, its arithmetic in double, every covariance element rounded once.  An update that takes the velocity
-        // block from a prior of 0.1 (m/s)^2 to the sensor's 1e-4 subtracts numbers that agree in their first three digits: P - u u' / s in
-        // fp32 keeps eps32 x prior / posterior of the result (4e-4 block-wise on the suite's states, sequential and joint alike), and
-        // fp32 roundings of P between the rows still leave 3e-5.  So P stays as loaded until its one pass and the rows
-        // are orthogonalised instead: w_k = P h_k - sum_{j<k} w_j (w_j . h_k) / s_j is the sequential form's u_k, from the ORIGINAL P.
-        // Kept as y_k = w_k / sqrt(s_k):  P+ = P - sum y_k y_k',  dx = sum y_k r_k / sqrt(s_k),  r_k = res_k - sum_{j<k} (h_k . y_j) r_j / sqrt(s_j).
-        // 3 N doubles beside the fp32 covariance: 256 + 186 registers for N = 18, no scratch.
-        // A pivot that is not > 0 (a record whose covariance is not positive definite) ends in "not applied", and its lane still reports
-        // nis = sum r_k^2 / s_k as the fp64 form and the header have it: the roots are taken of |s_k| and the sign of s_k goes with the
-        // products -- w_j (w_j . h_k) / s_j = sgn_j y_j (y_j . h_k), r_k^2 / s_k = sgn_k q_k^2.  With every pivot > 0 each sign is a
-        // select that keeps its operand: the same bits as without them.
-        double Y[3][N], q[3];                            // q[k] = r_k / sqrt(|s_k|)
-        bool neg[3];
-        T dx[N];
-        // P is made opaque in front of the pass: the compiler otherwise keeps the elements it widened for the rows alive for it, two
-        // registers each beside the covariance they were converted from (188 B of scratch; 0 B with it)
-        auto fresh = [&]() __attribute__((always_inline)) {
-            static_for<0, (L::NP + 3) / 4>([&](auto cc) { pin_chunk(P + 4 * decltype(cc)::value); });
-        };
-        static_for<0, 3>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            __builtin_amdgcn_sched_barrier(0);
-            T Hk[9];
-            row(k, Hk);
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                double acc = (double)PS(i, vcol(0)) * (double)Hk[0];
-#pragma unroll
-                for (int j = 1; j < 9; ++j) acc += (double)PS(i, vcol(j)) * (double)Hk[j];
-                Y[k][i] = acc;
-            }
-            double r = res[k];
-#pragma unroll
-            for (int j = 0; j < k; ++j) {
-                double c = 0.0;
-#pragma unroll
-                for (int m = 0; m < 9; ++m) c += (double)Hk[m] * Y[j][vcol(m)];
-                c = neg[j] ? -c : c;
-#pragma unroll
-                for (int i = 0; i < N; ++i) Y[k][i] -= Y[j][i] * c;
-                r -= c * q[j];
-            }
-            double hph = 0.0;
-#pragma unroll
-            for (int m = 0; m < 9; ++m) hph += (double)Hk[m] * Y[k][vcol(m)];
-            const double s = hph + varv[k], rs = 1.0 / sqrt(fabs(s));
-            pivots = pivots && s > 0.0;
-            neg[k] = s < 0.0;
-            q[k] = r * rs;
-            // nisv += sgn_k q_k^2, written out in the order the plain sum q_0^2 + q_1^2 + q_2^2 contracts to (ll keeps its last bit):
-            // q_0^2 is fused into the rounded q_1^2, every later term is fused into the sum
-            auto sq = [&](int j) __attribute__((always_inline)) { return neg[j] ? -q[j] : q[j]; };
-            if constexpr (k == 1) nisv = fma(sq(0), q[0], sq(1) * q[1]);
-            if constexpr (k >= 2) nisv = fma(sq(k), q[k], nisv);
-            detS *= s;
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                Y[k][i] *= rs;
-                dx[i] = k > 0 ? dx[i] + (T)(Y[k][i] * q[k]) : (T)(Y[k][i] * q[k]);
-            }
-        });
-        if (nis) nis[b] = (T)nisv;
-        if (dof) dof[b] = 3;
-        if (!(pivots && nisv <= gate)) {                // (both comparisons are false for a NaN)
-            applied[b] = 0;
-            if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, detS, 3);
-            return;
-        }
-        inject<T, N>(nom, dx);
-        // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
-        store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
-        store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, my_lane(), nom + L::NPQR);
+    // The two forms of the rows (the head of the file; the steps and their reasons: ekf_sensor.hpp).  fp32: P stays as loaded until its
+    // one pass, 3 N doubles y_k beside it; fp64: rows one and two update P in registers, the third row's pass stores
+    constexpr bool joint = sizeof(T) == 4;
+    using A = SensorArith<T>;
+    double Y[3][N], q[3];                                // fp32: y_k, q_k and the signs of s_k
+    bool neg[3];
+    T u[N], dk = T(0), dx[N];                            // fp64: the u and 1 / s of the row at hand; both: dx
+    RowSums g;
+    static_for<0, 3>([&](auto kc) {
+        constexpr int k = decltype(kc)::value;
         __builtin_amdgcn_sched_barrier(0);
-        fresh();
-        // chunk c: its elements' three terms, one rounding, its store (prev_id and the padding behind it go back as they came)
-        static_for<CN, RC::NCH>([&](auto cc) {
-            constexpr int c = decltype(cc)::value;
+        T Hk[9];
+        row(k, Hk);
+        // P h_k by output row over the 9 V columns: P(:, V) is all a row reads
+        A* w;
+        if constexpr (joint) w = Y[k];
+        else w = u;
 #pragma unroll
-            for (int k = 0; k < EPC; ++k) {
-                constexpr int e0 = (c - CN) * EPC;
-                const int e = e0 + k;
-                if (e < L::NP) {
-                    double a = (double)P[e];
+        for (int i = 0; i < N; ++i) {
+            A acc = (A)P[pidx<N>(i, vcol(0))] * (A)Hk[0];
 #pragma unroll
-                    for (int m = 0; m < 3; ++m) a -= Y[m][pk_row<N>(e)] * Y[m][pk_col<N>(e)];
-                    P[e] = (T)a;
-                }
-            }
-            store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
-            __builtin_amdgcn_sched_barrier(0);
-        });
+            for (int j = 1; j < 9; ++j) acc += (A)P[pidx<N>(i, vcol(j))] * (A)Hk[j];
+            w[i] = acc;
+        }
+        if constexpr (joint) {
+            joint_row<k, VCols, false>(Y, q, neg, dx, g, Hk, res[k], varv[k]);
+        } else {
+            seq_row<k, VCols>(u, dx, dk, g, Hk, res[k], varv[k], [](double&) {});
+            if constexpr (k < 2) rank1_pass<T, N, false>(rs, P, u, dk);
+        }
+    });
+    // the gate is decided behind the third row's s and r, before the first store
+    report(o, g, 3);
+    if (gate_shut(g, gate)) return leave_rejected(o, g, 3);
+    inject<T, N>(nom, dx);
+    store_nominal<T, N>(rs, nom);
+    if constexpr (joint) {
+        fresh<T, N>(P);
+        joint_pass<T, N, 3>(rs, P, Y);
     } else {
-        // fp64 records: the sequential rows, in the record type
-        T u[N], dx[N], dk = T(0);
-        // chunk c of the covariance takes the rank-1 term of the row at hand; the last row's pass stores each chunk behind its arithmetic
-        // (prev_id and the padding behind it go back as they came).  The scheduling barriers keep one row's work, and one chunk's, together:
-        // without them the scheduler forms all three rows of H and the scaled u of every chunk ahead of their use, and the fp32 N = 18
-        // kernel spilled 704 B
-        auto pass = [&](auto store) __attribute__((always_inline)) {
-            static_for<CN, RC::NCH>([&](auto cc) {
-                constexpr int c = decltype(cc)::value;
-#pragma unroll
-                for (int k = 0; k < EPC; ++k) {
-                    constexpr int e0 = (c - CN) * EPC;
-                    const int e = e0 + k;
-                    if (e < L::NP) P[e] -= (u[pk_row<N>(e)] * dk) * u[pk_col<N>(e)];
-                }
-                if constexpr (decltype(store)::value) store_chunks<T, N, c, c + 1, FBUS_X_CORRECT_ST>(rs, my_lane(), P + (c - CN) * EPC);
-                else pin_chunk(P + (c - CN) * EPC);
-                __builtin_amdgcn_sched_barrier(0);
-            });
-        };
-        static_for<0, 3>([&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            __builtin_amdgcn_sched_barrier(0);
-            T Hk[9];
-            row(k, Hk);
-#pragma unroll
-            for (int i = 0; i < N; ++i) {
-                T acc = PS(i, vcol(0)) * Hk[0];
-#pragma unroll
-                for (int j = 1; j < 9; ++j) acc += PS(i, vcol(j)) * Hk[j];
-                u[i] = acc;
-            }
-            double hph = 0.0, hdx = 0.0;
-#pragma unroll
-            for (int j = 0; j < 9; ++j) {
-                hph += (double)Hk[j] * (double)u[vcol(j)];
-                if (k > 0) hdx += (double)Hk[j] * (double)dx[vcol(j)];
-            }
-            const double s = hph + varv[k], r = res[k] - hdx, is = 1.0 / s;
-            pivots = pivots && s > 0.0;
-            nisv += r * r * is;
-            detS *= s;
-            const T g = (T)(r * is);
-            dk = (T)is;
-#pragma unroll
-            for (int i = 0; i < N; ++i) dx[i] = k > 0 ? dx[i] + u[i] * g : u[i] * g;
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (k < 2) pass(std::false_type{});
-        });
-        if (nis) nis[b] = (T)nisv;
-        if (dof) dof[b] = 3;
-        if (!(pivots && nisv <= gate)) {                    // (both comparisons are false for a NaN)
-            applied[b] = 0;
-            if (lik) lik_add(LikOut{ lik, B }, b, false, nisv, 0.0, detS, 3);
-            return;
-        }
-        inject<T, N>(nom, dx);
-        // the carried rotation is NOT refreshed by a measurement update: chunks holding only R are left alone
-        store_chunks<T, N, 0, RC::CH_PQ, FBUS_X_CORRECT_ST>(rs, my_lane(), nom);
-        store_chunks<T, N, RC::CH_PQR, CN, FBUS_X_CORRECT_ST>(rs, my_lane(), nom + L::NPQR);
-        __builtin_amdgcn_sched_barrier(0);
-        pass(std::true_type{});
+        rank1_pass<T, N, true>(rs, P, u, dk);
     }
-#undef PS
-    applied[b] = 1;
-    if (lik) lik_add(LikOut{ lik, B }, b, true, nisv, 0.0, detS, 3);
-}
-
-// grid: one wave per tile
-template <typename T, int N>
-void launch_velocity_k(hipStream_t st, T* recs, int B, const T* z, const T* gyro, const double* var, int var_stride, const unsigned char* skip,
-                       unsigned char* applied, const VelocitySensor& vs, const double* thr, T* nis, int* dof, double* lik)
-{
-    hipLaunchKernelGGL((correct_velocity_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, st, recs, B, z, gyro, var, var_stride,
-                       skip, applied, vs, thr, nis, dof, lik);
+    leave_applied(o, g, 3);
 }
 
 }  // namespace

@@ -613,59 +613,47 @@ int group_mix_t(fbus_ekf_t h, int G, const double* logw, const double* trans, do
     return FBUS_OK;
 }
 int do_group_mix(fbus_ekf_t h, int G, const double* lw, const double* tr, double* w, double* lc) { DISPATCH2(h, group_mix_t, h, G, lw, tr, w, lc); }
-// ---- the depth update (ekf_depth.hpp): one launcher for every form; one wave per tile whatever the batch, the team setting, the noise
-// table or the likelihood switch.  The gate table is the handle's (+inf without one), the likelihood accumulator null while the sums are off
-template <typename T, int N>
-int launch_depth_t(fbus_ekf_t h, const void* z, const double* var, int var_per_filter, const uint8_t* skip, void* nis, int32_t* dof)
+// ---- the streamed sensor updates (ekf_depth.hpp, ekf_velocity.hpp, ekf_rows.hpp): one launcher for every form of each, one route: one wave
+// per tile whatever the batch, the team setting, the noise table or the likelihood switch.  The gate table is the handle's (+inf without
+// one), the likelihood accumulator null while the sums are off.  SensorDev: the arrays every one of them takes behind its own inputs
+struct SensorDev { const double* var; int var_stride; const unsigned char* skip; void* nis; int* dof; };
+template <typename... KP, typename... A>
+int launch_sensor(fbus_ekf_t h, void (*kernel)(KP...), A... args)
 {
     h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
-    launch_depth_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, var, var_per_filter ? 1 : 0, (const unsigned char*)skip, h->d_applied,
-                         h->depth, h->d_gate, (T*)nis, (int*)dof, h->lik_on ? h->d_lik : nullptr);
+    launch_tile_k(kernel, h->stream, h->B, args...);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
-int launch_depth(fbus_ekf_t h, const void* z, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
-{
-    DISPATCH2(h, launch_depth_t, h, z, var, per, skip, nis, dof);
-}
-// ---- the velocity update (ekf_velocity.hpp): one launcher for every form, one route, as the depth update's
 template <typename T, int N>
-int launch_velocity_t(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
-                      int32_t* dof)
+int launch_depth_t(fbus_ekf_t h, const void* z, const SensorDev& d)
 {
-    h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
-    launch_velocity_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, (const T*)gyro, var, var_per_filter ? 1 : 0, (const unsigned char*)skip,
-                            h->d_applied, h->velocity, h->d_gate, (T*)nis, (int*)dof, h->lik_on ? h->d_lik : nullptr);
-    HIP_TRY(h, hipGetLastError());
-    return FBUS_OK;
+    return launch_sensor(h, correct_depth_kernel<T, N>, (T*)h->recs, h->B, (const T*)z, d.var, d.var_stride, d.skip, h->d_applied, h->depth,
+                         h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
 }
-int launch_velocity(fbus_ekf_t h, const void* z, const void* gyro, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
-{
-    DISPATCH2(h, launch_velocity_t, h, z, gyro, var, per, skip, nis, dof);
-}
-// ---- the general row update (ekf_rows.hpp): one launcher for every form, one route, as the velocity update's; m picks the instantiation
+int launch_depth(fbus_ekf_t h, const void* z, const SensorDev& d) { DISPATCH2(h, launch_depth_t, h, z, d); }
 template <typename T, int N>
-int launch_rows_t(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int var_per_filter, const uint8_t* skip, void* nis,
-                  int32_t* dof)
+int launch_velocity_t(fbus_ekf_t h, const void* z, const void* gyro, const SensorDev& d)
 {
-    h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
+    return launch_sensor(h, correct_velocity_kernel<T, N>, (T*)h->recs, h->B, (const T*)z, (const T*)gyro, d.var, d.var_stride, d.skip,
+                         h->d_applied, h->velocity, h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
+}
+int launch_velocity(fbus_ekf_t h, const void* z, const void* gyro, const SensorDev& d) { DISPATCH2(h, launch_velocity_t, h, z, gyro, d); }
+// m picks the instantiation
+template <typename T, int N>
+int launch_rows_t(fbus_ekf_t h, int m, const void* res, const void* H, const SensorDev& d)
+{
     const auto go = [&](auto mc) {
-        launch_rows_k<T, N, decltype(mc)::value>(h->stream, (T*)h->recs, h->B, (const T*)res, (const T*)H, var, var_per_filter ? 1 : 0,
-                                                 (const unsigned char*)skip, h->d_applied, h->d_gate, (T*)nis, (int*)dof,
-                                                 h->lik_on ? h->d_lik : nullptr);
+        return launch_sensor(h, correct_rows_kernel<T, N, decltype(mc)::value>, (T*)h->recs, h->B, (const T*)res, (const T*)H, d.var,
+                             d.var_stride, d.skip, h->d_applied, h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
     };
     switch (m) {
-    case 1: go(std::integral_constant<int, 1>{}); break;
-    case 2: go(std::integral_constant<int, 2>{}); break;
-    default: go(std::integral_constant<int, 3>{}); break;
+    case 1: return go(std::integral_constant<int, 1>{});
+    case 2: return go(std::integral_constant<int, 2>{});
+    default: return go(std::integral_constant<int, 3>{});
     }
-    HIP_TRY(h, hipGetLastError());
-    return FBUS_OK;
 }
-int launch_rows(fbus_ekf_t h, int m, const void* res, const void* H, const double* var, int per, const uint8_t* skip, void* nis, int32_t* dof)
-{
-    DISPATCH2(h, launch_rows_t, h, m, res, H, var, per, skip, nis, dof);
-}
+int launch_rows(fbus_ekf_t h, int m, const void* res, const void* H, const SensorDev& d) { DISPATCH2(h, launch_rows_t, h, m, res, H, d); }
 
 // the snapshot into row block f of a trajectory window's outputs (the frame-by-frame routes)
 int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
@@ -1560,102 +1548,83 @@ int group_mix_any(fbus_ekf_t h, Transport t, int G, const double* logw, const do
     });
 }
 
-// ---- the depth update: fbus_ekf_correct_depth / _dev / _async / _nis / _nis_dev ----------------------------------------------------------------
-// (the order of the tests is part of the interface: include/fbus_ekf.h)
-int check_depth(fbus_ekf_t h, const char* where, const void* z, const double* var, int var_per_filter)
+// ---- the streamed sensor updates: fbus_ekf_correct_depth / _velocity / _rows, each also _dev, _nis and _nis_dev; depth and velocity _async --
+// One argument check and one transport for the three.  (the order of the tests is part of the interface: include/fbus_ekf.h)
+struct SensorCall {
+    const char* stem;                   // the entry point the messages name: fbus_ekf_correct_<stem> + _async, or [_nis][_dev]
+    bool ready;                         // the update's own precondition, tested first, and what is said when it fails
+    const char* not_ready;
+    bool have;                          // the arrays that must not be NULL are there, and what is said when one is not
+    const char* missing;
+    int rows;                           // variances per filter
+    bool gated;                         // every form is gated: the table must reach dof `rows`
+};
+// nis: an _nis form (its outputs may still be null); in: the update's own input pieces, in front of var, skip, nis and dof;
+// go(SensorDev): the launch
+template <typename GO>
+int sensor_any(fbus_ekf_t h, Transport t, bool nis, const SensorCall& c, const Piece* in, int n_in, const double* var, int var_per_filter,
+               const uint8_t* skip, void* out_nis, int32_t* out_dof, GO go)
 {
-    if (!h) return FBUS_ERR_INVALID;
-    if (!h->depth_set) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": fbus_ekf_set_depth_sensor has not been called");
-    if (!z || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": z and var must not be NULL");
-    if (var_per_filter != 0 && var_per_filter != 1)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
-    return FBUS_OK;
+    DeviceGuard guard_(h);
+    const auto where = [&] {            // (put together only where it is said)
+        return std::string("fbus_ekf_correct_") + c.stem +
+               (t == ASYNC ? "_async" : nis ? (t == DEV ? "_nis_dev" : "_nis") : (t == DEV ? "_dev" : ""));
+    };
+    if (!c.ready) return fail(h, FBUS_ERR_INVALID, where() + ": " + c.not_ready);
+    if (!c.have) return fail(h, FBUS_ERR_INVALID, where() + ": " + c.missing);
+    if (var_per_filter != 0 && var_per_filter != 1) return fail(h, FBUS_ERR_INVALID, where() + ": var_per_filter must be 0 or 1");
+    if (c.gated) {
+        const int rc = check_gate_dof(h, c.rows, where().c_str());
+        if (rc != FBUS_OK) return rc;
+    }
+    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, where() + ": not between graph_begin and graph_end");
+    const size_t B = (size_t)h->B;
+    const void *dv, *ds;
+    void *dn, *dd;
+    Piece pc[6];
+    std::copy(in, in + n_in, pc);
+    pc[n_in] = in_piece(var, (var_per_filter ? B : 1) * c.rows * sizeof(double), &dv);
+    pc[n_in + 1] = in_piece(skip, B, &ds);
+    pc[n_in + 2] = out_piece(out_nis, B * esize(h), &dn);
+    pc[n_in + 3] = out_piece(out_dof, B * sizeof(int32_t), &dd);
+    return run_pieces(h, t, pc, n_in + 4, [&] {
+        return go(SensorDev{ (const double*)dv, var_per_filter ? 1 : 0, (const unsigned char*)ds, dn, (int*)dd });
+    });
 }
-// nis: an _nis form (its outputs may still be null)
 int depth_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const double* var, int var_per_filter, const uint8_t* skip,
               void* out_nis, int32_t* out_dof)
 {
-    DeviceGuard guard_(h);
-    const char* where = t == ASYNC ? "fbus_ekf_correct_depth_async"
-                                   : nis ? (t == DEV ? "fbus_ekf_correct_depth_nis_dev" : "fbus_ekf_correct_depth_nis")
-                                         : (t == DEV ? "fbus_ekf_correct_depth_dev" : "fbus_ekf_correct_depth");
-    const int rc = check_depth(h, where, z, var, var_per_filter);
-    if (rc != FBUS_OK) return rc;
-    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
-    const size_t B = (size_t)h->B;
-    const void *dz, *dv, *ds;
-    void *dn, *dd;
-    Piece pc[5] = { in_piece(z, B * esize(h), &dz), in_piece(var, (var_per_filter ? B : 1) * sizeof(double), &dv), in_piece(skip, B, &ds),
-                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
-    return run_pieces(h, t, pc, 5, [&] {
-        return launch_depth(h, dz, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
-    });
-}
-
-// ---- the velocity update: fbus_ekf_correct_velocity / _dev / _async / _nis / _nis_dev ----------------------------------------------------------
-// (the order of the tests is part of the interface: include/fbus_ekf.h)
-int check_velocity(fbus_ekf_t h, const char* where, const void* z, const double* var, int var_per_filter)
-{
     if (!h) return FBUS_ERR_INVALID;
-    if (!h->velocity_set) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": fbus_ekf_set_velocity_sensor has not been called");
-    if (!z || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": z and var must not be NULL");
-    if (var_per_filter != 0 && var_per_filter != 1)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
-    return FBUS_OK;
+    const void* dz;
+    const Piece in[1] = { in_piece(z, (size_t)h->B * esize(h), &dz) };
+    const SensorCall c{ "depth", h->depth_set, "fbus_ekf_set_depth_sensor has not been called", z && var, "z and var must not be NULL", 1, false };
+    return sensor_any(h, t, nis, c, in, 1, var, var_per_filter, skip, out_nis, out_dof,
+                      [&](const SensorDev& d) { return launch_depth(h, dz, d); });
 }
-// nis: an _nis form (its outputs may still be null)
 int velocity_any(fbus_ekf_t h, Transport t, bool nis, const void* z, const void* gyro, const double* var, int var_per_filter,
                  const uint8_t* skip, void* out_nis, int32_t* out_dof)
 {
-    DeviceGuard guard_(h);
-    const char* where = t == ASYNC ? "fbus_ekf_correct_velocity_async"
-                                   : nis ? (t == DEV ? "fbus_ekf_correct_velocity_nis_dev" : "fbus_ekf_correct_velocity_nis")
-                                         : (t == DEV ? "fbus_ekf_correct_velocity_dev" : "fbus_ekf_correct_velocity");
-    const int rc = check_velocity(h, where, z, var, var_per_filter);
-    if (rc != FBUS_OK) return rc;
-    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
-    const size_t B = (size_t)h->B;
-    const void *dz, *dg, *dv, *ds;
-    void *dn, *dd;
-    Piece pc[6] = { in_piece(z, B * 3 * esize(h), &dz), in_piece(gyro, B * 3 * esize(h), &dg),
-                    in_piece(var, (var_per_filter ? B : 1) * 3 * sizeof(double), &dv), in_piece(skip, B, &ds),
-                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
-    return run_pieces(h, t, pc, 6, [&] {
-        return launch_velocity(h, dz, dg, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
-    });
-}
-
-// ---- the general row update: fbus_ekf_correct_rows / _dev / _nis / _nis_dev -------------------------------------------------------------------
-// (the order of the tests is part of the interface: include/fbus_ekf.h)
-int check_rows(fbus_ekf_t h, const char* where, int m, const void* res, const void* H, const double* var, int var_per_filter)
-{
     if (!h) return FBUS_ERR_INVALID;
-    if (m < 1 || m > FBUS_ROWS_MAX)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": m = " + std::to_string(m) + " outside 1.." + std::to_string(FBUS_ROWS_MAX));
-    if (!res || !H || !var) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": res, H and var must not be NULL");
-    if (var_per_filter != 0 && var_per_filter != 1)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": var_per_filter must be 0 or 1");
-    return check_gate_dof(h, m, where);           // every form is gated: the table must reach dof m
+    const void *dz, *dg;
+    const size_t bytes = (size_t)h->B * 3 * esize(h);
+    const Piece in[2] = { in_piece(z, bytes, &dz), in_piece(gyro, bytes, &dg) };
+    const SensorCall c{ "velocity", h->velocity_set, "fbus_ekf_set_velocity_sensor has not been called", z && var, "z and var must not be NULL", 3, false };
+    return sensor_any(h, t, nis, c, in, 2, var, var_per_filter, skip, out_nis, out_dof,
+                      [&](const SensorDev& d) { return launch_velocity(h, dz, dg, d); });
 }
-// nis: an _nis form (its outputs may still be null)
+// (no _async form)
 int rows_any(fbus_ekf_t h, Transport t, bool nis, int m, const void* res, const void* H, const double* var, int var_per_filter,
              const uint8_t* skip, void* out_nis, int32_t* out_dof)
 {
-    DeviceGuard guard_(h);
-    const char* where = nis ? (t == DEV ? "fbus_ekf_correct_rows_nis_dev" : "fbus_ekf_correct_rows_nis")
-                            : (t == DEV ? "fbus_ekf_correct_rows_dev" : "fbus_ekf_correct_rows");
-    const int rc = check_rows(h, where, m, res, H, var, var_per_filter);
-    if (rc != FBUS_OK) return rc;
-    if (t == STAGED && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
-    const size_t B = (size_t)h->B, M = (size_t)m;
-    const void *dr, *dH, *dv, *ds;
-    void *dn, *dd;
-    Piece pc[6] = { in_piece(res, B * M * esize(h), &dr), in_piece(H, B * M * (size_t)h->N * esize(h), &dH),
-                    in_piece(var, (var_per_filter ? B : 1) * M * sizeof(double), &dv), in_piece(skip, B, &ds),
-                    out_piece(out_nis, B * esize(h), &dn), out_piece(out_dof, B * sizeof(int32_t), &dd) };
-    return run_pieces(h, t, pc, 6, [&] {
-        return launch_rows(h, m, dr, dH, (const double*)dv, var_per_filter, (const uint8_t*)ds, dn, (int32_t*)dd);
-    });
+    if (!h) return FBUS_ERR_INVALID;
+    const bool m_ok = m >= 1 && m <= FBUS_ROWS_MAX;
+    const void *dr, *dH;
+    const size_t bytes = (size_t)h->B * (size_t)m * esize(h);
+    const Piece in[2] = { in_piece(res, bytes, &dr), in_piece(H, bytes * (size_t)h->N, &dH) };
+    const std::string bad_m = m_ok ? std::string() : "m = " + std::to_string(m) + " outside 1.." + std::to_string(FBUS_ROWS_MAX);
+    const SensorCall c{ "rows", m_ok, bad_m.c_str(), res && H && var, "res, H and var must not be NULL", m, true };
+    return sensor_any(h, t, nis, c, in, 2, var, var_per_filter, skip, out_nis, out_dof,
+                      [&](const SensorDev& d) { return launch_rows(h, m, dr, dH, d); });
 }
 
 // ---- per-marker screening (ekf_screen.hpp): fbus_ekf_screen_markers / _dev ----------------------------------------------------------------------

@@ -578,45 +578,56 @@ class BatchedFilter:
         lv = None if lever is None else (C.c_double * 3)(*np.asarray(lever, np.float64).reshape(3))
         self._check(self._lib.fbus_ekf_set_depth_sensor(self._h, ax, float(offset), lv), "fbus_ekf_set_depth_sensor")
 
-    def _depth(self, z, var, skip, nis=False, transport=None):
-        """One depth update through fbus_ekf_correct_depth[_nis]<transport>, on _update's device / host / async branch.  var: one
-        variance or B of them, always float64."""
+    def _sensor_update(self, stem, arrays, var, m, skip, nis, transport, head=()):
+        """One streamed sensor update through fbus_ekf_correct_<stem>[_nis]<transport>, on _update's device / host / async branch.
+        arrays: the update's own inputs in call order, each (name, value, per-filter shape, may be None); the first one decides the
+        branch.  var: m variances or B x m of them, always float64.  head: the integer arguments in front of the arrays."""
         B = self.B
+        lead = arrays[0][1]
+        counts = f"{m} or {B}" + ("" if arrays[0][2] == () else f" x {m}")
         cur, out = None, ()
-        if transport is None and _is_dev(z):
+        if transport is None and _is_dev(lead):
             import torch
             transport = "_dev"
-            self._dev_checked(z, B, "z")
+            for name, a, shape, optional in arrays:
+                if not (optional and a is None):
+                    self._dev_checked(a, B * int(np.prod(shape, dtype=np.int64)), name)
+            vals = [a for _, a, _, _ in arrays]
             if not _is_dev(var):
-                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(z.device)
-            if var.dtype != torch.float64 or var.numel() not in (1, B):
-                raise ValueError(f"correct_depth: var must be float64 with 1 or {B} elements, got {var.dtype} x {var.numel()}")
+                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(lead.device)
+            if var.dtype != torch.float64 or var.numel() not in (m, m * B):
+                raise ValueError(f"correct_{stem}: var must be float64 with {counts} elements, got {var.dtype} x {var.numel()}")
             self._dev_checked(var, var.numel(), "var")
             if skip is not None:
                 self._dev_checked(skip, B, "skip")
             if nis:
-                out = self._nis_outputs(z)
+                out = self._nis_outputs(lead)
                 self._keep += list(out)
-            cur = self._order_in(z, var, skip)
-            per = 1 if (var.numel() == B and B > 1) else 0
+            cur = self._order_in(*vals, var, skip)
+            per = 1 if (var.numel() == m * B and B > 1) else 0
         else:
             conv = self._host_any if transport else self._host
             transport = transport or ""
-            z = conv(z, (B,))
+            vals = [None if (optional and a is None) else conv(a, (B,) + tuple(shape)) for _, a, shape, optional in arrays]
             var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
-            if var.size not in (1, B):
-                raise ValueError(f"correct_depth: var must have 1 or {B} elements, got {var.size}")
-            per = 1 if (var.size == B and B > 1) else 0
+            if var.size not in (m, m * B):
+                raise ValueError(f"correct_{stem}: var must have {counts} elements, got {var.size}")
+            per = 1 if (var.size == m * B and B > 1) else 0
             skip = None if skip is None else self._host(skip, (B,), np.uint8)
             if transport == "_async":       # pinned inputs are transferred in place: they live until async_inputs_consumed() / sync()
-                self._async_inputs += [z, var, skip]
+                self._async_inputs += vals + [var, skip]
             if nis:
                 out = self._nis_outputs(None)
-        name = "correct_depth" + ("_nis" if nis else "") + transport
-        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(z), self._p(var), per, self._p(skip), *[self._p(o) for o in out])
+        name = f"correct_{stem}" + ("_nis" if nis else "") + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, *head, *[self._p(a) for a in vals], self._p(var), per, self._p(skip),
+                                                    *[self._p(o) for o in out])
         self._check(rc, name)
         self._order_out(cur)
         return out if nis else None
+
+    def _depth(self, z, var, skip, nis=False, transport=None):
+        """One depth update: one variance or B of them."""
+        return self._sensor_update("depth", [("z", z, (), False)], var, 1, skip, nis, transport)
 
     def correct_depth(self, z, var, skip=None):
         """The depth (pressure) sensor update, one scalar row per filter: h = axis . (p + R lever) + offset, dx = P H' (z - h) / S,
@@ -646,48 +657,8 @@ class BatchedFilter:
         self._check(self._lib.fbus_ekf_set_velocity_sensor(self._h, mt, lv), "fbus_ekf_set_velocity_sensor")
 
     def _velocity(self, z, gyro, var, skip, nis=False, transport=None):
-        """One velocity update through fbus_ekf_correct_velocity[_nis]<transport>, on _depth's device / host / async branch.  var: three
-        variances or B x 3 of them, always float64."""
-        B = self.B
-        cur, out = None, ()
-        if transport is None and _is_dev(z):
-            import torch
-            transport = "_dev"
-            self._dev_checked(z, 3 * B, "z")
-            if gyro is not None:
-                self._dev_checked(gyro, 3 * B, "gyro")
-            if not _is_dev(var):
-                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(z.device)
-            if var.dtype != torch.float64 or var.numel() not in (3, 3 * B):
-                raise ValueError(f"correct_velocity: var must be float64 with 3 or {B} x 3 elements, got {var.dtype} x {var.numel()}")
-            self._dev_checked(var, var.numel(), "var")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            if nis:
-                out = self._nis_outputs(z)
-                self._keep += list(out)
-            cur = self._order_in(z, gyro, var, skip)
-            per = 1 if (var.numel() == 3 * B and B > 1) else 0
-        else:
-            conv = self._host_any if transport else self._host
-            transport = transport or ""
-            z = conv(z, (B, 3))
-            gyro = None if gyro is None else conv(gyro, (B, 3))
-            var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
-            if var.size not in (3, 3 * B):
-                raise ValueError(f"correct_velocity: var must have 3 or {B} x 3 elements, got {var.size}")
-            per = 1 if (var.size == 3 * B and B > 1) else 0
-            skip = None if skip is None else self._host(skip, (B,), np.uint8)
-            if transport == "_async":       # pinned inputs are transferred in place: they live until async_inputs_consumed() / sync()
-                self._async_inputs += [z, gyro, var, skip]
-            if nis:
-                out = self._nis_outputs(None)
-        name = "correct_velocity" + ("_nis" if nis else "") + transport
-        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(z), self._p(gyro), self._p(var), per, self._p(skip),
-                                                    *[self._p(o) for o in out])
-        self._check(rc, name)
-        self._order_out(cur)
-        return out if nis else None
+        """One velocity update: three variances or B x 3 of them."""
+        return self._sensor_update("velocity", [("z", z, (3,), False), ("gyro", gyro, (3,), True)], var, 3, skip, nis, transport)
 
     def correct_velocity(self, z, var, gyro=None, skip=None):
         """The body-velocity update (a Doppler velocity log; with z = 0 a zero-velocity update), three rows per filter:
@@ -709,50 +680,19 @@ class BatchedFilter:
 
     # ---- the general linearised measurement update (include/fbus_ekf.h; no reference counterpart) ------------------------------------
     def _rows(self, res, H, var, skip, nis=False):
-        """One row update through fbus_ekf_correct_rows[_nis][_dev], on _velocity's device / host branch.  m is read off res.shape[1];
-        var: m variances or B x m of them, always float64."""
+        """One row update, device or host form (there is no async one).  m is read off res.shape[1]; m variances or B x m of them."""
         B, N = self.B, self.N
         if getattr(res, "ndim", 0) != 2 or res.shape[0] != B:
             raise ValueError(f"correct_rows: res must be ({B}, m), got {tuple(getattr(res, 'shape', ()))}")
         m = int(res.shape[1])
-        cur, out = None, ()
         if _is_dev(res):
             import torch
-            transport = "_dev"
             dt = torch.float32 if self.dtype == 32 else torch.float64
             if not _is_dev(H) or res.dtype != dt or H.dtype != dt:
                 raise ValueError(f"correct_rows: res and H must both be {dt} device tensors")
-            self._dev_checked(res, m * B, "res")
-            self._dev_checked(H, m * N * B, "H")
-            if not _is_dev(var):
-                var = torch.as_tensor(np.ascontiguousarray(var, np.float64).ravel()).to(res.device)
-            if var.dtype != torch.float64 or var.numel() not in (m, m * B):
-                raise ValueError(f"correct_rows: var must be float64 with {m} or {B} x {m} elements, got {var.dtype} x {var.numel()}")
-            self._dev_checked(var, var.numel(), "var")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            if nis:
-                out = self._nis_outputs(res)
-                self._keep += list(out)
-            cur = self._order_in(res, H, var, skip)
-            per = 1 if (var.numel() == m * B and B > 1) else 0
-        else:
-            transport = ""
-            res = self._host(res, (B, m))
-            H = self._host(H.numpy() if _is_dev(H) else H, (B, m, N))
-            var = np.ascontiguousarray(var.numpy() if _is_dev(var) else var, np.float64).ravel()
-            if var.size not in (m, m * B):
-                raise ValueError(f"correct_rows: var must have {m} or {B} x {m} elements, got {var.size}")
-            per = 1 if (var.size == m * B and B > 1) else 0
-            skip = None if skip is None else self._host(skip, (B,), np.uint8)
-            if nis:
-                out = self._nis_outputs(None)
-        name = "correct_rows" + ("_nis" if nis else "") + transport
-        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, m, self._p(res), self._p(H), self._p(var), per, self._p(skip),
-                                                    *[self._p(o) for o in out])
-        self._check(rc, name)
-        self._order_out(cur)
-        return out if nis else None
+        elif _is_dev(H):
+            H = H.numpy()
+        return self._sensor_update("rows", [("res", res, (m,), False), ("H", H, (m, N), False)], var, m, skip, nis, None, head=(m,))
 
     def correct_rows(self, res, H, var, skip=None):
         """The general linearised measurement update, m = res.shape[1] rows per filter (1..capi.ROWS_MAX): the caller hands over the

@@ -45,6 +45,7 @@ def test_the_build_still_has_61_units(repo_root):
     spec.loader.exec_module(b)
     assert len(b.units()) == 61
     assert any(h.endswith("ekf_depth.hpp") for h in b.HEADERS)             # a change of the kernel rebuilds the library
+    assert any(h.endswith("ekf_sensor.hpp") for h in b.HEADERS)            # ... and so does one of the steps it shares
     main = open(os.path.join(repo_root, "fbus-ekf_amd", "csrc", "fbus_ekf.hip")).read()
     assert '#include "ekf_depth.hpp"' in main                               # instantiated from the main unit: no new family
 
