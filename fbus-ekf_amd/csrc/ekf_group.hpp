@@ -146,22 +146,25 @@ __device__ __forceinline__ double group_weight(const GM& gm, const double* __res
     return (usable && bi >= 0) ? ew / s : 0.0;
 }
 
-// step 3: this member's error state dl (order p v theta ba bg [g]) against the chart xs, in double for both record types
-template <typename T, int N>
-__device__ __forceinline__ void group_delta(const T* nom, const T* xs, double* dl)
+// where a member's components sit: in a record (Lay<N>), or in an array in the order of fbus_ekf_get_state (p3 v3 q4 ba3 bg3 g3)
+struct ApiOrder { static constexpr int OFF_P3 = 0, OFF_V = 3, OFF_Q = 6, OFF_BA = 10, OFF_BG = 13, OFF_G = 16; };
+// step 3: this member's error state dl (order p v theta ba bg [g]) against the chart xs, in double for both record types.
+// The member is nom, of type TM and laid out as ML says: a record's nominal part, or (ekf_nees.hpp) a truth row in double
+template <typename T, int N, typename ML = Lay<N>, typename TM = T>
+__device__ __forceinline__ void group_delta(const TM* nom, const T* xs, double* dl)
 {
     using L = Lay<N>;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        dl[i] = (double)nom[L::OFF_P3 + i] - (double)xs[L::OFF_P3 + i];
-        dl[3 + i] = (double)nom[L::OFF_V + i] - (double)xs[L::OFF_V + i];
-        dl[9 + i] = (double)nom[L::OFF_BA + i] - (double)xs[L::OFF_BA + i];
-        dl[12 + i] = (double)nom[L::OFF_BG + i] - (double)xs[L::OFF_BG + i];
-        if constexpr (N == 18) dl[15 + i] = (double)nom[L::OFF_G + i] - (double)xs[L::OFF_G + i];
+        dl[i] = (double)nom[ML::OFF_P3 + i] - (double)xs[L::OFF_P3 + i];
+        dl[3 + i] = (double)nom[ML::OFF_V + i] - (double)xs[L::OFF_V + i];
+        dl[9 + i] = (double)nom[ML::OFF_BA + i] - (double)xs[L::OFF_BA + i];
+        dl[12 + i] = (double)nom[ML::OFF_BG + i] - (double)xs[L::OFF_BG + i];
+        if constexpr (N == 18) dl[15 + i] = (double)nom[ML::OFF_G + i] - (double)xs[L::OFF_G + i];
     }
     {   // dtheta = Log(conj(q*) (x) q), in double for both record types: the inverse of inject()'s q <- normalize(q (x) dq(dtheta))
         const double qc[4] = { (double)xs[L::OFF_Q], -(double)xs[L::OFF_Q + 1], -(double)xs[L::OFF_Q + 2], -(double)xs[L::OFF_Q + 3] };
-        const double qi[4] = { (double)nom[L::OFF_Q], (double)nom[L::OFF_Q + 1], (double)nom[L::OFF_Q + 2], (double)nom[L::OFF_Q + 3] };
+        const double qi[4] = { (double)nom[ML::OFF_Q], (double)nom[ML::OFF_Q + 1], (double)nom[ML::OFF_Q + 2], (double)nom[ML::OFF_Q + 3] };
         double d[4];
         quat_mul(qc, qi, d);
         if (d[0] < 0.0) { d[0] = -d[0]; d[1] = -d[1]; d[2] = -d[2]; d[3] = -d[3]; }

@@ -17,6 +17,7 @@
 #include "ekf_velocity.hpp"
 #include "ekf_rows.hpp"
 #include "ekf_screen.hpp"
+#include "ekf_nees.hpp"
 #include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1697,6 +1698,38 @@ int screen_any(fbus_ekf_t h, Transport t, int kind, int M, const int32_t* ids, c
     });
 }
 
+// ---- consistency against a truth state (ekf_nees.hpp): fbus_ekf_nees / _dev ---------------------------------------------------------------------
+// One launcher for both forms and one route, as the screening has.  Read-only.
+template <typename T, int N, int D>
+int launch_nees_t(fbus_ekf_t h, const double* truth, const uint8_t* skip, const NeesOut& o)
+{
+    launch_nees_k<T, N>(h->stream, (const T*)h->recs, h->B, truth, (const unsigned char*)skip, o);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_nees(fbus_ekf_t h, const double* truth, const uint8_t* skip, const NeesOut& o) { DISPATCH(h, launch_nees_t, h, truth, skip, o); }
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int nees_any(fbus_ekf_t h, Transport t, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    const std::string where = t == DEV ? "fbus_ekf_nees_dev" : "fbus_ekf_nees";
+    if (!truth) return fail(h, FBUS_ERR_INVALID, where + ": truth is NULL");
+    const size_t B = (size_t)h->B, N = (size_t)h->N;
+    const size_t nb = B * FBUS_NEES_COLS * sizeof(double), eb = B * N * sizeof(double), lb = B * sizeof(double);
+    if (t == DEV && (in_records(h, nees, nb) || in_records(h, err, eb) || in_records(h, lnp, lb)))
+        return fail(h, FBUS_ERR_INVALID, where + ": an output overlaps the records");
+    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
+    if (!nees && !err && !lnp) return FBUS_OK;
+    const void *dt, *ds;
+    void *dn, *de, *dl;
+    Piece pc[5] = { in_piece(truth, B * 19 * sizeof(double), &dt), in_piece(skip, B, &ds), out_piece(nees, nb, &dn), out_piece(err, eb, &de),
+                    out_piece(lnp, lb, &dl) };
+    return run_pieces(h, t, pc, 5, [&] {
+        return launch_nees(h, (const double*)dt, (const uint8_t*)ds, NeesOut{ (double*)dn, (double*)de, (double*)dl });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -2650,6 +2683,14 @@ int fbus_ekf_screen_markers_dev(fbus_ekf_t h, int kind, int M, const int32_t* id
                                 int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept)
 {
     return screen_any(h, DEV, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept);
+}
+int fbus_ekf_nees(fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp)
+{
+    return nees_any(h, STAGED, truth, skip, nees, err, lnp);
+}
+int fbus_ekf_nees_dev(fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp)
+{
+    return nees_any(h, DEV, truth, skip, nees, err, lnp);
 }
 
 int fbus_ekf_set_velocity_sensor(fbus_ekf_t h, const double mount[9], const double lever[3])

@@ -14,12 +14,12 @@ from .capi import (DIALECT_CPP, DIALECT_MATLAB, MODE_NEAREST, MODE_STACKED, COV_
                    FbusError, FbusParams, default_params, declared_symbols, load_library, library_path)
 from .filter import BatchedFilter
 from .frame_batcher import FrameBatcher
-from . import synth, shard
+from . import synth, shard, consistency
 
 __all__ = [
     "DIALECT_CPP", "DIALECT_MATLAB", "MODE_NEAREST", "MODE_STACKED", "COV_SIMPLE", "COV_JOSEPH",
     "KERNEL_PREDICT", "KERNEL_CORRECT", "KERNEL_PREDICT_N", "KERNEL_MARKER_POSE", "KERNEL_FRAME",
     "VIS_REFRACTIVE", "VIS_PINHOLE", "VIS_CORNERS3D", "POSE_INIT", "POSE_RESET",
     "FbusError", "FbusParams", "default_params", "declared_symbols", "load_library", "library_path",
-    "BatchedFilter", "FrameBatcher", "synth", "shard",
+    "BatchedFilter", "FrameBatcher", "synth", "shard", "consistency",
 ]

@@ -29,6 +29,8 @@ NOISE_COLS = 7                     # FBUS_NOISE_COLS: q_v q_theta q_ba q_bg r_po
 SCREEN_POSE, SCREEN_PIXELS, SCREEN_CORNERS = 0, 1, 2   # fbus_ekf_screen_markers: the update whose rows are judged per marker slot
 GROUP_MAX = 64                     # FBUS_GROUP_MAX: the largest hypothesis group (fbus_ekf_group_fuse / _collapse)
 ROWS_MAX = 3                       # FBUS_ROWS_MAX: the most rows of one fbus_ekf_correct_rows call
+NEES_COLS = 8                      # FBUS_NEES_COLS: the columns of fbus_ekf_nees's `nees`, in this order
+NEES_FULL, NEES_POSE, NEES_P, NEES_V, NEES_THETA, NEES_BA, NEES_BG, NEES_G = range(8)
 
 
 class FbusError(RuntimeError):
@@ -175,6 +177,8 @@ def load_library():
         "fbus_ekf_correct_depth_nis_dev": ([H, vp, vp, C.c_int, u8p, vp, ip], C.c_int),
         "fbus_ekf_screen_markers": ([H, C.c_int, C.c_int, ip, vp, vp, C.c_int, u8p, ip, vp, ip, ip], C.c_int),
         "fbus_ekf_screen_markers_dev": ([H, C.c_int, C.c_int, ip, vp, vp, C.c_int, u8p, ip, vp, ip, ip], C.c_int),
+        "fbus_ekf_nees": ([H, vp, u8p, vp, vp, vp], C.c_int),
+        "fbus_ekf_nees_dev": ([H, vp, u8p, vp, vp, vp], C.c_int),
         "fbus_ekf_set_velocity_sensor": ([H, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         "fbus_ekf_correct_velocity": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
         "fbus_ekf_correct_velocity_dev": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),

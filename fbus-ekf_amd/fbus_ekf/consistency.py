@@ -1,0 +1,66 @@
+"""Consistency of a bank of filters against a known state: what to hold BatchedFilter.nees() against (pure numpy / math).
+
+Under a consistent filter -- truth ~ N(estimate, P) -- a column of nees is chi-square with the block's degrees of freedom, and the
+average over n independent filters times n is chi-square with n dof: the ANEES test of Bar-Shalom, Li and Kirubarajan, Estimation
+with Applications to Tracking and Navigation, section 5.4.  A mean above the interval says P is too small (over-confident), one
+below it that P is too large.
+"""
+import numpy as np
+
+from .capi import NEES_COLS
+from .gating import chi2_ppf
+
+NEES_NAMES = ("full", "pose", "p", "v", "theta", "ba", "bg", "g")      # the columns of fbus_ekf_nees, in order
+assert len(NEES_NAMES) == NEES_COLS
+
+
+def nees_dof(nstate):
+    """the degrees of freedom of the 8 columns (g: 0 for nstate 15, where the column is written as 0)"""
+    if nstate not in (15, 18):
+        raise ValueError("nstate must be 15 or 18")
+    return (nstate, 6, 3, 3, 3, 3, 3, 3 if nstate == 18 else 0)
+
+
+def anees_interval(dof, n, prob=0.95):
+    """the two-sided chi-square interval (lo, hi) that holds the average of n independent NEES values of `dof` degrees of freedom
+    with probability prob: chi2_ppf((1 -+ prob) / 2, n dof) / n"""
+    if dof <= 0 or n <= 0:
+        raise ValueError("dof and n must be positive")
+    if not 0.0 < prob < 1.0:
+        raise ValueError("prob must be in (0, 1)")
+    d = float(n) * float(dof)
+    return chi2_ppf(0.5 * (1.0 - prob), d) / n, chi2_ppf(0.5 * (1.0 + prob), d) / n
+
+
+def anees(nees, skip=None):
+    """(mean[8], left_out[8]): the column means of nees (B, 8) over the filters that are finite in that column and not skipped, and
+    how many filters each column left out.  A column without a filter left has mean NaN."""
+    a = np.asarray(nees, np.float64)
+    if a.ndim != 2 or a.shape[1] != NEES_COLS:
+        raise ValueError(f"nees must be (B, {NEES_COLS}), got {a.shape}")
+    use = np.isfinite(a)
+    if skip is not None:
+        use &= (np.asarray(skip).reshape(-1, 1) == 0)
+    cnt = use.sum(axis=0)
+    tot = np.where(use, a, 0.0).sum(axis=0)
+    mean = np.where(cnt > 0, tot / np.maximum(cnt, 1), np.nan)
+    return mean, a.shape[0] - cnt
+
+
+def summary(nees, nstate, prob=0.95, skip=None):
+    """per column name: {"mean", "dof", "n", "lo", "hi", "inside"} -- the ANEES of the filters that count (anees) against
+    anees_interval for that many.  A column without degrees of freedom (g for nstate 15) or without a filter left has
+    lo = hi = NaN and inside = None."""
+    mean, out = anees(nees, skip)
+    B = np.asarray(nees).shape[0]
+    res = {}
+    for c, (name, dof) in enumerate(zip(NEES_NAMES, nees_dof(nstate))):
+        n = int(B - out[c])
+        if dof > 0 and n > 0:
+            lo, hi = anees_interval(dof, n, prob)
+            inside = bool(lo <= mean[c] <= hi)
+        else:
+            lo = hi = float("nan")
+            inside = None
+        res[name] = {"mean": float(mean[c]), "dof": dof, "n": n, "lo": lo, "hi": hi, "inside": inside}
+    return res

@@ -778,6 +778,48 @@ class BatchedFilter:
         self._order_out(cur)
         return out
 
+    # ---- consistency against a truth state (include/fbus_ekf.h: fbus_ekf_nees) ----------------------------------------------
+    def nees(self, truth, skip=None, err=False, lnp=False):
+        """The normalised estimation error squared of every filter against `truth`, (B, 19) float64 in get_state()'s order
+        (p v q ba bg g; g ignored for nstate 15): with delta = truth (-) estimate, nees[:, c] = delta_J' P_JJ^-1 delta_J for the
+        capi.NEES_COLS blocks NEES_FULL (all N states), NEES_POSE (p and theta) and the 3 x 3 marginals NEES_P .. NEES_G, in double
+        for both record types.  err=True also returns delta, (B, N) in the order p v theta ba bg [g]; lnp=True the log-density of
+        the truth under N(estimate, P), -1/2 (nees_FULL + ln det P + N ln 2 pi).  A torch device tensor takes the stream-ordered,
+        capturable device form and returns device tensors; a numpy array is staged.  skip: (B,) uint8, nonzero = zeros in every
+        output.  A column is NaN when one of its delta components is not finite or its block is not positive definite; no other
+        column and no other filter is touched.  Read-only: no record, flag or likelihood sum changes.  fbus_ekf.consistency
+        has the chi-square bounds for the column means.  Returns nees, or (nees[, err][, lnp])."""
+        B, N = self.B, self.N
+        if tuple(getattr(truth, "shape", ())) != (B, 19):
+            raise ValueError(f"nees: truth must be ({B}, 19), got {tuple(getattr(truth, 'shape', ()))}")
+        cur = None
+        if _is_dev(truth):
+            import torch
+            if truth.dtype != torch.float64:
+                raise ValueError(f"nees: truth must be float64, got {truth.dtype}")
+            self._dev_checked(truth, B * 19, "truth")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=truth.device)
+            transport = "_dev"
+        else:
+            if np.asarray(truth).dtype != np.float64:
+                raise ValueError(f"nees: truth must be float64, got {np.asarray(truth).dtype}")
+            truth = self._host(truth, (B, 19), np.float64)
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            mk = lambda *shape: np.empty(shape, np.float64)
+            transport = ""
+        out = (mk(B, capi.NEES_COLS), mk(B, N) if err else None, mk(B) if lnp else None)
+        if transport:
+            self._keep += [o for o in out if o is not None]
+            cur = self._order_in(truth, skip, *out)
+        name = "nees" + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(truth), self._p(skip), *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        res = tuple(o for o in out if o is not None)
+        return res[0] if len(res) == 1 else res
+
     def applied(self):
         out = np.empty(self.B, np.uint8)
         self._check(self._lib.fbus_ekf_get_applied(self._h, self._p(out)), "get_applied")

@@ -229,6 +229,15 @@ public:
                             int32_t* dof = nullptr, int32_t* kept = nullptr, int geometry = FBUS_VIS_REFRACTIVE, const uint8_t* skip = nullptr)
     { check(fbus_ekf_screen_markers_dev(h_, kind, M, ids, a, b, geometry, skip, ids_out, nis, dof, kept), "screen_markers_dev"); }
 
+    // ---- consistency against a truth state (fbus_ekf.h; no reference counterpart): with delta = truth (-) estimate, nees =
+    // delta_J' P_JJ^-1 delta_J for the FBUS_NEES_COLS blocks (FBUS_NEES_FULL, _POSE, _P .. _G), err = delta (order p v theta ba bg [g]),
+    // lnp = the log-density of the truth under N(estimate, P).  truth: batch() x 19, ALWAYS double, in get_state's order; nees:
+    // batch() x FBUS_NEES_COLS, err: batch() x nstate(), lnp: batch(), all double; each output may be null.  Read-only.
+    void nees(const double* truth, double* nees, double* err = nullptr, double* lnp = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_nees(h_, truth, skip, nees, err, lnp), "nees"); }
+    void nees_dev(const double* truth, double* nees, double* err = nullptr, double* lnp = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_nees_dev(h_, truth, skip, nees, err, lnp), "nees_dev"); }
+
     // ---- the body-velocity (DVL) update (fbus_ekf.h; no reference counterpart).  Three rows per filter,
     // h = C (R' v + (gyro - bg) x lever); at the instrument's own rate, between camera frames:
     //   loop { predict_n(imu since the last reading); correct_velocity(z, gyro, var); }

@@ -114,7 +114,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      fbus_ekf_set_velocity_sensor, fbus_ekf_correct_velocity[_dev|_async|_nis|_nis_dev] (body-velocity update): added under 8
  *      without a bump;
  *      fbus_ekf_correct_rows[_dev|_nis|_nis_dev] (the general linearised measurement update: residual and Jacobian rows from the
- *      caller): added under 8 without a bump
+ *      caller): added under 8 without a bump;
+ *      fbus_ekf_nees[_dev] (NEES, error and log-density against a truth state; a read-only kernel): added under 8 without a bump
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -930,6 +931,57 @@ int fbus_ekf_screen_markers_dev(fbus_ekf_t h, int kind, int M, const int32_t* id
                                 const uint8_t* skip, int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept);
 int fbus_ekf_screen_markers(fbus_ekf_t h, int kind, int M, const int32_t* ids, const void* a, const void* b, int geometry,
                             const uint8_t* skip, int32_t* ids_out, void* nis, int32_t* dof, int32_t* kept);
+
+/* ---- consistency against a truth state: NEES, error and log-density ---------------------------------------------------------------
+ * NIS, the gate, the screen and the likelihood sums judge a filter from its innovations.  This call judges it against a KNOWN state --
+ * a simulator's or a motion-capture truth, or any reference state (a consensus of a bank, another build's result): with
+ * delta = truth (-) estimate, the normalised estimation error squared delta' P^-1 delta of the whole state and of each block, the
+ * error itself, and the log-density of the truth under N(estimate, P).  The reference has no counterpart (it runs one filter and is
+ * judged off line), so the model is stated here.  Nothing but the three outputs is written.
+ *
+ *   truth   [B][19] double for both record types (as var and the noise table are), in the order of fbus_ekf_get_state:
+ *           p3 v3 q4(wxyz) ba3 bg3 g3.  For N = 15 the last three are ignored.
+ *   skip    [B] bytes, nonzero = the filter is not judged; may be NULL
+ *   nees    [B][FBUS_NEES_COLS] double
+ *   err     [B][N] double, error-state order p v theta ba bg [g]
+ *   lnp     [B] double
+ *   Every output may be NULL, in which case it is not written.  A call with all three NULL is legal and launches nothing.
+ *
+ * For filter b:
+ * 1. delta is exactly step 3 of fbus_ekf_group_fuse with the estimate as the chart x*: on p, v, ba, bg (and g for N = 18) the plain
+ *    difference (double)truth - (double)record, one exact subtraction; delta_theta = Log(conj(q) (x) q_true) with that step's sign rule
+ *    and atan2 form, in double for both record types.  q_true is first normalised in double (q / sqrt(w^2 + x^2 + y^2 + z^2)); q is the
+ *    record's nominal quaternion, the carried rotation is not read.  err is delta as formed, NaNs included.
+ * 2. Column c of nees belongs to an index set J_c of the error state and is delta_J' (P_JJ)^-1 delta_J = |L^-1 delta_J|^2 with
+ *    L L' = P_JJ the Cholesky factorisation of that marginal, in double:
+ *        FBUS_NEES_FULL   all N states                          dof N
+ *        FBUS_NEES_POSE   {0, 1, 2, 6, 7, 8} (p and theta)      dof 6
+ *        FBUS_NEES_P, _V, _THETA, _BA, _BG, _G   the 3 x 3 marginals {0..2}, {3..5}, {6..8}, {9..11}, {12..14}, {15..17}, dof 3 each
+ *    For N = 15 column FBUS_NEES_G is written as 0.  The dofs are fixed and are not an output.  (The elimination order is free: the
+ *    leading k entries of L^-1 delta depend on the leading k x k block only, so a factorisation in the order p, theta, v, ... yields P
+ *    and POSE as prefix sums.  This definition, not the order, is the contract.)
+ * 3. lnp = -1/2 (nees_FULL + ln det P + N ln 2 pi), ln det P = the sum of the logs of the squared pivots L_ii^2 of the full
+ *    factorisation: the log-density of the truth under the estimate, a proper score for comparing tunings when truth is known.
+ * 4. A skipped filter gets 0 in every output.  Otherwise a column is NaN iff one of its delta components is not finite or one of its
+ *    block's pivots is not > 0 (the comparison is false for NaN); lnp is NaN iff FULL is.  Columns are independent of each other: a NaN
+ *    in the record's bg makes BG and FULL (and lnp) NaN and leaves P, V, THETA, BA, G and POSE as they are; a zero or non-finite
+ *    q_true makes every column that contains theta (THETA, POSE, FULL) and err's theta entries NaN.  A bad filter never reaches another.
+ * 5. Nothing else is written: the records stay byte-identical, and so do the applied flags, the likelihood sums, the noise table,
+ *    prev_id and the carried EMA sample.  An output that overlaps the records is refused with FBUS_ERR_INVALID (the rule of
+ *    fbus_ekf_snapshot_dev).
+ * 6. The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text); NULL truth; an
+ *    output that overlaps the records -- the last two with the entry point's name in fbus_ekf_last_error.
+ * 7. _dev: device pointers, stream-ordered, capturable; a captured call reads the truth array current at its replay.  nees should be
+ *    16-byte aligned (any allocation is).  The host form stages, launches, waits and copies back; it is refused between graph_begin
+ *    and graph_end.
+ * One kernel family, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, the noise table and the
+ * likelihood switch do not change the route, and two calls on the same inputs are bit-identical whatever the batch size or the
+ * filter's position in it.  Without an _async form.  Added under ABI 8 without a bump: detect the feature by symbol. */
+#define FBUS_NEES_COLS 8
+enum { FBUS_NEES_FULL = 0, FBUS_NEES_POSE = 1, FBUS_NEES_P = 2, FBUS_NEES_V = 3, FBUS_NEES_THETA = 4,
+       FBUS_NEES_BA = 5, FBUS_NEES_BG = 6, FBUS_NEES_G = 7 };
+int fbus_ekf_nees_dev(fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp);
+int fbus_ekf_nees    (fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
