@@ -23,6 +23,7 @@ import ekf_oracle_np as E
 import oracle_capi as oc
 import velocity_ref as V
 from fbus_ekf import capi, synth
+from sensor_families import Depth, Velocity
 from support import B_IND, J, SIZE, aa2q, imu_of, perturbed_setup, pose_setup, predicted_rows, r32, state_batch
 from util import cov_rel_err, cov_rel_err_blockwise
 
@@ -232,8 +233,8 @@ def ref_image(state, n, dialect, kind, ids, left, right, r_pix, joseph=False):
 
 
 # ---- the cells: inputs, readings, reference and rows of each kind ------------------------------------------------------------------------------
-DEPTH = dict(axis=np.array([0.12, -0.2, 1.0]), offset=0.4, lever=np.array([0.11, -0.07, 0.05]), var=1e-4)       # tests/test_depth_gpu.py's
-VELOCITY = dict(mount=V.tilted_mount(), lever=np.array([0.21, -0.08, 0.12]), var=np.array([1e-4, 4e-4, 2.5e-5]))   # tests/test_velocity_gpu.py's
+DEPTH = dict(axis=Depth.AXIS, offset=Depth.OFFSET, lever=Depth.LEVER, var=Depth.SENSOR_VAR)          # the sensors of tests/sensor_families.py
+VELOCITY = dict(mount=Velocity.MOUNT, lever=Velocity.LEVER, var=Velocity.VAR)
 KINDS = ("depth", "velocity", "pose_nearest", "pose_stacked", "left", "stereo", "corners")
 
 

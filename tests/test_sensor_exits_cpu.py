@@ -26,7 +26,7 @@ def test_the_lane_plan_meets_its_own_counts(name, m):
     assert not (planted & (kinds != X.CLEAN)).any()
     if name == "depth":
         assert not (kinds == X.EXTRA).any()
-    # the unusable lanes sit where tests/test_rows_gpu.py's mixed_inputs puts them
+    # the unusable lanes sit where sensor_families.Rows.mixed puts them
     mixed = (b // 64 != 1) & (b // 64 != 3)
     un = ~X.usable_kind(kinds) & mixed
     assert np.array_equal(un, mixed & (np.isin(b % 16, (3, 7, 11, 15)) | np.isin(b % 32, (5, 13, 21, 29))))

@@ -12,12 +12,12 @@ import pytest
 import torch
 
 import exits_plan as X
+from sensor_families import NAMES
 from support import same_rows
 from util import assert_parity
 
 pytestmark = pytest.mark.gpu
 
-NAMES = ("nominal", "rot", "P", "prev")
 LN2PI = float(np.log(2 * np.pi))
 
 
@@ -43,8 +43,8 @@ def lanes_of(raw, bpf):
 
 
 def fresh(fam, dtype, n, state):
-    """a handle of the family's carried() construction holding exactly `state`; -> (handle, the state as it reads back, its raw bytes)"""
-    f, _ = fam.carried(X.B, dtype, n)
+    """a handle of the family's construction holding exactly `state`; -> (handle, the state as it reads back, its raw bytes)"""
+    f = fam.handle(X.B, dtype, n, X.DIALECT[n])[0]
     f.set_state(*state)
     before = f.get_state()
     assert same_rows(named(state), named(before))                    # the restatement runs on what the records hold
@@ -55,9 +55,8 @@ def fresh(fam, dtype, n, state):
 def run_case(name, dtype, n, m):
     fam = X.family(name, m)
     rows, what = fam.rows, f"{X.family(name, m)} f{dtype} N={n}"
-    f, aux = fam.carried(X.B, dtype, n)
-    with f:
-        st0 = f.get_state()
+    f, st0, aux = fam.handle(X.B, dtype, n, X.DIALECT[n])
+    f.close()
     case = X.prepare(fam, st0, dtype, n, aux)
     X.reference_conditions(fam, case)                                # 1. the plan, the threshold's gap, the reference's own partition
     kinds, inp, thr = case.kinds, case.inp, case.thr
@@ -73,7 +72,7 @@ def run_case(name, dtype, n, m):
         f.set_gate(X.gate_only(rows, thr))
         f.loglik_enable()
         assert all((x == 0).all() for x in f.loglik())
-        nis, dof = fam.call(f, inp)
+        nis, dof = fam.call(f, inp, "nis")
         got, app = f.get_state(), f.applied().astype(bool)
         raw1, _ = raw_records(f)
         ll, lrows, lapp, lrej = f.loglik()
@@ -123,7 +122,7 @@ def run_case(name, dtype, n, m):
             assert np.array_equal(raw, raw0)                          # a fresh, identical handle
             if table == "wrong entries":
                 f.set_gate(X.gate_wrong_entries(rows))
-            nis_w, dof_w = fam.call(f, inp)
+            nis_w, dof_w = fam.call(f, inp, "nis")
             outs[table] = dict(raw=raw_records(f)[0], applied=f.applied(), nis=nis_w, dof=dof_w)
     healthy = kinds == X.CLEAN
     assert np.array_equal(outs["wrong entries"]["applied"].astype(bool), healthy), what          # nothing is rejected by the gate
