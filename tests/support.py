@@ -52,6 +52,21 @@ def frozen(x):
     return x
 
 
+# ---- the fp32-record floor of a free-running window (util.assert_window_parity) ------------------------------------------------------
+def round_records(nominal, rot, P):
+    """the record arrays rounded to fp32 IN PLACE: what an exact-arithmetic filter with fp32 records keeps of a step's result"""
+    nominal[...] = r32(nominal); rot[...] = r32(rot); P[...] = r32(P)
+
+
+def fp32_record_floor(run):
+    """run(fp32_records) -> (nominal, rot, P, ...): the fp64 reference of a window, with fp32_records=True the same arithmetic with the
+    record rounded to fp32 after every step (round_records).  -> (the fp64 run, util.parity_errors of the rounded run against it): the
+    `floor` of util.assert_window_parity"""
+    from util import parity_errors
+    ref = run(False)
+    return ref, parity_errors(run(True), ref)
+
+
 # ---- bit-equality -------------------------------------------------------------------------------------------------------------------
 def _bits(x):
     x = np.ascontiguousarray(x)

@@ -25,7 +25,7 @@ import pytest
 import oracle_capi as oc
 from fbus_ekf import BatchedFilter, capi, synth
 from replay_ref import OracleEngine
-from support import SIZE, device_caster, r32
+from support import SIZE, device_caster, fp32_record_floor, r32, round_records
 from util import PLAIN_WINDOW_TOL, assert_parity, assert_window_parity, pixel_scene
 
 pytestmark = pytest.mark.gpu
@@ -349,7 +349,7 @@ def test_window_of_frames_with_the_north_star_update(dialect, n, what, stereo, m
 
         def q():
             if fp32_records:
-                eng.nominal[...] = r32(eng.nominal); eng.rot[...] = r32(eng.rot); eng.P[...] = r32(eng.P)
+                round_records(eng.nominal, eng.rot, eng.P)
         k0 = 0
         for f, K in enumerate(kcount):
             for k in range(K):
@@ -367,8 +367,6 @@ def test_window_of_frames_with_the_north_star_update(dialect, n, what, stereo, m
             q()
         return eng.get_state()
 
-    ref = oracle_run(False)
-    from util import parity_errors
-    floor = parity_errors(oracle_run(True), ref)
+    ref, floor = fp32_record_floor(oracle_run)
     assert_window_parity(sa, ref, f"window of {F} frames vs oracle N={n} d{dialect} {what} {'stereo' if stereo else 'left'} mode {mode}",
                          dialect, n, floor=floor)
