@@ -2,7 +2,7 @@
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
 The library is len(units()) translation units compiled in parallel and linked into one shared object:
-  fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose, hypothesis groups: ekf_group.hpp, depth update: ekf_depth.hpp, velocity update: ekf_velocity.hpp, general row update: ekf_rows.hpp, the steps those three share: ekf_sensor.hpp, marker screening: ekf_screen.hpp, NEES against a truth state: ekf_nees.hpp)
+  fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose, hypothesis groups: ekf_group.hpp, depth update: ekf_depth.hpp, velocity update: ekf_velocity.hpp, general row update: ekf_rows.hpp, the steps those three share: ekf_sensor.hpp, marker screening: ekf_screen.hpp, NEES against a truth state: ekf_nees.hpp, draws from every filter's Gaussian: ekf_sample.hpp)
   kernels_tu.hip, once per unit         one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
                                         every row of FAMILIES for float, the rows marked fp64 for double, each for N = 18 and N = 15
 Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.
@@ -16,7 +16,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-HEADERS = [os.path.join(CSRC, h) for h in ("ekf_kernels.hpp", "ekf_device.hpp", "vision_device.hpp", "ekf_launch.hpp", "ekf_team.hpp", "ekf_meas.hpp", "ekf_meas_split.hpp", "ekf_group.hpp", "ekf_sensor.hpp", "ekf_depth.hpp", "ekf_velocity.hpp", "ekf_rows.hpp", "ekf_screen.hpp", "ekf_nees.hpp", "ekf_route.hpp")] + \
+HEADERS = [os.path.join(CSRC, h) for h in ("ekf_kernels.hpp", "ekf_device.hpp", "vision_device.hpp", "ekf_launch.hpp", "ekf_team.hpp", "ekf_meas.hpp", "ekf_meas_split.hpp", "ekf_group.hpp", "ekf_sensor.hpp", "ekf_depth.hpp", "ekf_velocity.hpp", "ekf_rows.hpp", "ekf_screen.hpp", "ekf_nees.hpp", "ekf_sample.hpp", "ekf_route.hpp")] + \
           [os.path.join(HERE, "..", "include", "fbus_ekf.h")]
 OUT = os.environ.get("FBUS_OUT") or os.path.join(HERE, "lib", "libfbus_ekf.so")   # FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds
 OBJDIR = os.environ.get("FBUS_OBJDIR") or os.path.join(os.path.dirname(OUT), "obj" if not os.environ.get("FBUS_OUT") else

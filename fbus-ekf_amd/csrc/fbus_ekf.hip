@@ -18,6 +18,7 @@
 #include "ekf_rows.hpp"
 #include "ekf_screen.hpp"
 #include "ekf_nees.hpp"
+#include "ekf_sample.hpp"
 #include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
@@ -1730,6 +1731,38 @@ int nees_any(fbus_ekf_t h, Transport t, const double* truth, const uint8_t* skip
     });
 }
 
+// ---- draws from every filter's own Gaussian (ekf_sample.hpp): fbus_ekf_sample / _dev ---------------------------------------------------------
+// One launcher for both forms and one route, as NEES has.  Read-only.
+template <typename T, int N, int D>
+int launch_sample_t(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, const SampleOut& o)
+{
+    launch_sample_k<T, N>(h->stream, (const T*)h->recs, h->B, S, xi, (const unsigned char*)skip, o);
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_sample(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, const SampleOut& o) { DISPATCH(h, launch_sample_t, h, S, xi, skip, o); }
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int sample_any(fbus_ekf_t h, Transport t, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn)
+{
+    DeviceGuard guard_(h);
+    if (!h) return FBUS_ERR_INVALID;
+    const std::string where = t == DEV ? "fbus_ekf_sample_dev" : "fbus_ekf_sample";
+    if (S < 1 || S > FBUS_SAMPLE_MAX) return fail(h, FBUS_ERR_INVALID, where + ": S must be 1.." + std::to_string(FBUS_SAMPLE_MAX));
+    if (!xi) return fail(h, FBUS_ERR_INVALID, where + ": xi is NULL");
+    const size_t B = (size_t)h->B, N = (size_t)h->N;
+    const size_t xb = (size_t)S * B * N * sizeof(double), sb = (size_t)S * B * 19 * sizeof(double);
+    if (t == DEV && (in_records(h, state, sb) || in_records(h, drawn, B)))
+        return fail(h, FBUS_ERR_INVALID, where + ": an output overlaps the records");
+    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
+    if (!state && !drawn) return FBUS_OK;
+    const void *dx, *ds;
+    void *dst, *dd;
+    Piece pc[4] = { in_piece(xi, xb, &dx), in_piece(skip, B, &ds), out_piece(state, sb, &dst), out_piece(drawn, B, &dd) };
+    return run_pieces(h, t, pc, 4, [&] {
+        return launch_sample(h, S, (const double*)dx, (const uint8_t*)ds, SampleOut{ (double*)dst, (unsigned char*)dd });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -2691,6 +2724,14 @@ int fbus_ekf_nees(fbus_ekf_t h, const double* truth, const uint8_t* skip, double
 int fbus_ekf_nees_dev(fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp)
 {
     return nees_any(h, DEV, truth, skip, nees, err, lnp);
+}
+int fbus_ekf_sample(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn)
+{
+    return sample_any(h, STAGED, S, xi, skip, state, drawn);
+}
+int fbus_ekf_sample_dev(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn)
+{
+    return sample_any(h, DEV, S, xi, skip, state, drawn);
 }
 
 int fbus_ekf_set_velocity_sensor(fbus_ekf_t h, const double mount[9], const double lever[3])

@@ -31,6 +31,7 @@ GROUP_MAX = 64                     # FBUS_GROUP_MAX: the largest hypothesis grou
 ROWS_MAX = 3                       # FBUS_ROWS_MAX: the most rows of one fbus_ekf_correct_rows call
 NEES_COLS = 8                      # FBUS_NEES_COLS: the columns of fbus_ekf_nees's `nees`, in this order
 NEES_FULL, NEES_POSE, NEES_P, NEES_V, NEES_THETA, NEES_BA, NEES_BG, NEES_G = range(8)
+SAMPLE_MAX = 256                   # FBUS_SAMPLE_MAX: the draws per filter of one fbus_ekf_sample call
 
 
 class FbusError(RuntimeError):
@@ -179,6 +180,8 @@ def load_library():
         "fbus_ekf_screen_markers_dev": ([H, C.c_int, C.c_int, ip, vp, vp, C.c_int, u8p, ip, vp, ip, ip], C.c_int),
         "fbus_ekf_nees": ([H, vp, u8p, vp, vp, vp], C.c_int),
         "fbus_ekf_nees_dev": ([H, vp, u8p, vp, vp, vp], C.c_int),
+        "fbus_ekf_sample": ([H, C.c_int, vp, u8p, vp, vp], C.c_int),
+        "fbus_ekf_sample_dev": ([H, C.c_int, vp, u8p, vp, vp], C.c_int),
         "fbus_ekf_set_velocity_sensor": ([H, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         "fbus_ekf_correct_velocity": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
         "fbus_ekf_correct_velocity_dev": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),

@@ -4,10 +4,13 @@ Under a consistent filter -- truth ~ N(estimate, P) -- a column of nees is chi-s
 average over n independent filters times n is chi-square with n dof: the ANEES test of Bar-Shalom, Li and Kirubarajan, Estimation
 with Applications to Tracking and Navigation, section 5.4.  A mean above the interval says P is too small (over-confident), one
 below it that P is too large.
+
+The way back -- states DRAWN from N(estimate, P) on the device, BatchedFilter.sample() -- takes its coordinates from here: sigma_points()
+and draw().
 """
 import numpy as np
 
-from .capi import NEES_COLS
+from .capi import NEES_COLS, SAMPLE_MAX
 from .gating import chi2_ppf
 
 NEES_NAMES = ("full", "pose", "p", "v", "theta", "ba", "bg", "g")      # the columns of fbus_ekf_nees, in order
@@ -64,3 +67,33 @@ def summary(nees, nstate, prob=0.95, skip=None):
             inside = None
         res[name] = {"mean": float(mean[c]), "dof": dof, "n": n, "lo": lo, "hi": hi, "inside": inside}
     return res
+
+
+def sigma_points(nstate, kappa=0.0):
+    """(xi (2N + 1, N), weights (2N + 1,)): the symmetric sigma-point set in the coordinates BatchedFilter.sample() takes -- the centre,
+    then +sqrt(N + kappa) e_i and -sqrt(N + kappa) e_i for i = 0 .. N - 1 -- with the weights kappa / (N + kappa) and 1 / (2 (N + kappa)):
+    sum w = 1, sum w xi = 0, sum w xi xi' = I, so the drawn states have the filter's own mean and covariance.  Broadcast xi over the
+    batch -- np.broadcast_to(xi[:, None, :], (2N + 1, B, N)) -- for sample()."""
+    if nstate not in (15, 18):
+        raise ValueError("nstate must be 15 or 18")
+    N, c = nstate, float(nstate) + float(kappa)
+    if not c > 0.0:
+        raise ValueError("nstate + kappa must be positive")
+    if 2 * N + 1 > SAMPLE_MAX:
+        raise ValueError("more sigma points than one sample() call takes")
+    r = np.sqrt(c)
+    xi = np.zeros((2 * N + 1, N))
+    xi[1 + np.arange(N), np.arange(N)] = r
+    xi[1 + N + np.arange(N), np.arange(N)] = -r
+    w = np.full(2 * N + 1, 0.5 / c)
+    w[0] = float(kappa) / c
+    return xi, w
+
+
+def draw(flt, S, generator=None):
+    """S states per filter drawn from N(estimate, P): torch.randn on the filter's device (generator: a torch.Generator of that device)
+    through flt.sample().  Returns (state (S, B, 19), xi (S, B, N)), float64 device tensors; nees(state[s]) is chi-square by
+    construction: FULL = |xi[s]|^2."""
+    import torch
+    xi = torch.randn((int(S), flt.B, flt.N), dtype=torch.float64, device=torch.device("cuda", flt.device), generator=generator)
+    return flt.sample(xi), xi

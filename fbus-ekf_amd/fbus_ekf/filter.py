@@ -820,6 +820,76 @@ class BatchedFilter:
         res = tuple(o for o in out if o is not None)
         return res[0] if len(res) == 1 else res
 
+    # ---- draws from every filter's own Gaussian (include/fbus_ekf.h: fbus_ekf_sample) --------------------------------------------
+    def sample(self, xi, skip=None, drawn=False):
+        """S states per filter drawn from N(estimate, P) on the device -- the inverse of nees(): xi, (S, B, N) float64, holds the
+        standard-normal (or sigma-point: consistency.sigma_points) coordinates of the draws in the FACTORISATION order p theta v ba bg
+        [g]; with L L' = the covariance in that order, delta = L xi in error-state order is injected into the nominal state in double
+        (plain sums, q (x) Exp(delta_theta) normalised).  Returns state, (S, B, 19) float64 in get_state()'s order: state[s] is a
+        ready truth for nees() -- which then returns FULL = |xi|^2, POSE = |xi[:6]|^2, P = |xi[:3]|^2 and err = delta -- or, cast, a
+        nominal for set_state().  drawn=True also returns (B,) uint8: 0 for a filter that is skipped (skip: (B,) uint8) or whose
+        covariance is not positive definite; every row of such a filter is its own nominal state.  A torch device tensor takes the
+        stream-ordered, capturable device form and returns device tensors; a numpy array is staged.  S is at most capi.SAMPLE_MAX.
+        Read-only: no record, flag or likelihood sum changes.  Returns state, or (state, drawn)."""
+        B, N = self.B, self.N
+        shape = tuple(getattr(xi, "shape", ()))
+        if len(shape) != 3 or shape[1:] != (B, N) or not 1 <= shape[0] <= capi.SAMPLE_MAX:
+            raise ValueError(f"sample: xi must be (S, {B}, {N}) with S in 1..{capi.SAMPLE_MAX}, got {shape}")
+        S = shape[0]
+        cur = None
+        if _is_dev(xi):
+            import torch
+            if xi.dtype != torch.float64:
+                raise ValueError(f"sample: xi must be float64, got {xi.dtype}")
+            self._dev_checked(xi, S * B * N, "xi")
+            if skip is not None:
+                self._dev_checked(skip, B, "skip")
+            out = (torch.empty((S, B, 19), dtype=torch.float64, device=xi.device),
+                   torch.empty(B, dtype=torch.uint8, device=xi.device) if drawn else None)
+            transport = "_dev"
+            self._keep += [o for o in out if o is not None]
+            cur = self._order_in(xi, skip, *out)
+        else:
+            if np.asarray(xi).dtype != np.float64:
+                raise ValueError(f"sample: xi must be float64, got {np.asarray(xi).dtype}")
+            xi = self._host(xi, (S, B, N), np.float64)
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            out = (np.empty((S, B, 19), np.float64), np.empty(B, np.uint8) if drawn else None)
+            transport = ""
+        name = "sample" + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, S, self._p(xi), self._p(skip), *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out if drawn else out[0]
+
+    def perturb(self, xi, skip=None):
+        """Moves every filter to ONE draw from its own N(estimate, P): xi (B, N) float64 device tensor, as one row of sample().  A
+        composition, not a kernel: sample() with S = 1, the row cast to the record type, the rotation matrix of the new unit quaternion
+        formed in float64 and rounded once, and set_state(nominal, rot) -- on the device -- for the filters that were drawn; the others
+        keep their state, and every covariance, prev_id and flag stays as it is.  The rotation is written on purpose: an in-place
+        perturb that left the CARRIED rotation behind would make the pose and pixel rows linearise at the old attitude until the next
+        predict.  Returns drawn, (B,) uint8 on the device."""
+        import torch
+        if not _is_dev(xi) or tuple(xi.shape) != (self.B, self.N):
+            raise ValueError(f"perturb: xi must be a ({self.B}, {self.N}) device tensor")
+        state, drawn = self.sample(xi.reshape(1, self.B, self.N), skip, drawn=True)
+        with torch.cuda.device(xi.device):
+            old_nom, old_rot = self.get_state_dev()
+            tt = old_nom.dtype
+            nom = state[0].to(tt)
+            w, x, y, z = nom[:, 6:10].to(torch.float64).unbind(1)      # the quaternion the record will hold
+            n2 = w * w + x * x + y * y + z * z
+            w, x, y, z = (c / torch.sqrt(n2) for c in (w, x, y, z))
+            rot = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y),
+                               2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x),
+                               2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], dim=1).to(tt)
+            keep = (drawn == 0)[:, None]
+            nom = torch.where(keep, old_nom, nom).contiguous()
+            rot = torch.where(keep, old_rot, rot).contiguous()
+        self._keep += [nom, rot]
+        self.set_state(nom, rot, None, None)
+        return drawn
+
     def applied(self):
         out = np.empty(self.B, np.uint8)
         self._check(self._lib.fbus_ekf_get_applied(self._h, self._p(out)), "get_applied")

@@ -238,6 +238,15 @@ public:
     void nees_dev(const double* truth, double* nees, double* err = nullptr, double* lnp = nullptr, const uint8_t* skip = nullptr)
     { check(fbus_ekf_nees_dev(h_, truth, skip, nees, err, lnp), "nees_dev"); }
 
+    // ---- draws from every filter's own Gaussian (fbus_ekf.h; no reference counterpart), the inverse of nees(): S states per filter,
+    // estimate (+) Pi' L xi with L L' = Pi P Pi' in the order p theta v ba bg [g].  xi: S x batch() x nstate(), ALWAYS double, in that
+    // order; state: S x batch() x 19 double in get_state's order (a row is a ready truth for nees()); drawn: batch() bytes, 0 = skipped
+    // or not positive definite (every row of that filter is its nominal).  S <= FBUS_SAMPLE_MAX; either output may be null.  Read-only.
+    void sample(int S, const double* xi, double* state, uint8_t* drawn = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_sample(h_, S, xi, skip, state, drawn), "sample"); }
+    void sample_dev(int S, const double* xi, double* state, uint8_t* drawn = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_sample_dev(h_, S, xi, skip, state, drawn), "sample_dev"); }
+
     // ---- the body-velocity (DVL) update (fbus_ekf.h; no reference counterpart).  Three rows per filter,
     // h = C (R' v + (gyro - bg) x lever); at the instrument's own rate, between camera frames:
     //   loop { predict_n(imu since the last reading); correct_velocity(z, gyro, var); }

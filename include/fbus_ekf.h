@@ -115,7 +115,8 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      without a bump;
  *      fbus_ekf_correct_rows[_dev|_nis|_nis_dev] (the general linearised measurement update: residual and Jacobian rows from the
  *      caller): added under 8 without a bump;
- *      fbus_ekf_nees[_dev] (NEES, error and log-density against a truth state; a read-only kernel): added under 8 without a bump
+ *      fbus_ekf_nees[_dev] (NEES, error and log-density against a truth state; a read-only kernel): added under 8 without a bump;
+ *      fbus_ekf_sample[_dev] (draws from every filter's own Gaussian N(estimate, P); a read-only kernel): added under 8 without a bump
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -982,6 +983,51 @@ enum { FBUS_NEES_FULL = 0, FBUS_NEES_POSE = 1, FBUS_NEES_P = 2, FBUS_NEES_V = 3,
        FBUS_NEES_BA = 5, FBUS_NEES_BG = 6, FBUS_NEES_G = 7 };
 int fbus_ekf_nees_dev(fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp);
 int fbus_ekf_nees    (fbus_ekf_t h, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp);
+
+/* ---- draws from every filter's own Gaussian: the inverse of NEES ----------------------------------------------------------------------
+ * fbus_ekf_nees judges a known state against N(estimate, P); this call DRAWS states from it: truth states for a calibration run, start
+ * states for a Monte-Carlo run against one truth, the sigma points of every filter, a particle cloud around each member of a bank --
+ * without moving a covariance to the host.  The reference has no counterpart, so the model is stated here.  Nothing but the two outputs
+ * is written.
+ *
+ *   S       1..FBUS_SAMPLE_MAX draws per filter in one call: one factorisation serves S products
+ *   xi      [S][B][N] double for both record types (as truth and var are): the standard-normal coordinates -- or sigma-point
+ *           coordinates -- of the draws, IN THE FACTORISATION ORDER p, theta, v, ba, bg, [g].  They are not inspected: a non-finite
+ *           entry gives non-finite entries in that row of that filter and nowhere else.
+ *   skip    [B] bytes, nonzero = the filter is not drawn; may be NULL
+ *   state   [S][B][19] double, in the order of fbus_ekf_get_state: p3 v3 q4(wxyz) ba3 bg3 g3.  Row [s] is a ready truth array for
+ *           fbus_ekf_nees, or -- cast to the record type -- a nominal array for fbus_ekf_set_state.
+ *   drawn   [B] bytes
+ *   Either output may be NULL, in which case it is not written.  A call with both NULL is legal and launches nothing.
+ *
+ * For filter b:
+ * 1. L is the lower Cholesky factor of Pi P Pi', formed in double for both record types, Pi the permutation (0,1,2, 6,7,8, 3,4,5,
+ *    9..N-1) that brings the error state p v theta ba bg [g] into the order p theta v ba bg [g].  The draw is delta = Pi' L xi_s, in
+ *    error-state order.  (As in the NEES section the definition is the contract, not the elimination code.  In this order xi's leading
+ *    3 and 6 coordinates alone decide delta_p and delta_(p, theta): fed back to fbus_ekf_nees as truth, a row returns
+ *    FULL = |xi|^2, POSE = |xi(0..5)|^2, P = |xi(0..2)|^2 and err = delta, up to rounding.)
+ * 2. On p, v, ba, bg (and g for N = 18): (double)record + delta, one addition per component.
+ * 3. The quaternion, in double: q_out = normalize(q (x) dq(delta_theta)), dq = (cos(|delta_theta| / 2), sin(|delta_theta| / 2) /
+ *    |delta_theta| delta_theta), and (1, 0, 0, 0) when |delta_theta| = 0 -- the injection of the measurement updates
+ *    (MeasureUpdate.m:92-98) and so the exact inverse of the Log of fbus_ekf_group_fuse's step 3 for |delta_theta| < pi.  q is the
+ *    record's nominal quaternion as stored; the carried rotation is not read.
+ * 4. For N = 15, g is the record's g.
+ * 5. drawn = 1 iff the filter is not skipped and all N pivots L_ii^2 are > 0 (the comparison is false for NaN).  Otherwise drawn = 0
+ *    and EVERY row of that filter is its own nominal state, converted to double and otherwise unchanged (a draw with delta = 0, without
+ *    the renormalisation).  A bad filter never reaches another.
+ * 6. Nothing else is written: the records stay byte-identical, and so do the applied flags, the likelihood sums, the noise table,
+ *    prev_id and the carried EMA sample.
+ * 7. An output that overlaps the records is refused with FBUS_ERR_INVALID (the rule of fbus_ekf_snapshot_dev).
+ * 8. The argument check runs before anything is staged, in this order: NULL handle (FBUS_ERR_INVALID, no text); S out of range; NULL
+ *    xi; an output that overlaps the records -- the last three with the entry point's name in fbus_ekf_last_error.
+ * 9. _dev: device pointers, stream-ordered, capturable; a captured call reads the xi current at its replay.  The host form stages,
+ *    launches, waits and copies back; it is refused between graph_begin and graph_end.
+ * One kernel family, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, the noise table and the
+ * likelihood switch do not change the route, and two calls on the same inputs are bit-identical whatever the batch size or the
+ * filter's position in it.  Without an _async form.  Added under ABI 8 without a bump: detect the feature by symbol. */
+#define FBUS_SAMPLE_MAX 256
+int fbus_ekf_sample_dev(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn);
+int fbus_ekf_sample    (fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
