@@ -2,7 +2,7 @@
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
 The library is len(units()) translation units compiled in parallel and linked into one shared object:
-  fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose, hypothesis groups: ekf_group.hpp, depth update: ekf_depth.hpp, velocity update: ekf_velocity.hpp, general row update: ekf_rows.hpp, the steps those three share: ekf_sensor.hpp, marker screening: ekf_screen.hpp, NEES against a truth state: ekf_nees.hpp, draws from every filter's Gaussian: ekf_sample.hpp)
+  fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose, hypothesis groups: ekf_group.hpp, depth update: ekf_depth.hpp, velocity update: ekf_velocity.hpp, general row update: ekf_rows.hpp, the steps those three share: ekf_sensor.hpp, marker screening: ekf_screen.hpp, NEES against a truth state, and the record stream and column step it shares with the draws: ekf_nees.hpp, draws from every filter's Gaussian: ekf_sample.hpp)
   kernels_tu.hip, once per unit         one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
                                         every row of FAMILIES for float, the rows marked fp64 for double, each for N = 18 and N = 15
 Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.

@@ -103,6 +103,23 @@ constexpr int GROUP_EB = 16;            // covariance elements per reduction bat
 constexpr int GROUP_ROWS = 18;          // rows of the term buffer: a batch, or the N entries of mu
 constexpr int GROUP_TP = 65;            // pitch of one element's 64 terms (odd: the readers of neighbouring elements hit different banks)
 
+// The packed covariance in batches of GROUP_EB elements, as group_fuse_kernel (full covariance) and group_mix_kernel walk it: batch k is
+// the chunks c0(k) .. c1(k) - 1 of the record; fetch<k> requests it into pb[k] and does nothing behind the last batch
+template <typename T, int N>
+struct GroupBatches {
+    static constexpr int EPC = Rec<T, N>::EPC, CN = Rec<T, N>::CH_NOM;
+    static constexpr int CB = GROUP_EB / EPC;                               // chunks per batch
+    static constexpr int NCC = (Lay<N>::NP + EPC - 1) / EPC;                // covariance chunks that hold an element of P
+    static constexpr int NB = (NCC + CB - 1) / CB;
+    static constexpr int c0(int k) { return CN + k * CB; }
+    static constexpr int c1(int k) { return (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC; }
+    template <int k>
+    static __device__ __forceinline__ void fetch(const GroupMap<T, N>& gm, T (*pb)[GROUP_EB])
+    {
+        if constexpr (k < NB) gm.template load<c0(k), c1(k)>(pb[k]);
+    }
+};
+
 // term[e * GROUP_TP + lane], e < ECNT, written by every lane  ->  sink(group, e, sum over the group's members in member order).
 // A lane without a share wrote -0.0, which changes no sum (not even one that is -0.0 itself).
 template <int ECNT, typename SINK>
@@ -275,22 +292,14 @@ group_fuse_kernel(const T* __restrict__ recs, size_t rec_bytes, int B, int G, co
     if constexpr (FULL) {
         if (!P && !pdiag) return;
         for (int r = lane; r < N * N; r += BLOCK) tab[r] = (short)(IO::cov_elem(r) - L::OFF_COV);
-        constexpr int CB = GROUP_EB / EPC;                  // chunks per batch
-        constexpr int NCC = (NP + EPC - 1) / EPC;           // covariance chunks that hold an element of P
-        constexpr int NB = (NCC + CB - 1) / CB;
+        using GB = GroupBatches<T, N>;
+        constexpr int NB = GB::NB;
         constexpr int PF = sizeof(T) == 4 ? 4 : 2;          // batches requested ahead of the one being reduced (16 chunks)
         T pb[NB][GROUP_EB];
-        const auto fetch = [&](auto kc) {
-            constexpr int k = decltype(kc)::value;
-            if constexpr (k < NB) {
-                constexpr int c0 = CN + k * CB, c1 = (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC;
-                gm.template load<c0, c1>(pb[k]);
-            }
-        };
-        static_for<0, PF>(fetch);
+        static_for<0, PF>([&](auto kc) { GB::template fetch<decltype(kc)::value>(gm, pb); });
         static_for<0, NB>([&](auto kc) {
             constexpr int k = decltype(kc)::value;
-            fetch(std::integral_constant<int, k + PF>{});
+            GB::template fetch<k + PF>(gm, pb);
             constexpr int q0 = k * GROUP_EB;
             constexpr int ECNT = NP - q0 < GROUP_EB ? NP - q0 : GROUP_EB;
             static_for<0, ECNT>([&](auto ec) {
@@ -471,25 +480,17 @@ group_mix_kernel(T* __restrict__ recs, size_t rec_bytes, int B, int G, const dou
     }
 
     // ---- step 5: P0_j = sum_i W_ij (P_i + (delta_i - m_j)(delta_i - m_j)'), a batch of packed elements at a time ------------------------
-    constexpr int CB = GROUP_EB / EPC;                      // chunks per batch
-    constexpr int NCC = (NP + EPC - 1) / EPC;               // covariance chunks that hold an element of P
-    constexpr int NB = (NCC + CB - 1) / CB;
+    using GB = GroupBatches<T, N>;
+    constexpr int NB = GB::NB;
     constexpr int PF = 2;                                   // batches requested ahead of the one being mixed
     T pb[NB][GROUP_EB];
-    const auto fetch = [&](auto kc) {
-        constexpr int k = decltype(kc)::value;
-        if constexpr (k < NB) {
-            constexpr int c0 = CN + k * CB, c1 = (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC;
-            gm.template load<c0, c1>(pb[k]);
-        }
-    };
-    static_for<0, PF>(fetch);
+    static_for<0, PF>([&](auto kc) { GB::template fetch<decltype(kc)::value>(gm, pb); });
     static_for<0, NB>([&](auto kc) {
         constexpr int k = decltype(kc)::value;
-        fetch(std::integral_constant<int, k + PF>{});
+        GB::template fetch<k + PF>(gm, pb);
         constexpr int q0 = k * GROUP_EB;
         constexpr int ECNT = NP - q0 < GROUP_EB ? NP - q0 : GROUP_EB;
-        constexpr int c0 = CN + k * CB, c1 = (k + 1) * CB < NCC ? CN + (k + 1) * CB : CN + NCC;
+        constexpr int c0 = GB::c0(k), c1 = GB::c1(k);
 #pragma unroll
         for (int e = 0; e < ECNT; ++e) term[e * GROUP_TP + lane] = (double)pb[k][e];
         wave_lds_fence();

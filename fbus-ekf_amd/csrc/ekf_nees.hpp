@@ -65,31 +65,66 @@ __device__ __forceinline__ double nees_block3(const T* P, const double* dl)
     return r;
 }
 
-template <typename T, int N>
-__global__ void __launch_bounds__(BLOCK, 1)
-nees_kernel(const T* __restrict__ recs, int B, const double* __restrict__ truth, const unsigned char* __restrict__ skip, NeesOut out)
+// ---- what nees_kernel and sample_kernel (ekf_sample.hpp) share: one stream and one sub-diagonal step, so that the two cannot drift apart ----
+// The prologue of both: the lane's filter b, in = b < B, the clamped index bc (lanes past B run along on the last filter's inputs and
+// store nothing), the kernel's own loads own(bc), the skip byte, the nominal chunks (the carried rotation between q and v is not
+// read), then the covariance chunks in storage order, non-temporally.  nom and P are the caller's own arrays.
+template <typename T, int N, typename OWN>
+__device__ __forceinline__ void factor_stream(const T* __restrict__ recs, int B, const unsigned char* __restrict__ skip, int& b, bool& in,
+                                              int& bc, unsigned char& skin, T* nom, T* P, OWN own)
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
     static_assert(BLOCK == 64, "one wave per 64-filter tile");
-    constexpr int NP = L::NP;
-    const int b = blockIdx.x * BLOCK + threadIdx.x;
-    const bool in = b < B;
-    const int bc = in ? b : B - 1;                      // lanes past B run along on the last filter's inputs and store nothing
+    b = blockIdx.x * BLOCK + threadIdx.x;
+    in = b < B;
+    bc = in ? b : B - 1;
     const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
-    double tr[19];
-#pragma unroll
-    for (int i = 0; i < 19; ++i) tr[i] = ld_once(truth + (size_t)bc * 19 + i);
-    const unsigned char skin = skip ? skip[bc] : (unsigned char)0;
+    own(bc);
+    skin = skip ? skip[bc] : (unsigned char)0;
     order_fence();
-    T nom[L::NNOM], P[RC::NCOVP];
-    constexpr int C_PQ = RC::CH_PQ, C_V = L::OFF_V / RC::EPC;      // (the carried rotation between them is not read)
+    constexpr int C_PQ = RC::CH_PQ, C_V = L::OFF_V / RC::EPC;
     static_assert(L::OFF_V % RC::EPC == 0, "v, ba, bg, g start on a chunk boundary");
     load_chunks<T, N, 0, C_PQ>(rs, my_lane(), nom);
     load_chunks<T, N, C_V, RC::CH_NOM>(rs, my_lane(), nom + L::OFF_V);
     order_fence();
     load_chunks<T, N, RC::CH_NOM, RC::NCH, AUX_NT>(rs, my_lane(), P);
     order_fence();
+}
+
+// The rows of column a of L below its pivot, `is` = nees_rsqrt of the pivot (0: the column is dropped): L(i, a) at nees_tri<N>(a, i)
+template <typename T, int N, int a>
+__device__ __forceinline__ void factor_below(const T* P, double* Lf, double is)
+{
+    constexpr int sa = nees_ord(a);
+    static_for<a + 1, N>([&](auto i_) {
+        constexpr int i = decltype(i_)::value;
+        double v = (double)P[pidx<N>(sa, nees_ord(i))];
+        static_for<0, a>([&](auto k_) {
+            constexpr int k = decltype(k_)::value;
+            v -= Lf[nees_tri<N>(k, i)] * Lf[nees_tri<N>(k, a)];
+        });
+        Lf[nees_tri<N>(a, i)] = v * is;
+    });
+    __builtin_amdgcn_sched_barrier(0);                  // column by column: what is live stays the triangle (P ahead, L behind)
+}
+
+template <typename T, int N>
+__global__ void __launch_bounds__(BLOCK, 1)
+nees_kernel(const T* __restrict__ recs, int B, const double* __restrict__ truth, const unsigned char* __restrict__ skip, NeesOut out)
+{
+    using L = Lay<N>;
+    using RC = Rec<T, N>;
+    constexpr int NP = L::NP;
+    int b, bc;
+    bool in;
+    unsigned char skin;
+    double tr[19];
+    T nom[L::NNOM], P[RC::NCOVP];
+    factor_stream<T, N>(recs, B, skip, b, in, bc, skin, nom, P, [&](int row) __attribute__((always_inline)) {
+#pragma unroll
+        for (int i = 0; i < 19; ++i) tr[i] = ld_once(truth + (size_t)row * 19 + i);
+    });
 
     // ---- delta: q_true normalised in double, then group_delta with the record as the chart ---------------------------------------------
     {
@@ -146,16 +181,7 @@ nees_kernel(const T* __restrict__ recs, int B, const double* __restrict__ truth,
         nees_pin(y[a]);
         nees_pin(acc);
         nees_pin(logdet);
-        static_for<a + 1, N>([&](auto i_) {
-            constexpr int i = decltype(i_)::value;
-            double v = (double)P[pidx<N>(sa, nees_ord(i))];
-            static_for<0, a>([&](auto k_) {
-                constexpr int k = decltype(k_)::value;
-                v -= Lf[nees_tri<N>(k, i)] * Lf[nees_tri<N>(k, a)];
-            });
-            Lf[nees_tri<N>(a, i)] = v * is;
-        });
-        __builtin_amdgcn_sched_barrier(0);              // column by column: what is live stays the triangle (P ahead, L behind)
+        factor_below<T, N, a>(P, Lf, is);
         if constexpr (a == 2) cp = ok ? acc : nanv;
         if constexpr (a == 5) pose = ok ? acc : nanv;
     });

@@ -25,22 +25,12 @@ sample_kernel(const T* __restrict__ recs, int B, int S, const double* __restrict
 {
     using L = Lay<N>;
     using RC = Rec<T, N>;
-    static_assert(BLOCK == 64, "one wave per 64-filter tile");
     constexpr int NP = L::NP;
-    const int b = blockIdx.x * BLOCK + threadIdx.x;
-    const bool in = b < B;
-    const int bc = in ? b : B - 1;                      // lanes past B run along on the last filter's inputs and store nothing
-    const __amdgpu_buffer_rsrc_t rs = tile_rsrc<T, N>(recs, my_tile());
-    const unsigned char skin = skip ? skip[bc] : (unsigned char)0;
-    order_fence();
+    int b, bc;
+    bool in;
+    unsigned char skin;
     T nom[L::NNOM], P[RC::NCOVP];
-    constexpr int C_PQ = RC::CH_PQ, C_V = L::OFF_V / RC::EPC;      // (the carried rotation between them is not read)
-    static_assert(L::OFF_V % RC::EPC == 0, "v, ba, bg, g start on a chunk boundary");
-    load_chunks<T, N, 0, C_PQ>(rs, my_lane(), nom);
-    load_chunks<T, N, C_V, RC::CH_NOM>(rs, my_lane(), nom + L::OFF_V);
-    order_fence();
-    load_chunks<T, N, RC::CH_NOM, RC::NCH, AUX_NT>(rs, my_lane(), P);
-    order_fence();
+    factor_stream<T, N>(recs, B, skip, b, in, bc, skin, nom, P, [](int) {});
 
     // ---- the factorisation of nees_kernel, kept whole: L(i, a) at nees_tri<N>(a, i), the diagonal included ------------------------------
     double Lf[NP];
@@ -56,16 +46,7 @@ sample_kernel(const T* __restrict__ recs, int B, int S, const double* __restrict
         ok = ok && pos;
         const double is = nees_rsqrt(piv, pos);
         Lf[nees_tri<N>(a, a)] = pos ? sqrt(pos ? piv : 1.0) : 0.0;
-        static_for<a + 1, N>([&](auto i_) {
-            constexpr int i = decltype(i_)::value;
-            double v = (double)P[pidx<N>(sa, nees_ord(i))];
-            static_for<0, a>([&](auto k_) {
-                constexpr int k = decltype(k_)::value;
-                v -= Lf[nees_tri<N>(k, i)] * Lf[nees_tri<N>(k, a)];
-            });
-            Lf[nees_tri<N>(a, i)] = v * is;
-        });
-        __builtin_amdgcn_sched_barrier(0);              // column by column: what is live stays the triangle (P ahead, L behind)
+        factor_below<T, N, a>(P, Lf, is);
     });
     const bool dr = ok && !skin;
     if (in && out.drawn) out.drawn[b] = dr ? (unsigned char)1 : (unsigned char)0;

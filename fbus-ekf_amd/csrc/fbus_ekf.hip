@@ -664,16 +664,18 @@ int snapshot_row(fbus_ekf_t h, const TrajDst& tj, int f)
     return do_snapshot(h, tj.nom ? (char*)tj.nom + rows * 19 * es : nullptr, tj.pdiag ? (char*)tj.pdiag + rows * h->N * es : nullptr,
                        tj.applied ? tj.applied + rows : nullptr);
 }
+// does a device output of `bytes` at p overlap the records (the rule of fbus_ekf_snapshot_dev)?
+bool in_records(fbus_ekf_t h, const void* p, size_t bytes)
+{
+    const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes, a = reinterpret_cast<uintptr_t>(p);
+    return p && a < r1 && a + bytes > r0;
+}
 // outputs must not overlap the records (the kernels read the records while the rows go out); FBUS_ERR_INVALID otherwise
 int check_traj(fbus_ekf_t h, const TrajDst& tj, int nframes, const char* what)
 {
     const size_t es = esize(h), rows = (size_t)nframes * h->B;
-    const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes;
-    const struct { const void* p; size_t bytes; } outs[3] = { { tj.nom, rows * 19 * es }, { tj.pdiag, rows * h->N * es }, { tj.applied, rows } };
-    for (const auto& o : outs) {
-        const uintptr_t a = reinterpret_cast<uintptr_t>(o.p);
-        if (o.p && a < r1 && a + o.bytes > r0) return fail(h, FBUS_ERR_INVALID, std::string(what) + ": an output overlaps the records");
-    }
+    if (in_records(h, tj.nom, rows * 19 * es) || in_records(h, tj.pdiag, rows * h->N * es) || in_records(h, tj.applied, rows))
+        return fail(h, FBUS_ERR_INVALID, std::string(what) + ": an output overlaps the records");
     return FBUS_OK;
 }
 
@@ -1462,90 +1464,99 @@ int check_group(fbus_ekf_t h, const char* where, int G)
         return fail(h, FBUS_ERR_INVALID, std::string(where) + ": the batch of " + std::to_string(h->B) + " is not a multiple of G = " + std::to_string(G));
     return FBUS_OK;
 }
-// does a device output of `bytes` at p overlap the records (the rule of fbus_ekf_snapshot_dev)?
-bool in_records(fbus_ekf_t h, const void* p, size_t bytes)
-{
-    const uintptr_t r0 = reinterpret_cast<uintptr_t>(h->recs), r1 = r0 + h->rec_bytes, a = reinterpret_cast<uintptr_t>(p);
-    return p && a < r1 && a + bytes > r0;
-}
-int group_fuse_any(fbus_ekf_t h, Transport t, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
+// One wrapper for the calls that read the records and report on them, or rewrite them group by group: fbus_ekf_group_fuse / _collapse /
+// _mix, fbus_ekf_nees and fbus_ekf_sample, each also _dev.  (the order of the tests is part of the interface: include/fbus_ekf.h)
+// A caller returns on a NULL handle, takes its name from report_name, runs its own tests (check_group, required pointers, ranges),
+// describes its arrays and ends in report_any, which tests in this order: _dev, an output piece inside the records; host form, a
+// capture in progress, then `inspect` -- what only the host form can look at; only_reads, no output asked for: nothing to do.
+std::string report_name(const char* stem, Transport t) { return std::string("fbus_ekf_") + stem + (t == DEV ? "_dev" : ""); }
+template <typename INSPECT, typename GO>
+int report_any(fbus_ekf_t h, Transport t, const std::string& where, bool only_reads, Piece* pc, int n, INSPECT inspect, GO go)
 {
     DeviceGuard guard_(h);
-    const char* where = t == DEV ? "fbus_ekf_group_fuse_dev" : "fbus_ekf_group_fuse";
-    int rc = check_group(h, where, G);
-    if (rc != FBUS_OK) return rc;
-    if (!logw && !h->d_lik)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
-    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
-    const size_t es = esize(h), B = (size_t)h->B, NG = B / G, N = (size_t)h->N;
-    if (t == DEV) {          // (staged outputs are the handle's own buffers)
-        const struct { const void* p; size_t bytes; } outs[5] = { { weight, B * sizeof(double) }, { best, NG * sizeof(int32_t) },
-                                                                  { nominal, NG * 19 * es }, { P, NG * N * N * es }, { pdiag, NG * N * es } };
-        for (const auto& o : outs)
-            if (in_records(h, o.p, o.bytes)) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
+    bool any_out = false;
+    for (int i = 0; i < n; ++i) {
+        any_out = any_out || pc[i].out;
+        if (t == DEV && pc[i].out && in_records(h, pc[i].out, pc[i].bytes))     // (staged outputs are the handle's own buffers)
+            return fail(h, FBUS_ERR_INVALID, where + ": an output overlaps the records");
     }
-    if (!weight && !best && !nominal && !P && !pdiag) return FBUS_OK;
+    if (t != DEV) {
+        if (h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
+        const int rc = inspect();
+        if (rc != FBUS_OK) return rc;
+    }
+    if (only_reads && !any_out) return FBUS_OK;
+    return run_pieces(h, t, pc, n, go);
+}
+template <typename GO>
+int report_any(fbus_ekf_t h, Transport t, const std::string& where, bool only_reads, Piece* pc, int n, GO go)
+{
+    return report_any(h, t, where, only_reads, pc, n, [] { return (int)FBUS_OK; }, go);
+}
+
+int group_fuse_any(fbus_ekf_t h, Transport t, int G, const double* logw, double* weight, int32_t* best, void* nominal, void* P, void* pdiag)
+{
+    const std::string where = report_name("group_fuse", t);
+    const int rc = check_group(h, where.c_str(), G);
+    if (rc != FBUS_OK) return rc;
+    if (!logw && !h->d_lik) return fail(h, FBUS_ERR_INVALID, where + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
+    const size_t es = esize(h), B = (size_t)h->B, NG = B / G, N = (size_t)h->N;
     const void* dl;
     void *dw, *db, *dn, *dP, *dd;
     Piece pc[6] = { in_piece(logw, B * sizeof(double), &dl), out_piece(weight, B * sizeof(double), &dw),
                     out_piece(best, NG * sizeof(int32_t), &db), out_piece(nominal, NG * 19 * es, &dn),
                     out_piece(P, NG * N * N * es, &dP), out_piece(pdiag, NG * N * es, &dd) };
-    return run_pieces(h, t, pc, 6, [&] {
+    return report_any(h, t, where, true, pc, 6, [&] {
         return do_group_fuse(h, G, dl ? (const double*)dl : h->d_lik, (double*)dw, (int32_t*)db, dn, dP, dd);
     });
 }
 int group_collapse_any(fbus_ekf_t h, Transport t, int G, const int32_t* src)
 {
-    DeviceGuard guard_(h);
-    const char* where = t == DEV ? "fbus_ekf_group_collapse_dev" : "fbus_ekf_group_collapse";
-    int rc = check_group(h, where, G);
+    const std::string where = report_name("group_collapse", t);
+    const int rc = check_group(h, where.c_str(), G);
     if (rc != FBUS_OK) return rc;
-    if (!src) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": src is NULL");
+    if (!src) return fail(h, FBUS_ERR_INVALID, where + ": src is NULL");
     const size_t NG = (size_t)h->B / G;
-    if (t != DEV) {
-        if (h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    const auto members = [&] {
         for (size_t j = 0; j < NG; ++j)
             if (src[j] >= G)
-                return fail(h, FBUS_ERR_INVALID, std::string(where) + ": src[" + std::to_string(j) + "] = " + std::to_string(src[j]) +
+                return fail(h, FBUS_ERR_INVALID, where + ": src[" + std::to_string(j) + "] = " + std::to_string(src[j]) +
                                                  " is not a member of a group of " + std::to_string(G) + " (negative: skip the group)");
-    }
+        return (int)FBUS_OK;
+    };
     const void* ds;
     Piece pc[1] = { in_piece(src, NG * sizeof(int32_t), &ds) };
-    return run_pieces(h, t, pc, 1, [&] { return do_group_collapse(h, G, (const int32_t*)ds); });
+    return report_any(h, t, where, false, pc, 1, members, [&] { return do_group_collapse(h, G, (const int32_t*)ds); });
 }
 int group_mix_any(fbus_ekf_t h, Transport t, int G, const double* logw, const double* trans, double* weight, double* logc)
 {
-    DeviceGuard guard_(h);
-    const char* where = t == DEV ? "fbus_ekf_group_mix_dev" : "fbus_ekf_group_mix";
-    int rc = check_group(h, where, G);
+    const std::string where = report_name("group_mix", t);
+    const int rc = check_group(h, where.c_str(), G);
     if (rc != FBUS_OK) return rc;
-    if (!trans) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans is NULL");
-    if (!logw && !h->d_lik)
-        return fail(h, FBUS_ERR_INVALID, std::string(where) + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
-    const size_t B = (size_t)h->B;
-    if (t == DEV) {
-        if (in_records(h, weight, B * sizeof(double)) || in_records(h, logc, B * sizeof(double)))
-            return fail(h, FBUS_ERR_INVALID, std::string(where) + ": an output overlaps the records");
-    } else {
-        if (h->capturing) return fail(h, FBUS_ERR_INVALID, std::string(where) + ": not between graph_begin and graph_end");
+    if (!trans) return fail(h, FBUS_ERR_INVALID, where + ": trans is NULL");
+    if (!logw && !h->d_lik) return fail(h, FBUS_ERR_INVALID, where + ": logw is NULL and fbus_ekf_loglik_enable(h, 1) has not been called");
+    const auto stochastic = [&] {
         for (int i = 0; i < G; ++i) {
             double s = 0.0;
             for (int j = 0; j < G; ++j) {
                 const double v = trans[i * G + j];
                 if (!std::isfinite(v) || v < 0.0)
-                    return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans row " + std::to_string(i) + " column " + std::to_string(j) +
-                                                     " = " + std::to_string(v) + " is not a probability");
+                    return fail(h, FBUS_ERR_INVALID, where + ": trans row " + std::to_string(i) + " column " + std::to_string(j) + " = " +
+                                                     std::to_string(v) + " is not a probability");
                 s += v;
             }
             if (std::fabs(s - 1.0) > 1e-9)
-                return fail(h, FBUS_ERR_INVALID, std::string(where) + ": trans row " + std::to_string(i) + " sums to " + std::to_string(s) + ", not to 1");
+                return fail(h, FBUS_ERR_INVALID, where + ": trans row " + std::to_string(i) + " sums to " + std::to_string(s) + ", not to 1");
         }
-    }
+        return (int)FBUS_OK;
+    };
+    const size_t B = (size_t)h->B;
     const void *dl, *dt;
     void *dw, *dc;
     Piece pc[4] = { in_piece(logw, B * sizeof(double), &dl), in_piece(trans, (size_t)G * G * sizeof(double), &dt),
                     out_piece(weight, B * sizeof(double), &dw), out_piece(logc, B * sizeof(double), &dc) };
-    return run_pieces(h, t, pc, 4, [&] {
+    // (in place: runs with both outputs NULL)
+    return report_any(h, t, where, false, pc, 4, stochastic, [&] {
         return do_group_mix(h, G, dl ? (const double*)dl : h->d_lik, (const double*)dt, (double*)dw, (double*)dc);
     });
 }
@@ -1709,24 +1720,18 @@ int launch_nees_t(fbus_ekf_t h, const double* truth, const uint8_t* skip, const 
     return FBUS_OK;
 }
 int launch_nees(fbus_ekf_t h, const double* truth, const uint8_t* skip, const NeesOut& o) { DISPATCH(h, launch_nees_t, h, truth, skip, o); }
-// (the order of the tests is part of the interface: include/fbus_ekf.h)
 int nees_any(fbus_ekf_t h, Transport t, const double* truth, const uint8_t* skip, double* nees, double* err, double* lnp)
 {
-    DeviceGuard guard_(h);
     if (!h) return FBUS_ERR_INVALID;
-    const std::string where = t == DEV ? "fbus_ekf_nees_dev" : "fbus_ekf_nees";
+    const std::string where = report_name("nees", t);
     if (!truth) return fail(h, FBUS_ERR_INVALID, where + ": truth is NULL");
     const size_t B = (size_t)h->B, N = (size_t)h->N;
-    const size_t nb = B * FBUS_NEES_COLS * sizeof(double), eb = B * N * sizeof(double), lb = B * sizeof(double);
-    if (t == DEV && (in_records(h, nees, nb) || in_records(h, err, eb) || in_records(h, lnp, lb)))
-        return fail(h, FBUS_ERR_INVALID, where + ": an output overlaps the records");
-    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
-    if (!nees && !err && !lnp) return FBUS_OK;
     const void *dt, *ds;
     void *dn, *de, *dl;
-    Piece pc[5] = { in_piece(truth, B * 19 * sizeof(double), &dt), in_piece(skip, B, &ds), out_piece(nees, nb, &dn), out_piece(err, eb, &de),
-                    out_piece(lnp, lb, &dl) };
-    return run_pieces(h, t, pc, 5, [&] {
+    Piece pc[5] = { in_piece(truth, B * 19 * sizeof(double), &dt), in_piece(skip, B, &ds),
+                    out_piece(nees, B * FBUS_NEES_COLS * sizeof(double), &dn), out_piece(err, B * N * sizeof(double), &de),
+                    out_piece(lnp, B * sizeof(double), &dl) };
+    return report_any(h, t, where, true, pc, 5, [&] {
         return launch_nees(h, (const double*)dt, (const uint8_t*)ds, NeesOut{ (double*)dn, (double*)de, (double*)dl });
     });
 }
@@ -1741,24 +1746,18 @@ int launch_sample_t(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, 
     return FBUS_OK;
 }
 int launch_sample(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, const SampleOut& o) { DISPATCH(h, launch_sample_t, h, S, xi, skip, o); }
-// (the order of the tests is part of the interface: include/fbus_ekf.h)
 int sample_any(fbus_ekf_t h, Transport t, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn)
 {
-    DeviceGuard guard_(h);
     if (!h) return FBUS_ERR_INVALID;
-    const std::string where = t == DEV ? "fbus_ekf_sample_dev" : "fbus_ekf_sample";
+    const std::string where = report_name("sample", t);
     if (S < 1 || S > FBUS_SAMPLE_MAX) return fail(h, FBUS_ERR_INVALID, where + ": S must be 1.." + std::to_string(FBUS_SAMPLE_MAX));
     if (!xi) return fail(h, FBUS_ERR_INVALID, where + ": xi is NULL");
     const size_t B = (size_t)h->B, N = (size_t)h->N;
-    const size_t xb = (size_t)S * B * N * sizeof(double), sb = (size_t)S * B * 19 * sizeof(double);
-    if (t == DEV && (in_records(h, state, sb) || in_records(h, drawn, B)))
-        return fail(h, FBUS_ERR_INVALID, where + ": an output overlaps the records");
-    if (t != DEV && h->capturing) return fail(h, FBUS_ERR_INVALID, where + ": not between graph_begin and graph_end");
-    if (!state && !drawn) return FBUS_OK;
     const void *dx, *ds;
     void *dst, *dd;
-    Piece pc[4] = { in_piece(xi, xb, &dx), in_piece(skip, B, &ds), out_piece(state, sb, &dst), out_piece(drawn, B, &dd) };
-    return run_pieces(h, t, pc, 4, [&] {
+    Piece pc[4] = { in_piece(xi, (size_t)S * B * N * sizeof(double), &dx), in_piece(skip, B, &ds),
+                    out_piece(state, (size_t)S * B * 19 * sizeof(double), &dst), out_piece(drawn, B, &dd) };
+    return report_any(h, t, where, true, pc, 4, [&] {
         return launch_sample(h, S, (const double*)dx, (const uint8_t*)ds, SampleOut{ (double*)dst, (unsigned char*)dd });
     });
 }

@@ -492,6 +492,42 @@ class BatchedFilter:
             logw = torch.from_numpy(np.ascontiguousarray(logw, np.float64).ravel()).to(dev)
         return self._dev_checked(logw, self.B, "logw")
 
+    def _report_call(self, stem, head, inputs, outputs, device=None):
+        """One call of fbus_ekf_<stem>[_dev] that reads its inputs and fills fresh outputs (the group, NEES and sample families), in the
+        manner of _sensor_update.  head: the integer arguments in front.  inputs: (name, value, shape, dtype) in call order; a value
+        of None is an absent array, a shape of None a device tensor the caller has checked already.  A float64 input must come as
+        float64 (tested, never converted), any other is converted on the host branch and taken as it is on the device.  The first
+        input decides the branch: a device tensor takes the stream-ordered _dev form, anything else is staged -- unless `device` is
+        given, which takes the _dev form on that device.  outputs: (shape, dtype or None for the record type, wanted) in call order.
+        Returns the outputs as a tuple, None for one that is not wanted."""
+        lead, cur = inputs[0][1], None
+        if device is not None or _is_dev(lead):
+            import torch
+            transport, device = "_dev", lead.device if device is None else device
+            for name, a, shape, dtype in inputs:
+                if a is None or shape is None:
+                    continue
+                if dtype is np.float64 and a.dtype != torch.float64:
+                    raise ValueError(f"{stem}: {name} must be float64, got {a.dtype}")
+                self._dev_checked(a, int(np.prod(shape, dtype=np.int64)), name)
+            vals = [a for _, a, _, _ in inputs]
+            out = tuple(torch.empty(shape, dtype=getattr(torch, np.dtype(dt or self.np_dtype).name), device=device) if want else None
+                        for shape, dt, want in outputs)
+            self._keep += [o for o in out if o is not None]
+            cur = self._order_in(*vals, *out)
+        else:
+            transport, vals = "", []
+            for name, a, shape, dtype in inputs:
+                if a is not None and dtype is np.float64 and np.asarray(a).dtype != np.float64:
+                    raise ValueError(f"{stem}: {name} must be float64, got {np.asarray(a).dtype}")
+                vals.append(None if a is None else self._host(a, shape, dtype))
+            out = tuple(np.empty(shape, dt or self.np_dtype) if want else None for shape, dt, want in outputs)
+        name = stem + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, *head, *[self._p(a) for a in vals], *[self._p(o) for o in out])
+        self._check(rc, name)
+        self._order_out(cur)
+        return out
+
     def group_fuse(self, G, logw=None, full_cov=True):
         """Evidence-weighted, moment-matched fusion of every contiguous group of G filters (fbus_ekf_group_fuse_dev): returns
         (weight (B,) float64, best (B/G,) int32, nominal (B/G, 19), P (B/G, N, N) or None, pdiag (B/G, N)), torch tensors on the
@@ -501,17 +537,11 @@ class BatchedFilter:
         import torch
         G, NG = self._group_count(G, "group_fuse_dev")
         dev = torch.device("cuda", self.device)
-        tt = torch.float32 if self.dtype == 32 else torch.float64
         logw = self._group_logw(logw, dev, "group_fuse")
-        out = (torch.empty(self.B, dtype=torch.float64, device=dev), torch.empty(NG, dtype=torch.int32, device=dev),
-               torch.empty((NG, 19), dtype=tt, device=dev),
-               torch.empty((NG, self.N, self.N), dtype=tt, device=dev) if full_cov else None,
-               torch.empty((NG, self.N), dtype=tt, device=dev))
-        self._keep += [o for o in out if o is not None]
-        cur = self._order_in(logw, *out)
-        self._check(self._lib.fbus_ekf_group_fuse_dev(self._h, G, self._p(logw), *(self._p(o) for o in out)), "group_fuse_dev")
-        self._order_out(cur)
-        return out
+        B, N, f64 = self.B, self.N, np.float64
+        return self._report_call("group_fuse", (G,), [("logw", logw, None, f64)],
+                                 [((B,), f64, True), ((NG,), np.int32, True), ((NG, 19), None, True), ((NG, N, N), None, full_cov),
+                                  ((NG, N), None, True)], device=dev)
 
     def group_collapse(self, G, src):
         """Overwrite every member of group j with the record of its member src[j], bit for bit (fbus_ekf_group_collapse): nominal state,
@@ -561,12 +591,8 @@ class BatchedFilter:
             trans = torch.from_numpy(noise.check_transition(trans, G)).to(dev)
         self._dev_checked(trans, G * G, "trans")
         logw = self._group_logw(logw, dev, "group_mix")
-        out = (torch.empty(self.B, dtype=torch.float64, device=dev), torch.empty(self.B, dtype=torch.float64, device=dev))
-        self._keep += list(out)
-        cur = self._order_in(logw, trans, *out)
-        self._check(self._lib.fbus_ekf_group_mix_dev(self._h, G, self._p(logw), self._p(trans), *(self._p(o) for o in out)), "group_mix_dev")
-        self._order_out(cur)
-        return out
+        return self._report_call("group_mix", (G,), [("logw", logw, None, np.float64), ("trans", trans, None, np.float64)],
+                                 [((self.B,), np.float64, True)] * 2, device=dev)
 
     # ---- depth (pressure) sensor update (include/fbus_ekf.h; no reference counterpart) ---------------------------------------
     def set_depth_sensor(self, axis, offset=0.0, lever=None):
@@ -792,32 +818,9 @@ class BatchedFilter:
         B, N = self.B, self.N
         if tuple(getattr(truth, "shape", ())) != (B, 19):
             raise ValueError(f"nees: truth must be ({B}, 19), got {tuple(getattr(truth, 'shape', ()))}")
-        cur = None
-        if _is_dev(truth):
-            import torch
-            if truth.dtype != torch.float64:
-                raise ValueError(f"nees: truth must be float64, got {truth.dtype}")
-            self._dev_checked(truth, B * 19, "truth")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=truth.device)
-            transport = "_dev"
-        else:
-            if np.asarray(truth).dtype != np.float64:
-                raise ValueError(f"nees: truth must be float64, got {np.asarray(truth).dtype}")
-            truth = self._host(truth, (B, 19), np.float64)
-            skip = None if skip is None else self._host(skip, (B,), np.uint8)
-            mk = lambda *shape: np.empty(shape, np.float64)
-            transport = ""
-        out = (mk(B, capi.NEES_COLS), mk(B, N) if err else None, mk(B) if lnp else None)
-        if transport:
-            self._keep += [o for o in out if o is not None]
-            cur = self._order_in(truth, skip, *out)
-        name = "nees" + transport
-        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, self._p(truth), self._p(skip), *[self._p(o) for o in out])
-        self._check(rc, name)
-        self._order_out(cur)
-        res = tuple(o for o in out if o is not None)
+        res = tuple(o for o in self._report_call("nees", (), [("truth", truth, (B, 19), np.float64), ("skip", skip, (B,), np.uint8)],
+                                                 [((B, capi.NEES_COLS), np.float64, True), ((B, N), np.float64, err),
+                                                  ((B,), np.float64, lnp)]) if o is not None)
         return res[0] if len(res) == 1 else res
 
     # ---- draws from every filter's own Gaussian (include/fbus_ekf.h: fbus_ekf_sample) --------------------------------------------
@@ -836,30 +839,8 @@ class BatchedFilter:
         if len(shape) != 3 or shape[1:] != (B, N) or not 1 <= shape[0] <= capi.SAMPLE_MAX:
             raise ValueError(f"sample: xi must be (S, {B}, {N}) with S in 1..{capi.SAMPLE_MAX}, got {shape}")
         S = shape[0]
-        cur = None
-        if _is_dev(xi):
-            import torch
-            if xi.dtype != torch.float64:
-                raise ValueError(f"sample: xi must be float64, got {xi.dtype}")
-            self._dev_checked(xi, S * B * N, "xi")
-            if skip is not None:
-                self._dev_checked(skip, B, "skip")
-            out = (torch.empty((S, B, 19), dtype=torch.float64, device=xi.device),
-                   torch.empty(B, dtype=torch.uint8, device=xi.device) if drawn else None)
-            transport = "_dev"
-            self._keep += [o for o in out if o is not None]
-            cur = self._order_in(xi, skip, *out)
-        else:
-            if np.asarray(xi).dtype != np.float64:
-                raise ValueError(f"sample: xi must be float64, got {np.asarray(xi).dtype}")
-            xi = self._host(xi, (S, B, N), np.float64)
-            skip = None if skip is None else self._host(skip, (B,), np.uint8)
-            out = (np.empty((S, B, 19), np.float64), np.empty(B, np.uint8) if drawn else None)
-            transport = ""
-        name = "sample" + transport
-        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, S, self._p(xi), self._p(skip), *[self._p(o) for o in out])
-        self._check(rc, name)
-        self._order_out(cur)
+        out = self._report_call("sample", (S,), [("xi", xi, (S, B, N), np.float64), ("skip", skip, (B,), np.uint8)],
+                                [((S, B, 19), np.float64, True), ((B,), np.uint8, drawn)])
         return out if drawn else out[0]
 
     def perturb(self, xi, skip=None):
