@@ -2,10 +2,13 @@
 """Builds fbus-ekf_amd/lib/libfbus_ekf.so (HIP, gfx950) in-tree with hipcc.
 
 The library is len(units()) translation units compiled in parallel and linked into one shared object:
-  fbus_ekf.hip                          handle, C ABI, the small kernels (pack/unpack, init, EMA, marker pose, hypothesis groups: ekf_group.hpp, depth update: ekf_depth.hpp, velocity update: ekf_velocity.hpp, general row update: ekf_rows.hpp, the steps those three share: ekf_sensor.hpp, marker screening: ekf_screen.hpp, NEES against a truth state, and the record stream and column step it shares with the draws: ekf_nees.hpp, draws from every filter's Gaussian: ekf_sample.hpp)
+  fbus_ekf.hip                          handle and C ABI; it defines and launches no kernel (unit "main")
   kernels_tu.hip, once per unit         one kernel family for one (float|double, N = 18|15), both dialects (-DFBUS_TU_T/N/FAMILY):
                                         every row of FAMILIES for float, the rows marked fp64 for double, each for N = 18 and N = 15
-Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source they include is newer.
+  small_tu.hip, once per unit           the same for the small families (state I/O, hypothesis groups, sensor updates, screening, reports),
+                                        built with the base flags alone, and once more for the kernels that depend on neither N nor the
+                                        dialect (unit "common")
+Objects live in fbus-ekf_amd/lib/obj/ (git-ignored) and are rebuilt when a source or any header under csrc/ is newer.
   python build.py [--force] [--only f32_18_correct,...] [--jobs N]
 FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds (A/B of differently built kernels via FBUS_EKF_LIB).
 """
@@ -16,16 +19,17 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-HEADERS = [os.path.join(CSRC, h) for h in ("ekf_kernels.hpp", "ekf_device.hpp", "vision_device.hpp", "ekf_launch.hpp", "ekf_team.hpp", "ekf_meas.hpp", "ekf_meas_split.hpp", "ekf_group.hpp", "ekf_sensor.hpp", "ekf_depth.hpp", "ekf_velocity.hpp", "ekf_rows.hpp", "ekf_screen.hpp", "ekf_nees.hpp", "ekf_sample.hpp", "ekf_route.hpp")] + \
-          [os.path.join(HERE, "..", "include", "fbus_ekf.h")]
+HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".hpp")) + [os.path.join(HERE, "..", "include", "fbus_ekf.h")]
 OUT = os.environ.get("FBUS_OUT") or os.path.join(HERE, "lib", "libfbus_ekf.so")   # FBUS_OUT / FBUS_EXTRA_FLAGS: experiment builds
 OBJDIR = os.environ.get("FBUS_OBJDIR") or os.path.join(os.path.dirname(OUT), "obj" if not os.environ.get("FBUS_OUT") else
                                                        "obj_" + os.path.splitext(os.path.basename(OUT))[0])
 MAX_ILP = "-mllvm -amdgpu-sched-strategy=max-ilp"
-# One row per kernel family (kernels_tu.hip lists what each number holds):
+# One row per kernel family (kernels_tu.hip and small_tu.hip list what each number holds):
 #   name: (FBUS_TU_FAMILY, the family whose flags it is built with, built for fp64 records too)
 # An extension family (a kernel of another family with a trailing pack) is built with the flags of the family it extends, both record
 # types.  fp64 has one fused frame kernel (family "frame": frame2_kernel) and runs the windows frame by frame.
+# The small families (None in the place of that family) are built from small_tu.hip with the base flags alone: no scheduler flag, no
+# FBUS_*_FLAGS override.
 FAMILIES = {
     "predict":    (1,  "predict", True),
     "correct":    (2,  "correct", True),
@@ -46,7 +50,29 @@ FAMILIES = {
     "correctlik": (18, "correct", True),
     "framesnz":   (19, "frames",  False),   # the trajectory windows with per-filter noise (the resident windows of a tabled handle)
     "fmeasnz":    (20, "fmeas",   False),
+    "state":      (21, None,      True),    # pack / unpack / snapshot / reset_cov and the two initialisations
+    "group":      (22, None,      True),    # hypothesis groups
+    "sensor":     (23, None,      True),    # depth, velocity and general rows
+    "screen":     (24, None,      True),    # per-marker screening
+    "report":     (25, None,      True),    # NEES and draws
 }
+COMMON = 26                           # small_tu.hip's unit that is built once: the kernels that depend on neither N nor the dialect
+# Seconds one unit took to compile, N = 18 (N = 15: about 0.7 of it), in a forced build with 16 jobs (EXPERIMENTS.md): build() starts
+# the longest first.  fp32, then the fp64 units that differ much from their fp32 twin; a family that is missing counts as 10.
+SECONDS = {"fmeas": 53, "fmeast": 39, "meas": 39, "fmeasnz": 38, "frame": 35, "correctlik": 34, "team": 33, "correctnis": 32, "correctnz": 32,
+           "framest": 30, "correct": 29, "frames": 29, "framesnz": 27, "measlik": 19, "measnis": 19, "sensor": 19, "measnz": 17, "msplit": 13,
+           "report": 12, "group": 11, "screen": 11, "predict": 10, "prednz": 8, "state": 4}
+SECONDS_F64 = {"meas": 54, "correctnz": 39, "measnis": 25, "measnz": 24, "measlik": 24, "frame": 12}
+SECONDS_ONCE = {"main": 19, "common": 6}
+
+
+def seconds_of(name):
+    """the estimate behind build()'s start order, for a unit name of units()"""
+    if name in SECONDS_ONCE:
+        return SECONDS_ONCE[name]
+    tn, n, fam = name.split("_")
+    base = SECONDS_F64.get(fam, SECONDS.get(fam, 10)) if tn == "f64" else SECONDS.get(fam, 10)
+    return base * (1.0 if n == "18" else 0.7)
 # Per-family scheduler choice, fp32 units (measured in one run, B = 65 536, tools/ab_bench.sh, profiles/logs/r02_ab2.log): the
 # max-ILP strategy of the AMDGPU machine scheduler shortens the per-call kernels, where one wave per SIMD has nothing
 # but its own independent instructions to cover dependent-issue stalls (predict 13.4 -> 13.05 us, stacked correct
@@ -70,11 +96,14 @@ def hipcc():
 
 def units():
     """(name, source, defines)"""
-    out = [("main", os.path.join(CSRC, "fbus_ekf.hip"), [])]
+    out = [("main", os.path.join(CSRC, "fbus_ekf.hip"), []), ("common", os.path.join(CSRC, "small_tu.hip"), [f"-DFBUS_TU_FAMILY={COMMON}"])]
     for tn, t in TYPES.items():
         for n in (18, 15):
             for fam, (code, like, f64) in FAMILIES.items():
                 if tn == "f64" and not f64:
+                    continue
+                if like is None:            # a small family: the base flags and the three defines, nothing else
+                    out.append((f"{tn}_{n}_{fam}", os.path.join(CSRC, "small_tu.hip"), [f"-DFBUS_TU_T={t}", f"-DFBUS_TU_N={n}", f"-DFBUS_TU_FAMILY={code}"]))
                     continue
                 # fp32: the family's flags -- the fp64 kernels sit at the 512-register limit and spill more under max-ILP
                 flags = F32_FLAGS[like] if tn == "f32" else os.environ.get("FBUS_F64_FLAGS_" + fam.upper(), F64_FLAGS.get(like, ""))
@@ -136,8 +165,7 @@ def build(force=False, verbose=False, only=None, jobs=None):
             continue
         if force or _stale(obj, src, defs) or (only and any(o in name for o in only)):
             todo.append((name, [hipcc()] + flags + defs + ["-c", src, "-o", obj], obj, _flags_of(defs)))
-    # the fp64 / fused-frame units take longest: start them first
-    todo.sort(key=lambda u: (("f64" in u[0]) * 2 + ("frame" in u[0]) + ("correct" in u[0])), reverse=True)  # "frame" matches "frames" too
+    todo.sort(key=lambda u: seconds_of(u[0]), reverse=True)     # the longest first: the tail of the build is then a short unit
     jobs = jobs or int(os.environ.get("FBUS_JOBS", "0")) or min(8, os.cpu_count() or 1)
 
     def run(u):
@@ -163,9 +191,9 @@ def build(force=False, verbose=False, only=None, jobs=None):
 
 
 def build_host_asan(out=None):
-    """The library with the HOST half of fbus_ekf.hip (handle, argument checks, staging, parameter tables, RCCL binding) under
-    AddressSanitizer + UBSan: `-fsanitize=address,undefined -fno-gpu-sanitize` instruments host code only, the device code
-    objects are the normal ones (GPU ASan is not available on this pool).  Linked against the already built kernel objects.
+    """The library with fbus_ekf.hip (handle, argument checks, staging, parameter tables, RCCL binding) under AddressSanitizer + UBSan:
+    `-fsanitize=address,undefined -fno-gpu-sanitize` instruments host code only, and fbus_ekf.hip holds no kernel: every device code
+    object is the normal one (GPU ASan is not available on this pool).  Linked against the already built objects of all other units.
     Load it with LD_PRELOAD of clang's ASan runtime (tests/test_sanitizers_cpu.py)."""
     build()
     out = out or os.path.join(os.path.dirname(OUT), "libfbus_ekf_asan.so")

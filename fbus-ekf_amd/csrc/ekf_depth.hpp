@@ -1,6 +1,6 @@
 // ekf_depth.hpp -- the depth (pressure) sensor update (fbus_ekf_correct_depth*, include/fbus_ekf.h).  No reference counterpart: the
 // reference names the sensor (`namespace FBUSEKF // Underwater Vision IMU Depth EKF`, C++/include/common.hpp:16) and has no update for it.
-// Included by fbus_ekf.hip only, next to the hypothesis groups.  gfx950 only.
+// Included by small_tu.hip's sensor family only.  gfx950 only.
 //
 // One scalar row on the index set J = {p, theta} of the pose rows, with R the record's carried rotation:
 //     h(x) = axis . (p + R lever) + offset      H_p = axis'      H_theta = (lever x (R' axis))'
@@ -26,9 +26,6 @@
 #include "ekf_sensor.hpp"       // the exits and the gate rule, store_nominal, the two covariance passes, pin_chunk, launch_tile_k
 
 namespace {
-
-// the sensor, by value (fbus_ekf_set_depth_sensor): unit axis, reading at the world origin, lever arm in the IMU frame
-struct DepthSensor { double axis[3], offset, lever[3]; };
 
 template <typename T, int N>
 struct DepthCut {
@@ -156,3 +153,12 @@ correct_depth_kernel(T* recs /* not __restrict__: order_fence()'s memory clobber
 }
 
 }  // namespace
+
+namespace fbus {
+template <typename T, int N>
+void launch_depth_k(hipStream_t s, T* recs, int B, const T* z, const double* var, int var_stride, const unsigned char* skip,
+                    unsigned char* applied, const DepthSensor& ds, const double* thr, T* nis, int* dof, double* lik)
+{
+    launch_tile_k(correct_depth_kernel<T, N>, s, B, recs, B, z, var, var_stride, skip, applied, ds, thr, nis, dof, lik);
+}
+}  // namespace fbus

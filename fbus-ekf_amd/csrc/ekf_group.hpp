@@ -1,6 +1,7 @@
 // ekf_group.hpp -- hypothesis groups: evidence-weighted fusion, collapse and IMM mixing (fbus_ekf_group_fuse / fbus_ekf_group_collapse /
 // fbus_ekf_group_mix, include/fbus_ekf.h).  No reference counterpart: the reference runs one filter on one thread (C++/src/filter.cpp:190-250).
-// Included by fbus_ekf.hip only, next to pack / unpack / snapshot.  gfx950 only.
+// Its kernels are instantiated by small_tu.hip's group family only; the sensor and report headers take pk_row / pk_col and group_delta from
+// here.  gfx950 only.
 //
 // Mapping: ONE FILTER PER LANE, as everywhere.  Group j = filters j G .. j G + G - 1; a wave serves floor(64 / G) whole groups: lane l is
 // member l % G of its (l / G)-th group, lanes past floor(64 / G) * G idle.  A group never spans two waves, which is what makes collapse
@@ -525,3 +526,33 @@ group_mix_kernel(T* __restrict__ recs, size_t rec_bytes, int B, int G, const dou
 }
 
 }  // namespace
+
+namespace fbus {
+// grid: one wave per floor(64 / G) whole groups
+template <typename T, int N>
+void launch_group_fuse_k(hipStream_t s, const T* recs, size_t rec_bytes, int B, int G, const double* logw, double* weight, int* best,
+                         T* nominal, T* P, T* pdiag)
+{
+    const int ngw = 64 / G, grid = (B / G + ngw - 1) / ngw;
+    const size_t lds = group_fuse_lds<T, N>(ngw);
+    if (P)
+        hipLaunchKernelGGL((group_fuse_kernel<T, N, true>), dim3(grid), dim3(BLOCK), lds, s, recs, rec_bytes, B, G, logw, weight, best, nominal,
+                           P, pdiag);
+    else
+        hipLaunchKernelGGL((group_fuse_kernel<T, N, false>), dim3(grid), dim3(BLOCK), lds, s, recs, rec_bytes, B, G, logw, weight, best, nominal,
+                           (T*)nullptr, pdiag);
+}
+template <typename T, int N>
+void launch_group_collapse_k(hipStream_t s, T* recs, size_t rec_bytes, int B, int G, const int* src)
+{
+    const int ngw = 64 / G, grid = (B / G + ngw - 1) / ngw;
+    hipLaunchKernelGGL((group_collapse_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, s, recs, rec_bytes, B, G, src);
+}
+template <typename T, int N>
+void launch_group_mix_k(hipStream_t s, T* recs, size_t rec_bytes, int B, int G, const double* logw, const double* trans, double* weight,
+                        double* logc)
+{
+    const int ngw = 64 / G, grid = (B / G + ngw - 1) / ngw;
+    hipLaunchKernelGGL((group_mix_kernel<T, N>), dim3(grid), dim3(BLOCK), group_mix_lds(G), s, recs, rec_bytes, B, G, logw, trans, weight, logc);
+}
+}  // namespace fbus

@@ -1,10 +1,11 @@
 // ekf_kernels.hpp -- the __global__ kernels of libfbus_ekf.so and their record <-> register helpers.
-// Included by fbus_ekf.hip (launchers + C ABI) and by the single-kernel experiments under tools/ (which
-// instantiate one kernel and read its ISA / time it in isolation).  gfx950 only.
+// Included by the kernel units (kernels_tu.hip, small_tu.hip; never by fbus_ekf.hip) and by the single-kernel experiments under
+// tools/ (which instantiate one kernel and read its ISA / time it in isolation).  gfx950 only.
 #pragma once
 #include "../../include/fbus_ekf.h"
 #include "ekf_device.hpp"
 #include "vision_device.hpp"
+#include "ekf_launch.hpp"       // the launchers' declarations and the argument types that cross to the host unit
 
 #include <hip/hip_runtime.h>
 
@@ -1661,3 +1662,57 @@ reset_cov_kernel(T* __restrict__ recs, int B, T d0, T d1, T d2, T d3, T d4, T d5
 }
 
 }  // namespace
+
+// ---- launchers of the kernels above that belong to no large family (declared in ekf_launch.hpp; instantiated in small_tu.hip: the ones
+// templated on N in family "state", the others in the unit that is built once) ----------------------------------------------------------------
+namespace fbus {
+template <typename T, int N>
+void launch_pack_k(hipStream_t s, T* recs, int B, const T* nominal, const T* rot, const T* P, const int* prev)
+{
+    hipLaunchKernelGGL((pack_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, recs, B, nominal, rot, P, prev);
+}
+template <typename T, int N>
+void launch_unpack_k(hipStream_t s, const T* recs, int B, T* nominal, T* rot, T* P, int* prev)
+{
+    hipLaunchKernelGGL((unpack_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, recs, B, nominal, rot, P, prev);
+}
+template <typename T, int N>
+void launch_reset_cov_k(hipStream_t s, T* recs, int B, const double* p0)
+{
+    hipLaunchKernelGGL((reset_cov_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, recs, B, (T)p0[0], (T)p0[1], (T)p0[2],
+                       (T)p0[3], (T)p0[4], (T)p0[5]);
+}
+template <typename T, int N>
+void launch_snapshot_k(hipStream_t s, const T* recs, int B, const unsigned char* d_applied, T* nominal, T* pdiag, unsigned char* applied)
+{
+    hipLaunchKernelGGL((snapshot_kernel<T, N>), dim3((B + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, recs, B, d_applied, nominal, pdiag, applied);
+}
+template <typename T, int N>
+void launch_init_gravity_bias_k(hipStream_t s, T* recs, int B, int Tn, const T* accel, const T* gyro)
+{
+    hipLaunchKernelGGL((init_gravity_bias_kernel<T, N>), dim3((B + 255) / 256), dim3(256), 0, s, recs, B, Tn, accel, gyro);
+}
+template <typename T, int N, int D>
+void launch_pose_init_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int what, double max_dist,
+                        const unsigned char* mask, T* out7, unsigned char* applied, const DevConst<T>& dc)
+{
+    hipLaunchKernelGGL((pose_init_kernel<T, N, D>), dim3((B + 255) / 256), dim3(256), 0, s, recs, B, M, ids, pos, quat, what, (T)max_dist, mask,
+                       out7, applied, dc);
+}
+template <typename T>
+void launch_marker_pose_k(hipStream_t s, int n, int geometry, const T* left, const T* right, T* pos, T* quat, T* corners3d,
+                          const VisConst<double>& vc)
+{
+    hipLaunchKernelGGL((marker_pose_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, n, geometry, left, right, pos, quat, corners3d, vc);
+}
+template <typename T>
+void launch_imu_ema_k(hipStream_t s, int B, int Tn, T* accel, T* gyro, T* carry, int have_carry)
+{
+    hipLaunchKernelGGL((imu_ema_kernel<T>), dim3((B + 255) / 256), dim3(256), 0, s, B, Tn, accel, gyro, carry, have_carry);
+}
+template <typename T>
+void launch_l0_eval_k(hipStream_t s, int op, int n, const T* a, const T* b, T* out)
+{
+    hipLaunchKernelGGL((l0_eval_kernel<T>), dim3((n + 255) / 256), dim3(256), 0, s, op, n, a, b, out);
+}
+}  // namespace fbus

@@ -1,9 +1,12 @@
-// ekf_launch.hpp -- host-callable launchers of the large kernel families.
+// ekf_launch.hpp -- host-callable launchers of every kernel of the library, and the argument types that cross from the host unit to them.
 //
 // The library is built from several translation units so that the kernels compile in parallel (and a kernel under
-// work rebuilds in seconds): kernels_tu.hip is compiled once per (scalar type, state size, family) with
-// -DFBUS_TU_T / -DFBUS_TU_N / -DFBUS_TU_FAMILY and holds the explicit instantiations of the function templates
-// declared here (both dialects); fbus_ekf.hip (handle, C ABI, the small kernels) only sees these declarations.
+// work rebuilds in seconds): kernels_tu.hip (the predict / update / frame families) and small_tu.hip (state I/O, hypothesis groups,
+// sensor updates, screening, reports) are compiled once per (scalar type, state size, family) with
+// -DFBUS_TU_T / -DFBUS_TU_N / -DFBUS_TU_FAMILY and hold the explicit instantiations of the function templates
+// declared here (both dialects); small_tu.hip is compiled once more for the kernels that depend on neither.  fbus_ekf.hip (handle,
+// C ABI) holds no kernel and launches none: it only sees these declarations.  A type named in a launcher's signature is declared
+// here, in namespace fbus: a launcher that names a type of an anonymous namespace has internal linkage and never reaches the linker.
 //
 // A launcher whose kernel takes a trailing parameter pack takes the same pack (`X... x`) and hands it on: one launcher and one
 // kernel choice per kernel, whatever the pack.  The packs that are instantiated (each in a unit of its own, listed at the top of
@@ -116,5 +119,87 @@ void launch_frame_meas_k(hipStream_t s, T* recs, int B, int F, const unsigned ch
                          int M, const int* ids, const T* left, const T* right, int geometry, int mode, double size, double r_meas,
                          double switch_thres, const unsigned char* skip, unsigned char* applied, const short* id2slot,
                          const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const T* qd, X... x);
+
+// ---- record I/O and initialisation (ekf_kernels.hpp; family "state") -----------------------------------------------------------------------
+// one wave per 64-filter tile (pack, unpack, snapshot, reset_cov) / one thread per filter (the two initialisations)
+template <typename T, int N>
+void launch_pack_k(hipStream_t s, T* recs, int B, const T* nominal, const T* rot, const T* P, const int* prev);
+template <typename T, int N>
+void launch_unpack_k(hipStream_t s, const T* recs, int B, T* nominal, T* rot, T* P, int* prev);
+// p0: the six variances of fbus_params::p0_diag
+template <typename T, int N>
+void launch_reset_cov_k(hipStream_t s, T* recs, int B, const double* p0);
+template <typename T, int N>
+void launch_snapshot_k(hipStream_t s, const T* recs, int B, const unsigned char* d_applied, T* nominal, T* pdiag, unsigned char* applied);
+template <typename T, int N>
+void launch_init_gravity_bias_k(hipStream_t s, T* recs, int B, int Tn, const T* accel, const T* gyro);
+template <typename T, int N, int D>
+void launch_pose_init_k(hipStream_t s, T* recs, int B, int M, const int* ids, const T* pos, const T* quat, int what, double max_dist,
+                        const unsigned char* mask, T* out7, unsigned char* applied, const DevConst<T>& dc);
+
+// ---- hypothesis groups (ekf_group.hpp; family "group"): one wave per floor(64 / G) whole groups ---------------------------------------------
+// P == nullptr: the diagonal alone (the kernel without the dense covariance)
+template <typename T, int N>
+void launch_group_fuse_k(hipStream_t s, const T* recs, size_t rec_bytes, int B, int G, const double* logw, double* weight, int* best,
+                         T* nominal, T* P, T* pdiag);
+template <typename T, int N>
+void launch_group_collapse_k(hipStream_t s, T* recs, size_t rec_bytes, int B, int G, const int* src);
+template <typename T, int N>
+void launch_group_mix_k(hipStream_t s, T* recs, size_t rec_bytes, int B, int G, const double* logw, const double* trans, double* weight,
+                        double* logc);
+
+// ---- the streamed sensor updates (ekf_depth.hpp, ekf_velocity.hpp, ekf_rows.hpp; family "sensor"): one wave per tile ------------------------
+// the depth sensor, by value (fbus_ekf_set_depth_sensor): unit axis, reading at the world origin, lever arm in the IMU frame
+struct DepthSensor { double axis[3], offset, lever[3]; };
+// the velocity sensor, by value (fbus_ekf_set_velocity_sensor): the rotation IMU frame -> instrument frame (row-major), the instrument's
+// position in the IMU frame
+struct VelocitySensor { double C[9], lever[3]; };
+// thr: the gate table; nis, dof, lik: each may be null
+template <typename T, int N>
+void launch_depth_k(hipStream_t s, T* recs, int B, const T* z, const double* var, int var_stride, const unsigned char* skip,
+                    unsigned char* applied, const DepthSensor& ds, const double* thr, T* nis, int* dof, double* lik);
+template <typename T, int N>
+void launch_velocity_k(hipStream_t s, T* recs, int B, const T* z, const T* gyro, const double* var, int var_stride,
+                       const unsigned char* skip, unsigned char* applied, const VelocitySensor& vs, const double* thr, T* nis, int* dof,
+                       double* lik);
+// m = 1..3 rows per filter: picks the instantiation
+template <typename T, int N>
+void launch_rows_k(hipStream_t s, T* recs, int B, int m, const T* res, const T* H, const double* var, int var_stride,
+                   const unsigned char* skip, unsigned char* applied, const double* thr, T* nis, int* dof, double* lik);
+
+// ---- per-marker screening (ekf_screen.hpp; family "screen"): one wave per tile -------------------------------------------------------------
+enum { SCREEN_PIX_LEFT = 0, SCREEN_PIX_STEREO = 1, SCREEN_CORNERS = 2 };
+// where the verdicts go: ids_out [B][M], nis [B][M] in T, dof [B][M], kept [B]; each may be null.  thr: the handle's gate table
+template <typename T> struct ScreenOut { int* ids; T* nis; int* dof; int* kept; const double* thr; };
+template <typename T, int N, int KIND>
+void launch_screen_meas_k(hipStream_t st, const T* recs, int B, int M, const int* ids, const T* a, const T* bb, int geometry, bool square_port,
+                          double size, double r_meas, const double* noise, const unsigned char* skip, const short* id2slot,
+                          const MeasConst& mc, const VisConst<double>& vc, const VisConst<T>& vct, const ScreenOut<T>& out);
+template <typename T, int N, int DIALECT>
+void launch_screen_pose_k(hipStream_t st, const T* recs, int B, int M, const int* ids, const T* pos, const T* quat, const double* noise,
+                          const unsigned char* skip, const DevConst<T>& dc, const ScreenOut<T>& out);
+
+// ---- NEES and draws (ekf_nees.hpp, ekf_sample.hpp; family "report"): one wave per tile ------------------------------------------------------
+struct NeesOut { double* nees; double* err; double* lnp; };     // [B][FBUS_NEES_COLS], [B][N], [B]; each may be null
+struct SampleOut { double* state; unsigned char* drawn; };      // [S][B][19], [B]; each may be null
+template <typename T, int N>
+void launch_nees_k(hipStream_t st, const T* recs, int B, const double* truth, const unsigned char* skip, const NeesOut& out);
+template <typename T, int N>
+void launch_sample_k(hipStream_t st, const T* recs, int B, int S, const double* xi, const unsigned char* skip, const SampleOut& out);
+
+// ---- the kernels that depend on neither the state size nor the dialect (small_tu.hip, built once; unit "common") -----------------------------
+template <typename T>
+void launch_marker_pose_k(hipStream_t s, int n, int geometry, const T* left, const T* right, T* pos, T* quat, T* corners3d,
+                          const VisConst<double>& vc);
+template <typename T>
+void launch_imu_ema_k(hipStream_t s, int B, int Tn, T* accel, T* gyro, T* carry, int have_carry);
+template <typename T>
+void launch_l0_eval_k(hipStream_t s, int op, int n, const T* a, const T* b, T* out);
+// B x FBUS_NOISE_COLS row-major -> fields [FBUS_NOISE_COLS][B] (fbus_ekf_set_noise_dev)
+void launch_noise_fields_k(hipStream_t s, const double* rows, double* fields, int B);
+// one row (q_v, q_theta, q_ba, q_bg, r_pos, r_quat, r_pix) into every filter's fields
+void launch_noise_own_row_k(hipStream_t s, double* fields, int B, const double* row);
+// the sums [4][B] as doubles -> the caller's typed arrays (fbus_ekf_loglik_get*; each may be null)
+void launch_lik_export_k(hipStream_t s, const double* acc, int B, double* ll, int64_t* rows, int32_t* applied, int32_t* rejected);
 
 }  // namespace fbus

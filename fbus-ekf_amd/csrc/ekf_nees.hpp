@@ -1,6 +1,6 @@
 // ekf_nees.hpp -- NEES, error and log-density of every filter against a truth state (fbus_ekf_nees*, include/fbus_ekf.h).  No reference
 // counterpart: the reference runs one filter and is judged off line; the model is stated in the header.
-// Included by fbus_ekf.hip only, next to the marker screening.  gfx950 only.
+// Included by small_tu.hip's report family only, through ekf_sample.hpp.  gfx950 only.
 //
 // With delta = truth (-) estimate (step 3 of fbus_ekf_group_fuse with the record as the chart: group_delta, ekf_group.hpp) a column of
 // `nees` is delta_J' (P_JJ)^-1 delta_J = |L^-1 delta_J|^2, L L' = P_JJ, in double for both record types.
@@ -17,10 +17,9 @@
 // the factorisation runs on with that column of L zeroed, so nothing it poisons is read by a column that is still clean.
 #pragma once
 #include "ekf_group.hpp"
+#include "ekf_launch.hpp"        // NeesOut, SampleOut
 
 namespace {
-
-struct NeesOut { double* nees; double* err; double* lnp; };     // [B][FBUS_NEES_COLS], [B][N], [B]; each may be null
 
 // the state behind position k of the factorisation order p, theta, v, ba, bg, g
 __host__ __device__ constexpr int nees_ord(int k) { return k < 3 ? k : k < 6 ? k + 3 : k < 9 ? k - 3 : k; }
@@ -190,11 +189,13 @@ nees_kernel(const T* __restrict__ recs, int B, const double* __restrict__ truth,
     if (in && out.lnp) out.lnp[b] = skin ? 0.0 : lnp;
 }
 
+}  // namespace
+
+namespace fbus {
 // grid: one wave per tile
 template <typename T, int N>
 void launch_nees_k(hipStream_t st, const T* recs, int B, const double* truth, const unsigned char* skip, const NeesOut& out)
 {
     hipLaunchKernelGGL((nees_kernel<T, N>), dim3((B + 63) / 64), dim3(BLOCK), 0, st, recs, B, truth, skip, out);
 }
-
-}  // namespace
+}  // namespace fbus

@@ -1,7 +1,7 @@
 // ekf_rows.hpp -- the general linearised measurement update (fbus_ekf_correct_rows*, include/fbus_ekf.h): the caller hands over the
 // innovation and the Jacobian rows, the library does the gain, the injection, the covariance, the NIS, the gate and the likelihood.
 // No reference counterpart (the reference has its pose rows and nothing else); the algebra is stated in the header.  Included by
-// fbus_ekf.hip only, next to ekf_velocity.hpp.  gfx950 only.
+// small_tu.hip's sensor family only.  gfx950 only.
 //
 // M rows (1..FBUS_ROWS_MAX) with DENSE H, every column of the error state p v theta ba bg [g] may be in play:
 //     S = H P H' + diag(var)      U = P H'      dx = U S^-1 res -> inject()      P <- P - U S^-1 U'
@@ -204,3 +204,19 @@ correct_rows_kernel(T* recs /* not __restrict__: see correct_depth_kernel */, in
 }
 
 }  // namespace
+
+namespace fbus {
+template <typename T, int N>
+void launch_rows_k(hipStream_t s, T* recs, int B, int m, const T* res, const T* H, const double* var, int var_stride,
+                   const unsigned char* skip, unsigned char* applied, const double* thr, T* nis, int* dof, double* lik)
+{
+    const auto go = [&](auto mc) {
+        launch_tile_k(correct_rows_kernel<T, N, decltype(mc)::value>, s, B, recs, B, res, H, var, var_stride, skip, applied, thr, nis, dof, lik);
+    };
+    switch (m) {
+    case 1: go(std::integral_constant<int, 1>{}); break;
+    case 2: go(std::integral_constant<int, 2>{}); break;
+    default: go(std::integral_constant<int, 3>{}); break;
+    }
+}
+}  // namespace fbus

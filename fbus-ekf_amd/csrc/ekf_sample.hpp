@@ -1,5 +1,5 @@
 // ekf_sample.hpp -- draws from every filter's own Gaussian N(estimate, P) (fbus_ekf_sample*, include/fbus_ekf.h): the inverse of NEES.
-// No reference counterpart; the model is stated in the header.  Included by fbus_ekf.hip only, next to ekf_nees.hpp.  gfx950 only.
+// No reference counterpart; the model is stated in the header.  Included by small_tu.hip's report family only.  gfx950 only.
 //
 // With L L' = Pi P Pi' in the factorisation order of nees_kernel (p, theta, v, ba, bg, g: nees_ord) a draw is delta = Pi' L xi, injected
 // into the record's nominal state in double: plain sums, and q <- normalize(q (x) dq(delta_theta)) -- inject() of ekf_device.hpp in double,
@@ -16,8 +16,6 @@
 #include "ekf_nees.hpp"
 
 namespace {
-
-struct SampleOut { double* state; unsigned char* drawn; };      // [S][B][19], [B]; each may be null
 
 template <typename T, int N>
 __global__ void __launch_bounds__(BLOCK, 1)
@@ -112,11 +110,13 @@ sample_kernel(const T* __restrict__ recs, int B, int S, const double* __restrict
     }
 }
 
+}  // namespace
+
+namespace fbus {
 // grid: one wave per tile
 template <typename T, int N>
 void launch_sample_k(hipStream_t st, const T* recs, int B, int S, const double* xi, const unsigned char* skip, const SampleOut& out)
 {
     hipLaunchKernelGGL((sample_kernel<T, N>), dim3((B + 63) / 64), dim3(BLOCK), 0, st, recs, B, S, xi, skip, out);
 }
-
-}  // namespace
+}  // namespace fbus

@@ -1,7 +1,7 @@
 // ekf_screen.hpp -- per-marker chi-square screening of a frame's marker slots (fbus_ekf_screen_markers*, include/fbus_ekf.h).
 // Reference counterpart in PLACE, not in test: VISION::RejectInvalidMarker (C++/src/vision.cpp:825-853, called at :73) drops single
 // detections in front of SetDetectionResult by their apparent motion; this drops them by their individual compatibility with the prior.
-// Included by fbus_ekf.hip only, next to the hypothesis groups and the depth update.  gfx950 only.
+// Included by small_tu.hip's screen family only.  gfx950 only.
 //
 // Every marker slot m of every filter is judged ALONE: the rows the kind's stacked update would fold for slot m, at the current record,
 //     nis_m = r_m' (H_m P H_m' + R_m)^-1 r_m = w sum res^2 - b_m' (P_JJ^-1 + Lam_m)^-1 b_m        (Lam_m, b_m: the fold's 6 x 6 sums)
@@ -22,11 +22,6 @@
 #include "ekf_meas.hpp"
 
 namespace {
-
-enum { SCREEN_PIX_LEFT = 0, SCREEN_PIX_STEREO = 1, SCREEN_CORNERS = 2 };
-
-// where the verdicts go: ids_out [B][M], nis [B][M] in T, dof [B][M], kept [B]; each may be null.  thr: the handle's gate table
-template <typename T> struct ScreenOut { int* ids; T* nis; int* dof; int* kept; const double* thr; };
 
 // what depends on the filter alone: the Cholesky factor C (lower, row-major 6 x 6; a pivot that is not positive drops its column, as
 // pose_nis does) of P_JJ, read from the chunks that hold it, and `poison`: 0, or NaN when P_JJ holds a non-finite value (a dropped
@@ -359,6 +354,9 @@ screen_pose_kernel(const T* __restrict__ recs, int B, int M, const int* ids, con
     if (b < B && out.kept) out.kept[b] = kept;
 }
 
+}  // namespace
+
+namespace fbus {
 // grid: one wave per tile
 template <typename T, int N, int KIND>
 void launch_screen_meas_k(hipStream_t st, const T* recs, int B, int M, const int* ids, const T* a, const T* bb, int geometry, bool square_port,
@@ -380,5 +378,4 @@ void launch_screen_pose_k(hipStream_t st, const T* recs, int B, int M, const int
     hipLaunchKernelGGL((screen_pose_kernel<T, N, DIALECT>), dim3((B + 63) / 64), dim3(64), 0, st, recs, B, M, ids, pos, quat, noise, skip, dc,
                        out);
 }
-
-}  // namespace
+}  // namespace fbus

@@ -5,6 +5,7 @@
 #pragma once
 #include "ekf_group.hpp"        // pk_row / pk_col: (row, column) of a packed covariance element
 #include "ekf_kernels.hpp"
+#include "ekf_launch.hpp"        // DepthSensor, VelocitySensor and the launchers' declarations
 
 namespace {
 

@@ -1,6 +1,6 @@
 // ekf_velocity.hpp -- the body-velocity (DVL, zero-velocity) update (fbus_ekf_correct_velocity*, include/fbus_ekf.h).  No reference
-// counterpart: the reference has no velocity measurement, the model is stated in the header.  Included by fbus_ekf.hip only, next to
-// ekf_depth.hpp.  gfx950 only.
+// counterpart: the reference has no velocity measurement, the model is stated in the header.  Included by small_tu.hip's sensor family
+// only.  gfx950 only.
 //
 // Three rows on the index set V = {v, theta, bg} (columns 3..8 and 12..14), with R the record's carried rotation, C the mount and
 // w = gyro - bg:
@@ -29,10 +29,6 @@
 #include "ekf_sensor.hpp"       // the exits and the gate rule, store_nominal, the two row steps and covariance passes, launch_tile_k
 
 namespace {
-
-// the sensor, by value (fbus_ekf_set_velocity_sensor): the rotation IMU frame -> instrument frame (row-major), the instrument's position
-// in the IMU frame
-struct VelocitySensor { double C[9], lever[3]; };
 
 __host__ __device__ constexpr int vcol(int k) { return k < 6 ? k + 3 : k + 6; }          // V-position -> state column
 // the column set of a row of H (ekf_sensor.hpp): its 9 entries on V
@@ -187,3 +183,13 @@ correct_velocity_kernel(T* recs /* not __restrict__: see correct_depth_kernel */
 }
 
 }  // namespace
+
+namespace fbus {
+template <typename T, int N>
+void launch_velocity_k(hipStream_t s, T* recs, int B, const T* z, const T* gyro, const double* var, int var_stride,
+                       const unsigned char* skip, unsigned char* applied, const VelocitySensor& vs, const double* thr, T* nis, int* dof,
+                       double* lik)
+{
+    launch_tile_k(correct_velocity_kernel<T, N>, s, B, recs, B, z, gyro, var, var_stride, skip, applied, vs, thr, nis, dof, lik);
+}
+}  // namespace fbus

@@ -1,5 +1,6 @@
-// fbus_ekf.hip -- kernels, launchers and the C ABI (include/fbus_ekf.h) of the
-// MI355X-native batched error-state EKF.  gfx950 only; no CPU fallback.
+// fbus_ekf.hip -- the handle and the C ABI (include/fbus_ekf.h) of the MI355X-native batched error-state EKF: argument checks,
+// transports, the choice of <T, N[, D]>, timing and the records_warm bookkeeping.  No kernel is defined or launched here: every
+// launch goes through a launcher declared in ekf_launch.hpp and built in a kernel unit.  gfx950 only; no CPU fallback.
 //
 // HBM layout of the filter records ("64-filter tiles of 16-byte chunks"): a record is
 // NRECP elements of T = NCH chunks of 16 bytes.  Filters are grouped in tiles of 64
@@ -10,15 +11,7 @@
 // NCH KiB region, and a rank's records are one contiguous block for the RCCL gather.
 #define FBUS_EKF_NO_ABI_CHECK      // this file DEFINES fbus_ekf_create: no macro here
 #include "../../include/fbus_ekf.h"
-#include "ekf_kernels.hpp"
 #include "ekf_launch.hpp"
-#include "ekf_group.hpp"
-#include "ekf_depth.hpp"
-#include "ekf_velocity.hpp"
-#include "ekf_rows.hpp"
-#include "ekf_screen.hpp"
-#include "ekf_nees.hpp"
-#include "ekf_sample.hpp"
 #include "ekf_route.hpp"
 
 #include <hip/hip_runtime.h>
@@ -523,9 +516,7 @@ int launch_frames_team(fbus_ekf_t h, int F, const unsigned char* kc, const void*
 template <typename T, int N>
 int pack_t(fbus_ekf_t h, const void* nom, const void* rot, const void* P, const int32_t* prev)
 {
-    const int grid = (h->B + BLOCK - 1) / BLOCK;             // one wave per 64-filter tile
-    hipLaunchKernelGGL((pack_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (T*)h->recs, h->B,
-                       (const T*)nom, (const T*)rot, (const T*)P, (const int*)prev);
+    launch_pack_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)nom, (const T*)rot, (const T*)P, (const int*)prev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -533,9 +524,7 @@ int pack_t(fbus_ekf_t h, const void* nom, const void* rot, const void* P, const 
 template <typename T, int N>
 int unpack_t(fbus_ekf_t h, void* nom, void* rot, void* P, int32_t* prev)
 {
-    const int grid = (h->B + BLOCK - 1) / BLOCK;             // one wave per 64-filter tile
-    hipLaunchKernelGGL((unpack_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (const T*)h->recs, h->B,
-                       (T*)nom, (T*)rot, (T*)P, (int*)prev);
+    launch_unpack_k<T, N>(h->stream, (const T*)h->recs, h->B, (T*)nom, (T*)rot, (T*)P, (int*)prev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -543,10 +532,7 @@ int unpack_t(fbus_ekf_t h, void* nom, void* rot, void* P, int32_t* prev)
 template <typename T, int N>
 int reset_cov_t(fbus_ekf_t h)
 {
-    const int grid = (h->B + BLOCK - 1) / BLOCK;
-    const double* d = h->prm.p0_diag;
-    hipLaunchKernelGGL((reset_cov_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (T*)h->recs, h->B,
-                       (T)d[0], (T)d[1], (T)d[2], (T)d[3], (T)d[4], (T)d[5]);
+    launch_reset_cov_k<T, N>(h->stream, (T*)h->recs, h->B, h->prm.p0_diag);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -568,9 +554,7 @@ int do_reset_cov(fbus_ekf_t h) { DISPATCH2(h, reset_cov_t, h); }
 template <typename T, int N>
 int snapshot_t(fbus_ekf_t h, void* nom, void* pdiag, uint8_t* applied)
 {
-    const int grid = (h->B + BLOCK - 1) / BLOCK;             // one wave per 64-filter tile, as unpack
-    hipLaunchKernelGGL((snapshot_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (const T*)h->recs, h->B, h->d_applied,
-                       (T*)nom, (T*)pdiag, applied);
+    launch_snapshot_k<T, N>(h->stream, (const T*)h->recs, h->B, h->d_applied, (T*)nom, (T*)pdiag, applied);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -579,14 +563,7 @@ int do_snapshot(fbus_ekf_t h, void* n, void* pd, uint8_t* a) { DISPATCH2(h, snap
 template <typename T, int N>
 int group_fuse_t(fbus_ekf_t h, int G, const double* logw, double* weight, int32_t* best, void* nom, void* P, void* pdiag)
 {
-    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
-    const size_t lds = group_fuse_lds<T, N>(ngw);
-    if (P)
-        hipLaunchKernelGGL((group_fuse_kernel<T, N, true>), dim3(grid), dim3(BLOCK), lds, h->stream, (const T*)h->recs, h->rec_bytes, h->B, G,
-                           logw, weight, (int*)best, (T*)nom, (T*)P, (T*)pdiag);
-    else
-        hipLaunchKernelGGL((group_fuse_kernel<T, N, false>), dim3(grid), dim3(BLOCK), lds, h->stream, (const T*)h->recs, h->rec_bytes, h->B, G,
-                           logw, weight, (int*)best, (T*)nom, (T*)nullptr, (T*)pdiag);
+    launch_group_fuse_k<T, N>(h->stream, (const T*)h->recs, h->rec_bytes, h->B, G, logw, weight, (int*)best, (T*)nom, (T*)P, (T*)pdiag);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -597,9 +574,8 @@ int do_group_fuse(fbus_ekf_t h, int G, const double* lw, double* w, int32_t* bes
 template <typename T, int N>
 int group_collapse_t(fbus_ekf_t h, int G, const int32_t* src)
 {
-    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
     h->records_warm = true;                                  // stored with the default cache policy
-    hipLaunchKernelGGL((group_collapse_kernel<T, N>), dim3(grid), dim3(BLOCK), 0, h->stream, (T*)h->recs, h->rec_bytes, h->B, G, (const int*)src);
+    launch_group_collapse_k<T, N>(h->stream, (T*)h->recs, h->rec_bytes, h->B, G, (const int*)src);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -607,10 +583,8 @@ int do_group_collapse(fbus_ekf_t h, int G, const int32_t* src) { DISPATCH2(h, gr
 template <typename T, int N>
 int group_mix_t(fbus_ekf_t h, int G, const double* logw, const double* trans, double* weight, double* logc)
 {
-    const int ngw = 64 / G, grid = (h->B / G + ngw - 1) / ngw;
     h->records_warm = true;                                  // stored with the default cache policy
-    hipLaunchKernelGGL((group_mix_kernel<T, N>), dim3(grid), dim3(BLOCK), group_mix_lds(G), h->stream, (T*)h->recs, h->rec_bytes, h->B, G,
-                       logw, trans, weight, logc);
+    launch_group_mix_k<T, N>(h->stream, (T*)h->recs, h->rec_bytes, h->B, G, logw, trans, weight, logc);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -619,41 +593,40 @@ int do_group_mix(fbus_ekf_t h, int G, const double* lw, const double* tr, double
 // per tile whatever the batch, the team setting, the noise table or the likelihood switch.  The gate table is the handle's (+inf without
 // one), the likelihood accumulator null while the sums are off.  SensorDev: the arrays every one of them takes behind its own inputs
 struct SensorDev { const double* var; int var_stride; const unsigned char* skip; void* nis; int* dof; };
-template <typename... KP, typename... A>
-int launch_sensor(fbus_ekf_t h, void (*kernel)(KP...), A... args)
+// `go(lik)` launches the update
+template <typename GO>
+int launch_sensor(fbus_ekf_t h, GO go)
 {
     h->records_warm = h->warm_after_correct;      // written through (sc1), as correct_kernel's records
-    launch_tile_k(kernel, h->stream, h->B, args...);
+    go(h->lik_on ? h->d_lik : nullptr);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
 template <typename T, int N>
 int launch_depth_t(fbus_ekf_t h, const void* z, const SensorDev& d)
 {
-    return launch_sensor(h, correct_depth_kernel<T, N>, (T*)h->recs, h->B, (const T*)z, d.var, d.var_stride, d.skip, h->d_applied, h->depth,
-                         h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
+    return launch_sensor(h, [&](double* lik) {
+        launch_depth_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, d.var, d.var_stride, d.skip, h->d_applied, h->depth, h->d_gate,
+                             (T*)d.nis, d.dof, lik);
+    });
 }
 int launch_depth(fbus_ekf_t h, const void* z, const SensorDev& d) { DISPATCH2(h, launch_depth_t, h, z, d); }
 template <typename T, int N>
 int launch_velocity_t(fbus_ekf_t h, const void* z, const void* gyro, const SensorDev& d)
 {
-    return launch_sensor(h, correct_velocity_kernel<T, N>, (T*)h->recs, h->B, (const T*)z, (const T*)gyro, d.var, d.var_stride, d.skip,
-                         h->d_applied, h->velocity, h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
+    return launch_sensor(h, [&](double* lik) {
+        launch_velocity_k<T, N>(h->stream, (T*)h->recs, h->B, (const T*)z, (const T*)gyro, d.var, d.var_stride, d.skip, h->d_applied,
+                                h->velocity, h->d_gate, (T*)d.nis, d.dof, lik);
+    });
 }
 int launch_velocity(fbus_ekf_t h, const void* z, const void* gyro, const SensorDev& d) { DISPATCH2(h, launch_velocity_t, h, z, gyro, d); }
-// m picks the instantiation
 template <typename T, int N>
 int launch_rows_t(fbus_ekf_t h, int m, const void* res, const void* H, const SensorDev& d)
 {
-    const auto go = [&](auto mc) {
-        return launch_sensor(h, correct_rows_kernel<T, N, decltype(mc)::value>, (T*)h->recs, h->B, (const T*)res, (const T*)H, d.var,
-                             d.var_stride, d.skip, h->d_applied, h->d_gate, (T*)d.nis, d.dof, h->lik_on ? h->d_lik : nullptr);
-    };
-    switch (m) {
-    case 1: return go(std::integral_constant<int, 1>{});
-    case 2: return go(std::integral_constant<int, 2>{});
-    default: return go(std::integral_constant<int, 3>{});
-    }
+    return launch_sensor(h, [&](double* lik) {
+        launch_rows_k<T, N>(h->stream, (T*)h->recs, h->B, m, (const T*)res, (const T*)H, d.var, d.var_stride, d.skip, h->d_applied, h->d_gate,
+                            (T*)d.nis, d.dof, lik);
+    });
 }
 int launch_rows(fbus_ekf_t h, int m, const void* res, const void* H, const SensorDev& d) { DISPATCH2(h, launch_rows_t, h, m, res, H, d); }
 
@@ -783,10 +756,8 @@ template <typename T>
 int launch_marker_pose_t(fbus_ekf_t h, int n, int geometry, const void* left, const void* right, void* pos,
                          void* quat, void* corners3d)
 {
-    const int grid = (n + 255) / 256;
     const int ev = timing_begin(h, FBUS_KERNEL_MARKER_POSE);
-    hipLaunchKernelGGL((marker_pose_kernel<T>), dim3(grid), dim3(256), 0, h->stream, n, geometry, (const T*)left,
-                       (const T*)right, (T*)pos, (T*)quat, (T*)corners3d, make_vc<double>(h));
+    launch_marker_pose_k<T>(h->stream, n, geometry, (const T*)left, (const T*)right, (T*)pos, (T*)quat, (T*)corners3d, make_vc<double>(h));
     timing_end(h, ev);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
@@ -795,8 +766,7 @@ int launch_marker_pose_t(fbus_ekf_t h, int n, int geometry, const void* left, co
 template <typename T, int N>
 int init_gb_t(fbus_ekf_t h, int Tn, const void* accel, const void* gyro)
 {
-    hipLaunchKernelGGL((init_gravity_bias_kernel<T, N>), dim3((h->B + 255) / 256), dim3(256), 0, h->stream, (T*)h->recs,
-                       h->B, Tn, (const T*)accel, (const T*)gyro);
+    launch_init_gravity_bias_k<T, N>(h->stream, (T*)h->recs, h->B, Tn, (const T*)accel, (const T*)gyro);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -806,9 +776,8 @@ template <typename T, int N, int D>
 int pose_init_t(fbus_ekf_t h, int M, const int32_t* ids, const void* pos, const void* quat, int what,
                 const uint8_t* mask, void* out7)
 {
-    hipLaunchKernelGGL((pose_init_kernel<T, N, D>), dim3((h->B + 255) / 256), dim3(256), 0, h->stream, (T*)h->recs, h->B,
-                       M, (const int*)ids, (const T*)pos, (const T*)quat, what, (T)h->prm.max_dist,
-                       (const unsigned char*)mask, (T*)out7, h->d_applied, make_dc<T>(h));
+    launch_pose_init_k<T, N, D>(h->stream, (T*)h->recs, h->B, M, (const int*)ids, (const T*)pos, (const T*)quat, what, h->prm.max_dist,
+                                (const unsigned char*)mask, (T*)out7, h->d_applied, make_dc<T>(h));
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -1441,13 +1410,10 @@ int imu_ema_any(fbus_ekf_t h, Transport t, int T, void* accel, void* gyro, int r
     void *da, *dg;
     Piece pc[2] = { inout_piece(accel, bytes, &da), inout_piece(gyro, bytes, &dg) };
     return run_pieces(h, t, pc, 2, [&] {
-        const int grid = (h->B + 255) / 256;
         if (h->dtype == 32)
-            hipLaunchKernelGGL((imu_ema_kernel<float>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (float*)da, (float*)dg,
-                               (float*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
+            launch_imu_ema_k<float>(h->stream, h->B, T, (float*)da, (float*)dg, (float*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
         else
-            hipLaunchKernelGGL((imu_ema_kernel<double>), dim3(grid), dim3(256), 0, h->stream, h->B, T, (double*)da, (double*)dg,
-                               (double*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
+            launch_imu_ema_k<double>(h->stream, h->B, T, (double*)da, (double*)dg, (double*)h->d_ema_carry, h->ema_has_carry ? 1 : 0);
         HIP_TRY(h, hipGetLastError());
         h->ema_has_carry = true;
         return (int)FBUS_OK;
@@ -2464,14 +2430,6 @@ int fbus_ekf_set_gate(fbus_ekf_t h, int n, const double* thresholds)
 
 // ---- per-filter noise (fbus_ekf_set_noise*, include/fbus_ekf.h) ----
 namespace {
-// B x FBUS_NOISE_COLS row-major -> fields [FBUS_NOISE_COLS][B] (fbus_ekf_set_noise_dev; one thread per entry, reads coalesced)
-__global__ void noise_fields_kernel(const double* __restrict__ rows, double* __restrict__ fields, int B)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * FBUS_NOISE_COLS) return;
-    const size_t b = i / FBUS_NOISE_COLS, c = i % FBUS_NOISE_COLS;
-    fields[c * (size_t)B + b] = rows[i];
-}
 const char* const kNoiseCols[FBUS_NOISE_COLS] = { "q_v", "q_theta", "q_ba", "q_bg", "r_pos", "r_quat", "r_pix" };
 // the table buffer, allocated once (the +inf gate table behind the fields written with it)
 int ensure_noise(fbus_ekf_t h)
@@ -2492,36 +2450,16 @@ int ensure_noise(fbus_ekf_t h)
 }
 // fbus_params' own row into every filter's table fields: what the likelihood kernels (always the tabled kind) read while the caller has
 // set no table.  Stream-ordered; noise_on is not touched.
-__global__ void noise_own_row_kernel(double* __restrict__ fields, int B, double q0, double q1, double q2, double q3, double r_pos,
-                                     double r_quat, double r_pix)
-{
-    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (size_t)B * FBUS_NOISE_COLS) return;
-    const int c = (int)(i / (size_t)B);
-    fields[i] = c == 0 ? q0 : c == 1 ? q1 : c == 2 ? q2 : c == 3 ? q3 : c == 4 ? r_pos : c == 5 ? r_quat : r_pix;
-}
 int lik_fill(fbus_ekf_t h)
 {
     int rc = ensure_noise(h);
     if (rc != FBUS_OK) return rc;
-    const size_t n = (size_t)FBUS_NOISE_COLS * h->B;
     const fbus_params& p = h->prm;
     // (r_pix may be unset -- 0 -- on a handle that never runs the pixel rows: those entry points refuse it themselves)
-    hipLaunchKernelGGL(noise_own_row_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, h->d_noise, h->B, p.q_diag[0],
-                       p.q_diag[1], p.q_diag[2], p.q_diag[3], p.r_pos, p.r_quat, p.r_pix);
+    const double row[FBUS_NOISE_COLS] = { p.q_diag[0], p.q_diag[1], p.q_diag[2], p.q_diag[3], p.r_pos, p.r_quat, p.r_pix };
+    launch_noise_own_row_k(h->stream, h->d_noise, h->B, row);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
-}
-// the sums [4][B] as doubles -> the caller's typed arrays (fbus_ekf_loglik_get*; each may be null)
-__global__ void lik_export_kernel(const double* __restrict__ acc, int B, double* __restrict__ ll, int64_t* __restrict__ rows,
-                                  int32_t* __restrict__ applied, int32_t* __restrict__ rejected)
-{
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= B) return;
-    if (ll) ll[b] = acc[b];
-    if (rows) rows[b] = (int64_t)acc[(size_t)B + b];
-    if (applied) applied[b] = (int32_t)acc[2 * (size_t)B + b];
-    if (rejected) rejected[b] = (int32_t)acc[3 * (size_t)B + b];
 }
 }  // namespace
 
@@ -2564,8 +2502,7 @@ int fbus_ekf_loglik_get_dev(fbus_ekf_t h, double* ll, int64_t* rows, int32_t* ap
     if (!h) return FBUS_ERR_INVALID;
     if (!h->d_lik) return fail(h, FBUS_ERR_INVALID, "fbus_ekf_loglik_get_dev: fbus_ekf_loglik_enable(h, 1) has not been called");
     if (!ll && !rows && !applied && !rejected) return FBUS_OK;
-    hipLaunchKernelGGL(lik_export_kernel, dim3((unsigned)((h->B + 255) / 256)), dim3(256), 0, h->stream, h->d_lik, h->B, ll, rows, applied,
-                       rejected);
+    launch_lik_export_k(h->stream, h->d_lik, h->B, ll, rows, applied, rejected);
     HIP_TRY(h, hipGetLastError());
     return FBUS_OK;
 }
@@ -2625,8 +2562,7 @@ int fbus_ekf_set_noise_dev(fbus_ekf_t h, const double* table)
     if (!table) { h->noise_on = false; return h->lik_on ? lik_fill(h) : FBUS_OK; }
     int rc = ensure_noise(h);
     if (rc != FBUS_OK) return rc;
-    const size_t n = (size_t)FBUS_NOISE_COLS * h->B;
-    hipLaunchKernelGGL(noise_fields_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, table, h->d_noise, h->B);
+    launch_noise_fields_k(h->stream, table, h->d_noise, h->B);
     HIP_TRY(h, hipGetLastError());
     h->noise_on = true;
     return FBUS_OK;
@@ -3054,13 +2990,8 @@ int fbus_ekf_l0_eval(fbus_ekf_t h, int op, int n, const void* a, const void* b, 
     Piece pc[3] = { in_piece(a, (size_t)n * wa[op] * es, &da), in_piece(wb[op] ? b : nullptr, (size_t)n * wb[op] * es, &db),
                     out_piece(out, (size_t)n * wo[op] * es, &dout) };
     return run_pieces(h, STAGED, pc, 3, [&] {
-        const int grid = (n + 255) / 256;
-        if (h->dtype == 32)
-            hipLaunchKernelGGL((l0_eval_kernel<float>), dim3(grid), dim3(256), 0, h->stream, op, n, (const float*)da, (const float*)db,
-                               (float*)dout);
-        else
-            hipLaunchKernelGGL((l0_eval_kernel<double>), dim3(grid), dim3(256), 0, h->stream, op, n, (const double*)da, (const double*)db,
-                               (double*)dout);
+        if (h->dtype == 32) launch_l0_eval_k<float>(h->stream, op, n, (const float*)da, (const float*)db, (float*)dout);
+        else launch_l0_eval_k<double>(h->stream, op, n, (const double*)da, (const double*)db, (double*)dout);
         HIP_TRY(h, hipGetLastError());
         return (int)FBUS_OK;
     });

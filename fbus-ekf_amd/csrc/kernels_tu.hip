@@ -22,6 +22,7 @@
 //  19 10's window with per-filter q, r_pos, r_quat (frames_kernel with TrajOut and NoiseIn; fp32 only; the window without trajectory
 //     outputs and the fused frame of a tabled handle run here too, with null outputs and F = 1)
 //  20 11's window with per-filter q and r_pix / r_pos (frame_meas_kernel with TrajOut and NoiseIn; fp32 only; likewise)
+//  21-26 are small_tu.hip's: state I/O, hypothesis groups, sensor updates, screening, NEES and draws, and the kernels built once
 // A launcher is written once for its kernel and takes the kernel's trailing pack; the families that extend another (10-18) instantiate the
 // launcher of the family they extend with their pack (FBUS_TU_PACK), and what they choose differently is an `if constexpr` on the pack.
 // gfx950 only.

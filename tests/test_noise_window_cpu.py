@@ -49,9 +49,11 @@ def test_unit_count_is_the_expansion_of_the_table():
     f32 = len(b.FAMILIES)
     f64 = sum(1 for _, _, on in b.FAMILIES.values() if on)
     units = b.units()
-    assert len(units) == 1 + 2 * (f32 + f64) == 61
+    # every row for fp32, the rows marked so for fp64, each for N = 18 and N = 15; the host unit; the kernels built once
+    assert len(units) == 2 * (f32 + f64) + 1 + 1 == 82
     names = [u[0] for u in units]
     assert len(set(names)) == len(names)
+    assert "main" in names and "common" in names
     fam19 = [n for n, (code, _, _) in b.FAMILIES.items() if code == 19][0]
     fam20 = [n for n, (code, _, _) in b.FAMILIES.items() if code == 20][0]
     for fam, code in ((fam19, 19), (fam20, 20)):
@@ -60,4 +62,24 @@ def test_unit_count_is_the_expansion_of_the_table():
             defs = [u[2] for u in units if u[0] == f"f32_{n}_{fam}"][0]
             assert f"-DFBUS_TU_FAMILY={code}" in defs and "-DFBUS_TU_T=float" in defs and f"-DFBUS_TU_N={n}" in defs
     # the README states the count
-    assert "61 units" in open(os.path.join(ROOT, "README.md")).read()
+    assert "82 units" in open(os.path.join(ROOT, "README.md")).read()
+
+
+def test_the_host_unit_holds_no_kernel_and_the_small_families_take_the_base_flags():
+    main = open(os.path.join(ROOT, "fbus-ekf_amd", "csrc", "fbus_ekf.hip")).read()
+    assert "__global__" not in main and "hipLaunchKernelGGL" not in main
+    included = re.findall(r'#include "(ekf_\w+\.hpp)"', main)
+    assert included and set(included) <= {"ekf_launch.hpp", "ekf_route.hpp"}
+    b = _build_module()
+    small = {"state", "group", "sensor", "screen", "report"}
+    assert small <= set(b.FAMILIES) and all(b.FAMILIES[f][2] for f in small)        # fp64 records too
+    t_of = {"f32": "float", "f64": "double"}
+    seen = 0
+    for name, src, defs in b.units():
+        tn, _, rest = name.partition("_")
+        n, _, fam = rest.partition("_")
+        if fam in small:
+            assert defs == [f"-DFBUS_TU_T={t_of[tn]}", f"-DFBUS_TU_N={n}", f"-DFBUS_TU_FAMILY={b.FAMILIES[fam][0]}"], name
+            assert os.path.basename(src) == "small_tu.hip"
+            seen += 1
+    assert seen == 4 * len(small)

@@ -6,6 +6,7 @@ the domain of the re-acquisition cells of tests/test_rows_gpu.py."""
 import ctypes as C
 import importlib.util
 import os
+import re
 
 import numpy as np
 import pytest
@@ -209,15 +210,24 @@ def test_the_four_symbols_are_declared_exported_and_refuse_a_null_handle(repo_ro
     assert f"#define FBUS_ROWS_MAX {capi.ROWS_MAX}\n" in hdr and capi.ROWS_MAX == W.ROWS_MAX == 3
 
 
-def test_the_build_still_has_61_units(repo_root):
+def test_the_kernel_builds_in_its_family_unit(repo_root):
     spec = importlib.util.spec_from_file_location("fbus_build_rows", os.path.join(repo_root, "fbus-ekf_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    assert len(b.units()) == 61
-    assert any(h.endswith("ekf_rows.hpp") for h in b.HEADERS)              # a change of the kernel rebuilds the library
+    assert any(h.endswith("ekf_rows.hpp") for h in b.HEADERS)            # a change of the kernel rebuilds the library
     assert any(h.endswith("ekf_sensor.hpp") for h in b.HEADERS)            # ... and so does one of the steps it shares
-    main = open(os.path.join(repo_root, "fbus-ekf_amd", "csrc", "fbus_ekf.hip")).read()
-    assert '#include "ekf_rows.hpp"' in main                                # instantiated from the main unit: no new family
+    csrc = os.path.join(repo_root, "fbus-ekf_amd", "csrc")
+    units = [u for u in b.units() if u[0].endswith("_sensor")]
+    assert sorted(u[0] for u in units) == ["f32_15_sensor", "f32_18_sensor", "f64_15_sensor", "f64_18_sensor"]
+    assert {u[1] for u in units} == {os.path.join(csrc, "small_tu.hip")}
+    # the family's branch of the unit source includes the header (over the steps the three sensor updates share): that unit instantiates the kernel
+    code = b.FAMILIES["sensor"][0]
+    tu = open(os.path.join(csrc, "small_tu.hip")).read()
+    assert re.search(rf'#elif FBUS_TU_FAMILY == {code}\n(?:#include "ekf_\w+\.hpp"\n)*?#include "ekf_rows.hpp"\n', tu)
+    assert all(f"-DFBUS_TU_FAMILY={code}" in u[2] for u in units)
+    assert '#include "ekf_sensor.hpp"' in open(os.path.join(csrc, "ekf_rows.hpp")).read()
+    main = open(os.path.join(csrc, "fbus_ekf.hip")).read()
+    assert '#include "ekf_rows.hpp"' not in main                                  # ... and the host unit does not
 
 
 def test_the_python_and_cxx_layers_carry_the_methods(repo_root):

@@ -1,10 +1,11 @@
 """CPU suite of the per-marker screen (include/fbus_ekf.h, fbus_ekf_screen_markers*; added under FBUS_ABI_VERSION 8 without a bump): the two
-symbols, their prototypes and null-handle checks, the unit count of the build, the Python and C++ layers, and the algebra the kernels
+symbols, their prototypes and null-handle checks, the unit that builds the kernels, the Python and C++ layers, and the algebra the kernels
 evaluate the per-marker statistic by -- the Cholesky factor of P_JJ once per filter, then per marker |D^-1 C' b|^2 -- restated in numpy
 against r' (H P H' + R)^-1 r of one marker's rows."""
 import ctypes as C
 import importlib.util
 import os
+import re
 
 import numpy as np
 import pytest
@@ -31,14 +32,22 @@ def test_the_two_symbols_are_declared_exported_prototyped_and_refuse_a_null_hand
         assert getattr(lib, n)(None, capi.SCREEN_PIXELS, 0, None, None, None, 0, None, None, None, None, None) == 1
 
 
-def test_the_build_still_has_61_units(repo_root):
+def test_the_kernel_builds_in_its_family_unit(repo_root):
     spec = importlib.util.spec_from_file_location("fbus_build_screen", os.path.join(repo_root, "fbus-ekf_amd", "build.py"))
     b = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(b)
-    assert len(b.units()) == 61
-    assert any(h.endswith("ekf_screen.hpp") for h in b.HEADERS)            # a change of the kernels rebuilds the library
-    main = open(os.path.join(repo_root, "fbus-ekf_amd", "csrc", "fbus_ekf.hip")).read()
-    assert '#include "ekf_screen.hpp"' in main                              # instantiated from the main unit: no new family
+    assert any(h.endswith("ekf_screen.hpp") for h in b.HEADERS)            # a change of the kernel rebuilds the library
+    csrc = os.path.join(repo_root, "fbus-ekf_amd", "csrc")
+    units = [u for u in b.units() if u[0].endswith("_screen")]
+    assert sorted(u[0] for u in units) == ["f32_15_screen", "f32_18_screen", "f64_15_screen", "f64_18_screen"]
+    assert {u[1] for u in units} == {os.path.join(csrc, "small_tu.hip")}
+    # the family's branch of the unit source includes the header: that unit instantiates the kernel
+    code = b.FAMILIES["screen"][0]
+    tu = open(os.path.join(csrc, "small_tu.hip")).read()
+    assert re.search(rf'#elif FBUS_TU_FAMILY == {code}\n(?:#include "ekf_\w+\.hpp"\n)*?#include "ekf_screen.hpp"\n', tu)
+    assert all(f"-DFBUS_TU_FAMILY={code}" in u[2] for u in units)
+    main = open(os.path.join(csrc, "fbus_ekf.hip")).read()
+    assert '#include "ekf_screen.hpp"' not in main                                  # ... and the host unit does not
 
 
 def test_the_python_and_cxx_layers_carry_the_method(repo_root):
