@@ -179,6 +179,14 @@ template <typename T, int N, int DIALECT>
 void launch_screen_pose_k(hipStream_t st, const T* recs, int B, int M, const int* ids, const T* pos, const T* quat, const double* noise,
                           const unsigned char* skip, const DevConst<T>& dc, const ScreenOut<T>& out);
 
+// ---- predicted corner pixels (ekf_project.hpp; family "screen"): one wave per tile ----------------------------------------------------------
+// left, right [B][M][8] in T, cov_left, cov_right [B][M][4][3], view [B][M]; each may be null (CAM = 1: right and cov_right are not read)
+template <typename T> struct ProjectOut { T* left; T* right; double* cov_left; double* cov_right; unsigned char* view; };
+// CAM: 1 = left camera, 2 = stereo; r_pix: ignored with a noise table
+template <typename T, int N, int CAM>
+void launch_project_k(hipStream_t st, const T* recs, int B, int M, const int* ids, bool square_port, double size, double r_pix,
+                      const double* noise, const unsigned char* skip, const short* id2slot, const MeasConst& mc, const ProjectOut<T>& out);
+
 // ---- NEES and draws (ekf_nees.hpp, ekf_sample.hpp; family "report"): one wave per tile ------------------------------------------------------
 struct NeesOut { double* nees; double* err; double* lnp; };     // [B][FBUS_NEES_COLS], [B][N], [B]; each may be null
 struct SampleOut { double* state; unsigned char* drawn; };      // [S][B][19], [B]; each may be null

@@ -1728,6 +1728,54 @@ int sample_any(fbus_ekf_t h, Transport t, int S, const double* xi, const uint8_t
     });
 }
 
+// ---- predicted corner pixels with their innovation covariance (ekf_project.hpp): fbus_ekf_project_markers / _dev -------------------------------
+// One launcher for both forms and one route, as the screening has.  Read-only.
+struct ProjectDst { void* left; void* right; double* cov_left; double* cov_right; uint8_t* view; };
+template <typename T, int N, int D>
+int launch_project_t(fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, const ProjectDst& o)
+{
+    const ProjectOut<T> out{ (T*)o.left, (T*)o.right, o.cov_left, o.cov_right, (unsigned char*)o.view };
+    const double* noise = h->noise_on ? h->d_noise : nullptr;
+    const bool sq = route_key(h).square_port;
+    const auto go = [&](auto cam) {
+        launch_project_k<T, N, decltype(cam)::value>(h->stream, (const T*)h->recs, h->B, M, (const int*)ids, sq, h->prm.marker_size, h->prm.r_pix,
+                                                     noise, (const unsigned char*)skip, h->d_id2slot, make_mc(h), out);
+    };
+    if (cameras == 2) go(std::integral_constant<int, 2>{});
+    else go(std::integral_constant<int, 1>{});
+    HIP_TRY(h, hipGetLastError());
+    return FBUS_OK;
+}
+int launch_project(fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, const ProjectDst& o)
+{
+    DISPATCH(h, launch_project_t, h, M, ids, cameras, skip, o);
+}
+// (the order of the tests is part of the interface: include/fbus_ekf.h)
+int project_any(fbus_ekf_t h, Transport t, int M, const int32_t* ids, int cameras, const uint8_t* skip, void* left, void* right,
+                double* cov_left, double* cov_right, uint8_t* view)
+{
+    if (!h) return FBUS_ERR_INVALID;
+    const std::string where = report_name("project_markers", t);
+    if (M < 1 || M > FBUS_MAX_VISIBLE)
+        return fail(h, FBUS_ERR_INVALID, where + ": M = " + std::to_string(M) + " outside 1.." + std::to_string(FBUS_MAX_VISIBLE));
+    if (!ids) return fail(h, FBUS_ERR_INVALID, where + ": ids is NULL");
+    if (cameras != 1 && cameras != 2)
+        return fail(h, FBUS_ERR_INVALID, where + ": cameras = " + std::to_string(cameras) + " is neither 1 (left) nor 2 (stereo)");
+    if (cameras == 1) { right = nullptr; cov_right = nullptr; }                 // (not written: may be anything)
+    if (t == DEV && !(points_aligned(left, right) && points_aligned(cov_left, cov_right)))
+        return fail(h, FBUS_ERR_INVALID, where + ": left / right / cov_left / cov_right must be 16-byte aligned device pointers");
+    if (!(h->prm.r_pix > 0)) return fail(h, FBUS_ERR_INVALID, where + ": r_pix must be positive");
+    const size_t es = esize(h), B = (size_t)h->B, BM = B * M;
+    const void *di, *ds;
+    void *dl, *dr, *dcl, *dcr, *dv;
+    Piece pc[7] = { in_piece(ids, BM * sizeof(int32_t), &di), in_piece(skip, B, &ds), out_piece(left, BM * 8 * es, &dl),
+                    out_piece(right, BM * 8 * es, &dr), out_piece(cov_left, BM * 12 * sizeof(double), &dcl),
+                    out_piece(cov_right, BM * 12 * sizeof(double), &dcr), out_piece(view, BM, &dv) };
+    return report_any(h, t, where, true, pc, 7, [&] {
+        return launch_project(h, M, (const int32_t*)di, cameras, (const uint8_t*)ds, ProjectDst{ dl, dr, (double*)dcl, (double*)dcr, (uint8_t*)dv });
+    });
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------------
@@ -2667,6 +2715,16 @@ int fbus_ekf_sample(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, 
 int fbus_ekf_sample_dev(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn)
 {
     return sample_any(h, DEV, S, xi, skip, state, drawn);
+}
+int fbus_ekf_project_markers(fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, void* left, void* right,
+                             double* cov_left, double* cov_right, uint8_t* view)
+{
+    return project_any(h, STAGED, M, ids, cameras, skip, left, right, cov_left, cov_right, view);
+}
+int fbus_ekf_project_markers_dev(fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, void* left, void* right,
+                                 double* cov_left, double* cov_right, uint8_t* view)
+{
+    return project_any(h, DEV, M, ids, cameras, skip, left, right, cov_left, cov_right, view);
 }
 
 int fbus_ekf_set_velocity_sensor(fbus_ekf_t h, const double mount[9], const double lever[3])

@@ -5,7 +5,8 @@
 //  22 group   hypothesis groups: fuse, collapse, mix (ekf_group.hpp)
 //  23 sensor  the streamed sensor updates: depth, velocity, rows, and the steps they share (ekf_depth.hpp, ekf_velocity.hpp, ekf_rows.hpp
 //             over ekf_sensor.hpp)
-//  24 screen  per-marker screening: pixel / corner rows and pose rows (ekf_screen.hpp)
+//  24 screen  per-marker screening: pixel / corner rows and pose rows (ekf_screen.hpp); predicted corner pixels with their innovation
+//             covariance (ekf_project.hpp)
 //  25 report  NEES against a truth state and draws from every filter's Gaussian: one record stream and one column step (ekf_nees.hpp,
 //             ekf_sample.hpp)
 // and once with -DFBUS_TU_FAMILY=26 alone (unit "common"):
@@ -25,6 +26,7 @@
 #include "ekf_velocity.hpp"
 #include "ekf_rows.hpp"
 #elif FBUS_TU_FAMILY == 24
+#include "ekf_project.hpp"
 #include "ekf_screen.hpp"
 #elif FBUS_TU_FAMILY == 25
 #include "ekf_sample.hpp"
@@ -97,6 +99,8 @@ FBUS_INST(launch_screen_meas_k<FBUS_TN, SCREEN_PIX_STEREO>)
 FBUS_INST(launch_screen_meas_k<FBUS_TN, SCREEN_CORNERS>)
 FBUS_INST(launch_screen_pose_k<FBUS_TN, DIALECT_MATLAB>)
 FBUS_INST(launch_screen_pose_k<FBUS_TN, DIALECT_CPP>)
+FBUS_INST(launch_project_k<FBUS_TN, 1>)
+FBUS_INST(launch_project_k<FBUS_TN, 2>)
 #elif FBUS_TU_FAMILY == 25
 FBUS_INST(launch_nees_k<FBUS_TN>)
 FBUS_INST(launch_sample_k<FBUS_TN>)

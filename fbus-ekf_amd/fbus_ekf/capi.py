@@ -182,6 +182,8 @@ def load_library():
         "fbus_ekf_nees_dev": ([H, vp, u8p, vp, vp, vp], C.c_int),
         "fbus_ekf_sample": ([H, C.c_int, vp, u8p, vp, vp], C.c_int),
         "fbus_ekf_sample_dev": ([H, C.c_int, vp, u8p, vp, vp], C.c_int),
+        "fbus_ekf_project_markers": ([H, C.c_int, ip, C.c_int, u8p, vp, vp, vp, vp, u8p], C.c_int),
+        "fbus_ekf_project_markers_dev": ([H, C.c_int, ip, C.c_int, u8p, vp, vp, vp, vp, u8p], C.c_int),
         "fbus_ekf_set_velocity_sensor": ([H, C.POINTER(C.c_double), C.POINTER(C.c_double)], C.c_int),
         "fbus_ekf_correct_velocity": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),
         "fbus_ekf_correct_velocity_dev": ([H, vp, vp, vp, C.c_int, u8p], C.c_int),

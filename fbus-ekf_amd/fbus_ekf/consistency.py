@@ -97,3 +97,17 @@ def draw(flt, S, generator=None):
     import torch
     xi = torch.randn((int(S), flt.B, flt.N), dtype=torch.float64, device=torch.device("cuda", flt.device), generator=generator)
     return flt.sample(xi), xi
+
+
+def observe(truth_filter, ids, sigma, generator=None, cameras=2):
+    """The pixels a frame would hold if truth_filter's states were the truth: project_markers() on that handle plus N(0, sigma^2) per
+    coordinate, on the device.  ids: (B, M) int32 device tensor of the markers asked for.  Returns (ids_seen, left, right): ids_seen =
+    ids with -1 where a marker does not have all 4 x cameras corners in view, left / right (right None for cameras=1) in the record
+    type -- ready inputs for correct_pixels on ANOTHER handle of the same batch and record type.  With draw() and nees() this closes
+    the Monte-Carlo loop on the device: sample -> set_state on a truth handle -> observe -> correct_pixels -> nees."""
+    import torch
+    left, right, view, _, _ = truth_filter.project_markers(ids, cameras=cameras, cov=False)
+    full = 0xFF if cameras == 2 else 0x0F
+    ids_seen = torch.where(view == full, ids, torch.full_like(ids, -1))
+    noisy = lambda a: a + float(sigma) * torch.randn(a.shape, dtype=a.dtype, device=a.device, generator=generator)
+    return ids_seen, noisy(left), (noisy(right) if right is not None else None)

@@ -804,6 +804,51 @@ class BatchedFilter:
         self._order_out(cur)
         return out
 
+    # ---- predicted corner pixels with their innovation covariance (include/fbus_ekf.h: fbus_ekf_project_markers) -----------------
+    def project_markers(self, ids, cameras=2, skip=None, cov=True):
+        """Where the four corners of every listed marker appear in the left (cameras=1) or in both images (2) given each filter's
+        state -- the h(x) of correct_pixels as an output --, which of them are in view, and the innovation covariance
+        S = H P_JJ H' + r_pix I of every projection (r_pix: the filter's own row when a noise table is set).  ids: (B, M) int32, -1
+        or an id outside the map = absent.  Returns (left, right, view, cov_left, cov_right): left, right (B, M, 8) in the record
+        type, x0 y0 .. x3 y3 -- the arrays correct_pixels takes --, view (B, M) uint8 (bit k: left corner k in view, bit 4 + k: right
+        corner k), cov_* (B, M, 4, 3) float64 = (S_uu, S_uv, S_vv) per corner; right and cov_right are None for cameras=1, both
+        cov_* for cov=False.  A projection out of view, a slot that is absent and a skipped filter (skip: (B,) uint8) give zeros and
+        clear bits.  numpy arrays for host inputs, device tensors (stream-ordered, capturable) for device inputs.  Read-only: no
+        record, flag or likelihood sum changes.  gating.search_window turns cov_* into a search box."""
+        B = self.B
+        if cameras not in (1, 2):
+            raise ValueError(f"project_markers: cameras = {cameras} is neither 1 (left) nor 2 (stereo)")
+        stereo, cur = cameras == 2, None
+        if _is_dev(ids):
+            import torch
+            transport, M = "_dev", ids.numel() // B
+            self._rows_checked(B, M, ids, (), skip)
+            if ids.dtype != torch.int32:
+                raise ValueError(f"project_markers: ids must be int32, got {ids.dtype}")
+            dt = torch.float32 if self.dtype == 32 else torch.float64
+            new = lambda shape, t: torch.empty(shape, dtype=t, device=ids.device)
+            u8, f64 = torch.uint8, torch.float64
+            cur = self._order_in(ids, skip)
+        else:
+            transport = ""
+            ids = np.ascontiguousarray(ids, np.int32).reshape(B, -1)
+            M = ids.shape[1]
+            skip = None if skip is None else self._host(skip, (B,), np.uint8)
+            dt, u8, f64 = self.np_dtype, np.uint8, np.float64
+            new = lambda shape, t: np.empty(shape, t)
+        left, view = new((B, M, 8), dt), new((B, M), u8)
+        right = new((B, M, 8), dt) if stereo else None
+        cov_left = new((B, M, 4, 3), f64) if cov else None
+        cov_right = new((B, M, 4, 3), f64) if cov and stereo else None
+        if transport:
+            self._keep += [o for o in (left, right, view, cov_left, cov_right) if o is not None]
+        name = "project_markers" + transport
+        rc = getattr(self._lib, "fbus_ekf_" + name)(self._h, M, self._p(ids), int(cameras), self._p(skip), self._p(left), self._p(right),
+                                                    self._p(cov_left), self._p(cov_right), self._p(view))
+        self._check(rc, name)
+        self._order_out(cur)
+        return left, right, view, cov_left, cov_right
+
     # ---- consistency against a truth state (include/fbus_ekf.h: fbus_ekf_nees) ----------------------------------------------
     def nees(self, truth, skip=None, err=False, lnp=False):
         """The normalised estimation error squared of every filter against `truth`, (B, 19) float64 in get_state()'s order

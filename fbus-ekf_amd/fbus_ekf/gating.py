@@ -72,6 +72,17 @@ def chi2_ppf(prob, d):
     return x
 
 
+def search_window(cov, prob=0.997):
+    """the half-widths (..., 2) of the axis-aligned box around the prob ellipse of a predicted image point: cov (..., 3) =
+    (S_uu, S_uv, S_vv) as BatchedFilter.project_markers returns it -> sqrt(chi2_ppf(prob, 2) (S_uu, S_vv)); 0 where the covariance
+    is 0 (a projection that is not in view).  numpy array or torch tensor, returned in kind."""
+    k = chi2_ppf(prob, 2)
+    if hasattr(cov, "data_ptr"):
+        import torch
+        return torch.sqrt(k * cov[..., [0, 2]])
+    return np.sqrt(k * np.asarray(cov, np.float64)[..., [0, 2]])
+
+
 def chi2_gate(prob, max_dof=GATE_MAX_DOF):
     """the gate table of max_dof + 1 entries: thr[d] = chi2_ppf(prob, d), thr[0] = inf (a filter without rows is never rejected)"""
     thr = np.empty(int(max_dof) + 1, np.float64)

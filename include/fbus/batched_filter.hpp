@@ -247,6 +247,18 @@ public:
     void sample_dev(int S, const double* xi, double* state, uint8_t* drawn = nullptr, const uint8_t* skip = nullptr)
     { check(fbus_ekf_sample_dev(h_, S, xi, skip, state, drawn), "sample_dev"); }
 
+    // ---- predicted corner pixels with their innovation covariance (fbus_ekf.h): the h(x) of correct_pixels as an output.  ids: batch() x M;
+    // cameras: 1 = left, 2 = stereo; left, right: batch() x M x 8 (x0 y0 .. x3 y3, the arrays correct_pixels takes); cov_left, cov_right:
+    // batch() x M x 4 x 3, ALWAYS double, (S_uu, S_uv, S_vv) per corner of S = H P_JJ H' + r_pix I; view: batch() x M bytes, bit k = left
+    // corner k in view, bit 4 + k = right corner k.  A projection out of view, an absent slot and a skipped filter give zeros.  Each output
+    // may be null.  Read-only.
+    void project_markers(int M, const int32_t* ids, int cameras, Real* left, Real* right = nullptr, uint8_t* view = nullptr,
+                         double* cov_left = nullptr, double* cov_right = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_project_markers(h_, M, ids, cameras, skip, left, right, cov_left, cov_right, view), "project_markers"); }
+    void project_markers_dev(int M, const int32_t* ids, int cameras, Real* left, Real* right = nullptr, uint8_t* view = nullptr,
+                             double* cov_left = nullptr, double* cov_right = nullptr, const uint8_t* skip = nullptr)
+    { check(fbus_ekf_project_markers_dev(h_, M, ids, cameras, skip, left, right, cov_left, cov_right, view), "project_markers_dev"); }
+
     // ---- the body-velocity (DVL) update (fbus_ekf.h; no reference counterpart).  Three rows per filter,
     // h = C (R' v + (gyro - bg) x lever); at the instrument's own rate, between camera frames:
     //   loop { predict_n(imu since the last reading); correct_velocity(z, gyro, var); }

@@ -116,7 +116,9 @@ int fbus_params_validate(const fbus_params* prm, char* msg, size_t msg_len);
  *      fbus_ekf_correct_rows[_dev|_nis|_nis_dev] (the general linearised measurement update: residual and Jacobian rows from the
  *      caller): added under 8 without a bump;
  *      fbus_ekf_nees[_dev] (NEES, error and log-density against a truth state; a read-only kernel): added under 8 without a bump;
- *      fbus_ekf_sample[_dev] (draws from every filter's own Gaussian N(estimate, P); a read-only kernel): added under 8 without a bump
+ *      fbus_ekf_sample[_dev] (draws from every filter's own Gaussian N(estimate, P); a read-only kernel): added under 8 without a bump;
+ *      fbus_ekf_project_markers[_dev] (predicted corner pixels, their innovation covariance and visibility; a read-only kernel): added
+ *      under 8 without a bump
  *   7  fbus_ekf_frames_fused_traj_dev, fbus_ekf_frames_meas_fused_traj_dev, fbus_ekf_snapshot_dev (struct unchanged)
  *   6  round 6: fbus_ekf_*_async, fbus_ekf_async_inputs_consumed / _stats, fbus_ekf_host_register / _unregister (struct unchanged)
  *   5  round 5: fbus_ekf_frame_meas_fused_dev, fbus_ekf_frames_meas_fused_dev (struct unchanged)
@@ -1028,6 +1030,53 @@ int fbus_ekf_nees    (fbus_ekf_t h, const double* truth, const uint8_t* skip, do
 #define FBUS_SAMPLE_MAX 256
 int fbus_ekf_sample_dev(fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn);
 int fbus_ekf_sample    (fbus_ekf_t h, int S, const double* xi, const uint8_t* skip, double* state, uint8_t* drawn);
+
+/* ---- predicted corner pixels with their innovation covariance: the measurement model as an output ---------------------------------------
+ * fbus_ekf_correct_pixels, the frame entry points and fbus_ekf_screen_markers evaluate h(x) -- map corner -> port -> image point -- and
+ * its Jacobian inside their folds and never hand it out.  This call does: where the four corners of a marker of the map appear in the
+ * left (and right) image given each filter's state, how uncertain that prediction is, and which corners are in view at all.  Uses: a
+ * search window for the detector (the reference's front end searches the whole image and rejects detections by apparent motion,
+ * C++/src/vision.cpp:825-853); pixels of a truth state for a Monte-Carlo run that stays on the device (fbus_ekf_sample -> a handle that
+ * holds the truths -> this call -> fbus_ekf_correct_pixels_dev on another handle -> fbus_ekf_nees_dev); the per-corner mask behind a dof.
+ *
+ *   ids       [B][M] int32, M in 1..FBUS_MAX_VISIBLE, with the meaning every update gives it: -1 or an id outside the map = absent
+ *   cameras   1 = left camera only, 2 = stereo.  With 1, right and cov_right are not written and may be anything, and bits 4..7 of view
+ *             are 0
+ *   skip      [B] bytes, nonzero = the filter produces zeros; may be NULL
+ *   left, right          [B][M][8] in the handle's dtype: x0 y0 .. x3 y3 of corners.txt -- bit for bit the arrays
+ *                        fbus_ekf_correct_pixels_dev takes
+ *   cov_left, cov_right  [B][M][4][3] double: (S_uu, S_uv, S_vv) per corner
+ *   view      [B][M] bytes: bit k is set when left corner k is in view, bit 4 + k when right corner k is
+ *   Every output may be NULL, in which case it is not written.  A call with all outputs NULL is legal and launches nothing.
+ *
+ * For filter b, a slot whose id is in the map, camera c and corner k:
+ * 1. X = M_c (R'(c_w - p) - pil) + t_c with R the record's CARRIED rotation, pil = R'(R P_IL) taken literally, c_w = P_m + R_m c_k,
+ *    c_k = (0,0,0), (0,s,0), (s,s,0), (s,0,0), s = marker_size; M_c, t_c take the IMU frame into camera c's refraction frame.  This is
+ *    the h of fbus_ekf_correct_pixels, not a new model.
+ * 2. The corner is in view iff z_w = n.X - d_air - d_glass > 0 and |X - (n.X) n|^2 < klim z_w^2, klim = 0.81 a1^2 / (1 - a1^2),
+ *    a1 = n_air / n_water: in front of the port and inside 0.9 of its field of view.  Both comparisons are false for NaN.
+ * 3. uv = pi(X), the forward projection of the update at the update's precision (a closed-form start in fp32, then one Halley step of
+ *    the port equation in double for fp32 records, two for fp64), rounded once to the handle's dtype when stored.
+ * 4. S = H P_JJ H' + r_pix I_2 in double for both record types; H: the 2 x 6 Jacobian rows (p and theta columns) of that projection,
+ *    [ -(R a)' | (a x R'(c_w - p))' ] with a' = d pi / d X M_c, in image coordinates (u, v); r_pix: the filter's own row when a noise
+ *    table is set (the rule of fbus_ekf_screen_markers, item 3).
+ * 5. A projection that is not in view gets 0 in its coordinates and covariance and a clear bit; so does every projection of a slot
+ *    whose id is not in the map, and of a skipped filter.  Every slot is written: the caller needs no memset.
+ * 6. Nothing else is written: the records stay byte-identical, and so do the applied flags, the likelihood sums, the noise table,
+ *    prev_id and the carried EMA sample.
+ * 7. The argument check runs before anything is staged, in this order, each but the first with the entry point's name in
+ *    fbus_ekf_last_error: NULL handle (FBUS_ERR_INVALID, no text); M out of range; NULL ids; cameras not 1 or 2; (_dev) left / right /
+ *    cov_left / cov_right not 16-byte aligned; r_pix <= 0; an output that overlaps the records (the rule of fbus_ekf_snapshot_dev).
+ * 8. _dev: device pointers, stream-ordered, capturable.  The host form stages, launches, waits and copies back; it is refused between
+ *    graph_begin and graph_end.  Without an _async form.
+ * 9. One kernel family, one wave per 64-filter tile at every batch size: fbus_ekf_set_team, the policy batch, the noise table (beyond
+ *    r_pix) and the likelihood switch do not change the route, and two calls on the same inputs are bit-identical whatever the batch
+ *    size or the filter's position in it.
+ * Added under ABI 8 without a bump: detect the feature by symbol. */
+int fbus_ekf_project_markers_dev(fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, void* left, void* right,
+                                 double* cov_left, double* cov_right, uint8_t* view);
+int fbus_ekf_project_markers    (fbus_ekf_t h, int M, const int32_t* ids, int cameras, const uint8_t* skip, void* left, void* right,
+                                 double* cov_left, double* cov_right, uint8_t* view);
 
 /* ---- L0 helpers on the device (unit-test hook) -------------------------------- */
 /* Evaluates ONE of the device inline helpers the kernels are built from for n independent inputs -- what
