@@ -726,6 +726,8 @@ def test_long_run_stability_and_degenerate_inputs():
         assert np.abs(g_nom[:, 0:3] - nom[:, 0:3]).max() < 0.05          # held at the measured pose
         assert np.abs(g_nom[:, 16:19] - [9.8, 0, 0]).max() < 0.5           # gravity estimate converged near truth
         # degenerate inputs: gyro == gyro bias (w == 0) and a measurement equal to the prediction
+        # (per-call predict, Matlab dialect, finiteness only: tests/test_imu_edges_gpu.py holds these and the other edges of predict's
+        # domain against the oracle on every route that predicts, in both dialects)
         flt.set_state(nom, rot, P, prev)
         acc, _ = synth.imu_samples(0, B, 0, 1, nom)
         flt.predict(acc[0], nom[:, 13:16].astype(np.float32).astype(np.float64), DT)
